@@ -18,7 +18,16 @@ There is no collective on the data path; ONE all_gather of the poses of all K st
 
 Launch: `python bench.py --gpus N --steps K --warmup W`; for N > 1 under torch.distributed.run (one rank per GPU, RCCL).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with, besides the required keys:
+A plain run sets up, warms up, times the K steps and prints ONE JSON line on rank 0: `metric`, `value` (sequences/s), `unit`,
+`higher_is_better`, `dtype`, `ms_per_step` (wall milliseconds of one timed step) and the run's `config`.  `--dump-outputs DIR` writes what the
+timed path handed back for its LAST step, after the timed region: DIR/pose.npy (the all_gathered poses of that step's sequences,
+[sequences, 20, 9] float32) and DIR/ggs_stats.npy (rank 0's GGS statistics of its shard of that step, [10 guided steps, sequences, 5, 4]
+float32).  The inputs are seeded (z, noise; the matches are synthesised from the engine's own unguided model mean), so the same arguments
+give the same inputs from run to run of one build, and of two builds whose unguided sampling computes the same bits.  Two builds whose
+denoiser arithmetic differs also get slightly different matches: an output-for-output comparison of such builds then includes that
+input drift, and needs a tolerance rather than bit equality.
+
+`--full` adds, outside the timed region, everything else the line has carried (each leg still has its own --no-* switch):
   roofline        dominant kernel (pd_ggs_lane_kernel<14>): `frac` = algorithmic fp32 FLOPs of ONE launch / the MEAN duration of the launches
                   the timed region itself ran (every one of them stamped by the kernel: pd_ggs_launch_stamps) / 157.3 TFLOP/s (SURVEY 8d
                   prices it against the fp32 vector ALU); sub-objects `in_pipe` (those launches), `alone` (a launch on an idle chip,
@@ -32,12 +41,14 @@ Prints ONE JSON line on rank 0 (contract in the task statement) with, besides th
   fresh_inputs    the same pipe with every pass uploading NEW z / noise / matches inside the timed region
                   (pinned host -> device copies + asynchronous device-side match ingestion)
   cold_single_batch  ONE batch of 64 sequences alone on an idle chip (latency, sequences/s): what `value`'s steady-state rate is NOT
-  dry_dist        (--dry-dist on a single-GPU box) the N > 1 collectives executed on RCCL with a world of one rank
   from_images     the drop-in PoseDiffusionModel.forward on 20 images (DINO features at three scales + sampler + decode), GGS off / on:
                   the one workload the reference publishes a wall time for (README.md:45)
   rank_emulation  one rank of the driver's 2 / 4 / 8-GPU strong-scaling run emulated on this GPU, with the predicted curve
   cpu_baseline    the reference files verbatim (kind "reference") when the reference tree is present, else the oracle
                   port (kind "port"), on the host cores of this box: fixed thread counts, 20 denoiser steps + ONE whole guided step
+  config.headline_slots_equal_alone  three slots of the timed launch shape re-run alone, bit for bit; with --full the timed region also
+                  copies the GGS launch stamps out behind every pass (the roofline's `in_pipe` launches)
+`dry_dist` (--dry-dist on a single-GPU box, with or without --full): the N > 1 collectives executed on RCCL with a world of one rank.
 
 The legs live in bench_legs.py (one callable each); this file owns the command line, the timed region and the JSON line.
 """
@@ -94,6 +105,11 @@ def parse_args(argv=None):
     ap.add_argument("--no-stream-probe", action="store_true", help="skip tools/stream_probe (this box's match-stream reference rates)")
     ap.add_argument("--no-launch-stamps", action="store_true",
                     help="do not read the GGS launch stamps of the timed region (roofline.frac then falls back to the launch alone; A/B of the readout's cost)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline (rooflines, per-config, exact mode, fresh inputs, cold batch, images, rank emulation, "
+                         "CPU baseline, the slot check); a plain run only sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (pose.npy, ggs_stats.npy) to DIR")
     return ap.parse_args(argv)
 
 
@@ -123,10 +139,10 @@ def setup(args, rank, world, dev):
     slots = depth if args.ggs_slots <= 0 else min(args.ggs_slots, depth)
     pipe = SamplingPipeline(engines, slots, dev, unguided_streams=max(0, args.unguided_streams), trace=args.trace)
     # one resident engine batch per context (different sequences: seeds offset per context and rank)
-    want_fresh = not args.no_fresh_inputs
+    want_fresh = args.full and not args.no_fresh_inputs
     check_slots = sorted({0, min(EB - 1, ((EB - 1) // 3) | 1), EB - 1})        # headline_slots_equal_alone: these slots of context 0 are re-run alone
     inputs = [make_batch_inputs(engines[j], diff, EB, dev, seed0=100_000 * rank + j * EB,
-                                keep_host=True if want_fresh else (check_slots if j == 0 else False)) for j in range(depth)]
+                                keep_host=True if want_fresh else (check_slots if j == 0 and args.full else False)) for j in range(depth)]
     wgs = args.ggs_wgs if args.ggs_wgs > 0 else pipe.wgs_per_seq(EB)
     flags = int(os.environ.get("PD_GGS_RESERVED", "0"))                         # A/B switch, pd_engine.h
     if wgs == 1 and not (flags & _lib.PD_GGS_CFG_NO_LANE_ITEMS):
@@ -157,8 +173,10 @@ def setup(args, rank, world, dev):
         return p
 
     bc.pass_inputs, bc.submit = pass_inputs, submit
-    # one preallocated row of launch stamps per pass of the warm-up and the timed region (nothing is allocated between the passes of the pipe)
-    bc.stamp_rows = torch.zeros(4 * (K + args.warmup) + 64, COND_START, 2, dtype=torch.int64, device=dev) if (hasattr(eng.lib, "pd_ggs_launch_stamps") and not args.no_launch_stamps) else None
+    # one preallocated row of launch stamps per pass of the warm-up and the timed region (nothing is allocated between the passes of the pipe);
+    # only the roofline of --full reads them
+    want_stamps = args.full and hasattr(eng.lib, "pd_ggs_launch_stamps") and not args.no_launch_stamps
+    bc.stamp_rows = torch.zeros(4 * (K + args.warmup) + 64, COND_START, 2, dtype=torch.int64, device=dev) if want_stamps else None
     bc.stamps_used = 0
     return bc
 
@@ -211,9 +229,19 @@ def timed_region(bc, dry):
     assert gathered.shape[0] == bc.step_total and gathered.shape[1] == K
     # every guided step must have run its full 700 iterations (no data-dependent early exit skipped work)
     iters = torch.cat([p.stats[:, :, :, 1].sum(dim=(0, 2)).cpu() for p in pend])
-    return {"dt": dt, "pend": pend, "iters": iters, "finite": bool(torch.isfinite(gathered).all().item()),
+    p_, r0, r1 = shard.step_rows(K - 1, bc.group, bc.B_step)                   # what the last timed step handed back (--dump-outputs)
+    last = {"pose": gathered[:, K - 1].float().cpu(), "ggs_stats": pend[p_].stats[:, r0:r1].float().cpu()}
+    return {"dt": dt, "pend": pend, "iters": iters, "finite": bool(torch.isfinite(gathered).all().item()), "last": last,
             "in_pipe_ms": L.in_pipe_launches([p.stamps for p in pend if getattr(p, "stamps", None) is not None]),
             "in_pipe_busy": L.in_pipe_busy([p.stamps for p in pend if getattr(p, "stamps", None) is not None])}
+
+
+def dump_outputs(folder, last):
+    """--dump-outputs: the last timed step's arrays as DIR/<name>.npy (float32)."""
+    import numpy as np
+    os.makedirs(folder, exist_ok=True)
+    for name, t in last.items():
+        np.save(os.path.join(folder, f"{name}.npy"), t.numpy().astype(np.float32))
 
 
 def main():
@@ -251,24 +279,27 @@ def main():
             print(f"  sub {i:2d}: U {a:7.1f} -> {b2:7.1f} ({b2 - a:5.1f})   G {c:7.1f} -> {d:7.1f} ({d - c:5.1f})", file=sys.stderr)
     ms_per_step = dt / K * 1e3
     value = bc.step_total * K / dt
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, tr["last"])
 
-    # ---- everything below is outside the timed region
-    pass_latency_ms, full_pose = L.pass_latency(bc)
-    cold = L.cold_single_batch(bc)
-    n_passes = len(passes_for(bc, K))
-    fast = L.exact_mode(bc, full_pose, n_passes) if (not args.no_fast_mode and EB * N_FRAMES >= PD_STREAM_MIN_ROWS) else None
-    fresh = L.fresh_inputs(bc, full_pose, n_passes) if bc.want_fresh else None
-    slots_equal = L.headline_slots_equal_alone(bc, full_pose) if rank == 0 else None
-    roofline, ggs_alone_ms = L.roofline_ggs(bc, full_pose, tr["in_pipe_ms"], tr["in_pipe_busy"])
-    roofline_den, den_ms = L.roofline_denoiser(bc)
-    ranks = L.rank_emulation(bc) if (rank == 0 and world == 1 and not args.no_rank_emulation and bc.strong and EB >= 160) else None
-    per_config = L.per_config(bc) if (not args.no_per_config and rank == 0) else None      # (closes the extra contexts: keep it after the legs that use them)
-    images = None
-    if not args.no_from_images and rank == 0 and world == 1:
-        try:
-            images = L.from_images(bc)
-        except Exception as e:  # noqa: BLE001  (the headline must still be reported)
-            images = {"error": repr(e)}
+    # ---- everything below is outside the timed region, and runs with --full only
+    pass_latency_ms = slots_equal = cold = fast = fresh = roofline = roofline_den = ranks = per_config = images = None
+    if args.full:
+        pass_latency_ms, full_pose = L.pass_latency(bc)
+        cold = L.cold_single_batch(bc)
+        n_passes = len(passes_for(bc, K))
+        fast = L.exact_mode(bc, full_pose, n_passes) if (not args.no_fast_mode and EB * N_FRAMES >= PD_STREAM_MIN_ROWS) else None
+        fresh = L.fresh_inputs(bc, full_pose, n_passes) if bc.want_fresh else None
+        slots_equal = L.headline_slots_equal_alone(bc, full_pose) if rank == 0 else None
+        roofline, ggs_alone_ms = L.roofline_ggs(bc, full_pose, tr["in_pipe_ms"], tr["in_pipe_busy"])
+        roofline_den, den_ms = L.roofline_denoiser(bc)
+        ranks = L.rank_emulation(bc) if (rank == 0 and world == 1 and not args.no_rank_emulation and bc.strong and EB >= 160) else None
+        per_config = L.per_config(bc) if (not args.no_per_config and rank == 0) else None      # (closes the extra contexts: keep it after the legs that use them)
+        if not args.no_from_images and rank == 0 and world == 1:
+            try:
+                images = L.from_images(bc)
+            except Exception as e:  # noqa: BLE001  (the headline must still be reported)
+                images = {"error": repr(e)}
 
     M = N_FRAMES * (N_FRAMES - 1) // 2 * PER_PAIR
     k_eff = bc.wgs or 24
@@ -293,14 +324,16 @@ def main():
             "hip_graph": bc.use_graph, "pipeline_depth": depth, "guided_slots": bc.slots, "unguided_streams": max(0, args.unguided_streams),
             "ggs_workgroups_per_sequence": k_eff, "engine_pass_latency_ms_unpipelined": pass_latency_ms,
             "parallelism": f"dp{world} (independent sequences, one final all_gather)", "outputs_finite": tr["finite"],
-            "headline_slots_equal_alone": slots_equal, "headline_slots_checked": bc.check_slots,
+            "headline_slots_equal_alone": slots_equal, "headline_slots_checked": bc.check_slots if args.full else None,
             "multi_gpu": "no hardware scaling curve was measured by the builder (every lease had one GPU); `rank_emulation` holds the predicted one",
+            "full": args.full,
         },
-        "roofline": roofline,
-        "roofline_denoiser": roofline_den,
-        "per_step_ms": {"denoiser_step": den_ms, "ggs_guided_step": roofline["launch_ms"], "ggs_guided_step_alone": ggs_alone_ms,
-                        "ggs_iteration_us": roofline["launch_ms"] * 1e3 / (7 * cfg.iter_num)},
     }
+    if args.full:
+        out["roofline"] = roofline
+        out["roofline_denoiser"] = roofline_den
+        out["per_step_ms"] = {"denoiser_step": den_ms, "ggs_guided_step": roofline["launch_ms"], "ggs_guided_step_alone": ggs_alone_ms,
+                              "ggs_iteration_us": roofline["launch_ms"] * 1e3 / (7 * cfg.iter_num)}
     if cold is not None:
         out["cold_single_batch"] = cold
     if dry:
@@ -311,14 +344,15 @@ def main():
         if val is not None:
             out[key] = val
     if rank == 0:
-        skipped = {"value": None, "unit": "sequences/s", "cores": torch.get_num_threads(), "host_cores": os.cpu_count(), "kind": "port"}
-        if args.cpu_budget_s > 0 and world == 1:
-            try:
-                out["cpu_baseline"] = cpu_baseline(args.cpu_budget_s)
-            except Exception as e:  # noqa: BLE001  (the GPU number must still be reported)
-                out["cpu_baseline"] = dict(skipped, sample=f"failed: {e!r}")
-        else:
-            out["cpu_baseline"] = dict(skipped, sample="skipped (measured on rank 0 at N=1 only)")
+        if args.full:
+            skipped = {"value": None, "unit": "sequences/s", "cores": torch.get_num_threads(), "host_cores": os.cpu_count(), "kind": "port"}
+            if args.cpu_budget_s > 0 and world == 1:
+                try:
+                    out["cpu_baseline"] = cpu_baseline(args.cpu_budget_s)
+                except Exception as e:  # noqa: BLE001  (the GPU number must still be reported)
+                    out["cpu_baseline"] = dict(skipped, sample=f"failed: {e!r}")
+            else:
+                out["cpu_baseline"] = dict(skipped, sample="skipped (measured on rank 0 at N=1 only)")
         sys.stdout.flush()
         C.CDLL(None).fflush(None)           # RCCL's banner sits in libc's stdout buffer: out with it while descriptor 1 is still stderr
         os.dup2(result_fd, 1)

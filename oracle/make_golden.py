@@ -422,8 +422,59 @@ def make_decode_args():
     print("decode_args.npz", os.path.getsize(os.path.join(OUT, "decode_args.npz")))
 
 
+def make_live_reference():
+    """tests/golden/live_reference.npz -- the reference's Denoiser.forward (models/denoiser.py), geometry_guided_sampling
+    (util/geometry_guided_sampling.py) and MultiScaleImageFeatureExtractor (models/image_feature_extractor.py, around the restated ViT
+    of oracle/vit_oracle.py), executed in place on small inputs: the cases tests/test_oracle_golden.py compares the oracle with."""
+    from oracle import vit_oracle as VO
+    ref = RS.load_reference()
+    diff = RS.build_reference_diffuser(seed=0)
+    synth.randomize_norm_and_bias_(diff.model)
+    x = torch.randn(2, 9, 9, generator=torch.Generator().manual_seed(3))
+    z = synth.make_z(2, 9)
+    tt = torch.full((2,), 17, dtype=torch.long)
+    with torch.no_grad():
+        eps = diff.model(x, tt, z)
+    out = {"den_x": x.numpy(), "den_z": z.numpy(), "den_t": tt.numpy(), "den_eps": eps.numpy(),
+           "den_weight_checksum": weight_checksum(diff.model.state_dict())}
+    enc = synth.make_cameras(6, seed=1)
+    md = synth.make_matches(enc, 224, 224, per_pair=30, seed=1)
+    x0 = synth.perturb_pose(enc, seed=2)
+    cfg = dict(synth.GGS_CFG, iter_num=4)
+    out.update(ggs_x0=x0.numpy(), ggs_kp1=md["kp1"], ggs_kp2=md["kp2"], ggs_i12=md["i12"], ggs_img_shape=np.array(md["img_shape"]),
+               ggs_iter_num=np.array(4), ggs_t=np.array(1), ggs_out=quiet(ref.geometry_guided_sampling, x0.clone(), 1, md, cfg).numpy())
+    net = VO.make_vit(seed=3, dtype=torch.float64)
+    ext = RS.load_reference_extractor(net)
+    # fp64 throughout (stored features must not depend on the host's BLAS / thread count): the file's normalisation buffers are float32
+    # tensors of its own decimal constants (image_feature_extractor.py:24-25, :47-48); they are rebuilt from the same constants in fp64
+    ref_globals = type(ext).__init__.__globals__
+    for name, key in (("_resnet_mean", "_RESNET_MEAN"), ("_resnet_std", "_RESNET_STD")):
+        setattr(ext, name, torch.tensor(ref_globals[key], dtype=torch.float64).view(1, 3, 1, 1))
+    img = torch.rand(2, 3, 224, 224, generator=torch.Generator().manual_seed(4), dtype=torch.float64)
+    with torch.no_grad():
+        out["vit_features64"] = ext(img).numpy()
+    np.savez_compressed(os.path.join(OUT, "live_reference.npz"), **out)
+    print("live_reference.npz", os.path.getsize(os.path.join(OUT, "live_reference.npz")))
+
+
+def make_default_cfg():
+    """tests/golden/default_cfg.json -- the MODEL and GGS nodes of the reference's cfgs/default.yaml (what demo.py instantiates)."""
+    import json
+    import yaml
+    with open(os.path.join(RS.REF_ROOT, "cfgs", "default.yaml")) as f:
+        cfg = yaml.safe_load(f)
+    with open(os.path.join(OUT, "default_cfg.json"), "w") as f:
+        json.dump({k: cfg[k] for k in ("MODEL", "GGS")}, f, indent=1, sort_keys=True)
+        f.write("\n")
+    print("default_cfg.json", os.path.getsize(os.path.join(OUT, "default_cfg.json")))
+
+
 if __name__ == "__main__":
-    if len(sys.argv) > 1 and sys.argv[1] == "decode_args":
+    if len(sys.argv) > 1 and sys.argv[1] == "default_cfg":
+        make_default_cfg()      # only the config-node fixture
+    elif len(sys.argv) > 1 and sys.argv[1] == "live_reference":
+        make_live_reference()   # only the fixture of the live-reference comparisons
+    elif len(sys.argv) > 1 and sys.argv[1] == "decode_args":
         make_decode_args()      # only the decode-parameter fixture
     elif len(sys.argv) > 1 and sys.argv[1] == "pred_x0":
         make_pred_x0()          # only the objective="pred_x0" fixture
@@ -444,3 +495,5 @@ if __name__ == "__main__":
         make_guided_free()
         make_guided_free(seeds=(0,), N=20, cond_start=10, per_pair=300, name="guided_free_full")
         make_decode_args()
+        make_live_reference()
+        make_default_cfg()

@@ -1,10 +1,9 @@
-"""Row R2 / BASELINE configs[0]: the reference's own `pose_diffusion/demo.py` and `cfgs/default.yaml`, UNCHANGED, on the
-drop-in packages (posediffusion_amd/run_reference.py + compat/shims + tools/make_synthetic_ckpt.py).
+"""Row R2 / BASELINE configs[0]: the call sequence of the reference's `pose_diffusion/demo.py` and the MODEL / GGS nodes of its
+`cfgs/default.yaml` on the drop-in packages (posediffusion_amd/run_reference.py + compat/shims + tools/make_synthetic_ckpt.py).
 
-The reference tree is read where it lies (`PD_REFERENCE_ROOT`, `/root/reference`, or a staged `<repo>/_ref_stage`); it
-does not exist on the GPU box of the round-end run, so the tests that execute demo.py skip there and the same call
-sequence is covered by `test_demo_call_sequence_on_synthetic_folder` (which needs no reference file).  A transcript of
-demo.py itself running on an MI355X is committed under profiles/ (round2_demo_*.log).
+demo.py itself is not part of this repository, so the suite runs its call sequence (`test_demo_call_sequence_on_synthetic_folder`)
+and pins the config nodes against tests/golden/default_cfg.json (oracle/make_golden.py `default_cfg`).  Transcripts of demo.py
+itself running unchanged on an MI355X are committed under profiles/ (round*_demo_ggs_off.log; tools/round6_end.sh).
 """
 import os
 import subprocess
@@ -15,17 +14,6 @@ import pytest
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _reference_root():
-    for cand in (os.environ.get("PD_REFERENCE_ROOT"), "/root/reference", os.path.join(ROOT, "_ref_stage")):
-        if cand and os.path.isfile(os.path.join(cand, "pose_diffusion", "demo.py")):
-            return cand
-    return None
-
-
-REF = _reference_root()
-needs_ref = pytest.mark.skipif(REF is None, reason="reference tree not present (it never is on the GPU box)")
 
 
 def _run(script, overrides, cwd, timeout=900):
@@ -61,19 +49,24 @@ def test_hydra_and_omegaconf_standins(tmp_path):
 def test_default_cfg_instantiates_through_the_registry_and_checkpoint_round_trips(tmp_path):
     """cfgs/default.yaml's MODEL node -> `instantiate(cfg.MODEL, _recursive_=False)` (demo.py:46) through the drop-in
     `models` registry; tools/make_synthetic_ckpt.py writes the reference key set; `load_state_dict(strict=True)`
-    (demo.py:56-57) round-trips bit for bit.  With the reference present the yaml is read from where it lies and the
-    built-in copy of its MODEL node is pinned against it."""
+    (demo.py:56-57) round-trips bit for bit.  The built-in copy of the MODEL node is pinned against the reference's
+    (tests/golden/default_cfg.json), and the checkpoint is also built from a yaml holding the recorded nodes."""
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import make_synthetic_ckpt as mk
     from posediffusion_amd.compat import install_shims, to_container
     install_shims()
     from omegaconf import OmegaConf
-    cfg_path = os.path.join(REF, "cfgs", "default.yaml") if REF else None
-    if cfg_path:
-        cfg = OmegaConf.load(cfg_path)
-        assert to_container(cfg.MODEL) == mk.DEFAULT_MODEL_CFG, "built-in copy of cfgs/default.yaml MODEL is stale"
-        assert to_container(cfg.GGS) == {"enable": True, "start_step": 10, "learning_rate": 0.01, "iter_num": 100,
-                                         "sampson_max": 10, "min_matches": 10, "alpha": 0.0001}
+    import json
+    import yaml
+    with open(os.path.join(ROOT, "tests", "golden", "default_cfg.json")) as f:
+        nodes = json.load(f)
+    cfg_path = str(tmp_path / "default.yaml")
+    with open(cfg_path, "w") as f:
+        yaml.safe_dump(nodes, f)
+    cfg = OmegaConf.load(cfg_path)
+    assert to_container(cfg.MODEL) == mk.DEFAULT_MODEL_CFG, "built-in copy of cfgs/default.yaml MODEL is stale"
+    assert to_container(cfg.GGS) == {"enable": True, "start_step": 10, "learning_rate": 0.01, "iter_num": 100,
+                                     "sampson_max": 10, "min_matches": 10, "alpha": 0.0001}
     ckpt = str(tmp_path / "synthetic.pth")
     sd = mk.write_checkpoint(ckpt, cfg_path, seed=0)
     keys = set(sd)
@@ -92,22 +85,6 @@ def test_default_cfg_instantiates_through_the_registry_and_checkpoint_round_trip
         assert torch.equal(v, sd[k]), k
 
 
-@needs_ref
-@pytest.mark.skipif(torch.cuda.is_available(), reason="CPU container only: with a GPU the run completes (GPU test below)")
-def test_reference_demo_runs_unchanged_until_the_first_gpu_touch(tmp_path):
-    """demo.py executed from where it lies: hydra.main loads ../cfgs/default.yaml, overrides apply, the model is built
-    through the registry -- and, without a GPU, the first engine call fails LOUDLY (no CPU fallback exists)."""
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import make_synthetic_ckpt as mk
-    ckpt = str(tmp_path / "synthetic.pth")
-    mk.write_checkpoint(ckpt, os.path.join(REF, "cfgs", "default.yaml"))
-    pd = os.path.join(REF, "pose_diffusion")
-    r = _run(os.path.join(pd, "demo.py"), ["image_folder=samples/apple", f"ckpt={ckpt}", "GGS.enable=False"], cwd=pd)
-    assert "Model Config:" in r.stdout and "_target_: models.PoseDiffusionModel" in r.stdout and "enable: false" in r.stdout
-    assert r.returncode != 0
-    assert "runs only on an AMD GPU" in r.stderr and "demo.py" in r.stderr
-
-
 # ------------------------------------------------------------------------------------------------ GPU
 def _write_synthetic_folder(folder, n_frames=6, size=(96, 128), with_matches=False):
     from PIL import Image
@@ -124,32 +101,6 @@ def _write_synthetic_folder(folder, n_frames=6, size=(96, 128), with_matches=Fal
     if with_matches:
         md = synth.make_matches(enc, 224, 224, per_pair=50, seed=31)
         np.savez(os.path.join(folder, "pd_matches.npz"), kp1=md["kp1"], kp2=md["kp2"], i12=md["i12"])
-
-
-@pytest.mark.gpu
-@needs_ref
-@pytest.mark.parametrize("ggs", [False, True])
-def test_reference_demo_end_to_end_on_the_engine(tmp_path, ggs):
-    """BASELINE configs[0] on the drop-in: `demo.py image_folder=samples/apple ckpt=<synthetic> GGS.enable=False` from
-    the reference tree, and the GGS-on branch on a folder that carries pre-extracted matches (hloc is out of scope)."""
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import make_synthetic_ckpt as mk
-    ckpt = str(tmp_path / "synthetic.pth")
-    mk.write_checkpoint(ckpt, os.path.join(REF, "cfgs", "default.yaml"))
-    pd = os.path.join(REF, "pose_diffusion")
-    if ggs:
-        folder = str(tmp_path / "seq")
-        _write_synthetic_folder(folder, n_frames=6, with_matches=True)
-        over = [f"image_folder={folder}", f"ckpt={ckpt}", "GGS.enable=True", "GGS.iter_num=5"]
-    else:
-        over = ["image_folder=samples/apple", f"ckpt={ckpt}", "GGS.enable=False"]
-    r = _run(os.path.join(pd, "demo.py"), over, cwd=pd)
-    assert r.returncode == 0, r.stderr[-3000:]
-    out = r.stdout
-    assert f"Loaded checkpoint from: {ckpt}" in out
-    assert ("Sampling with GGS" if ggs else "Sampling without GGS") in out
-    assert "Time taken:" in out and "the absolute rotation error is" in out
-    assert "Please check your visdom connection" in out
 
 
 @pytest.mark.gpu

@@ -61,9 +61,10 @@ def test_lane_kernel_at_the_headline_launch(engine, headline_batch, B):
     fabric, DMA landing latencies several times those of a 3-sequence launch -- is what a miscounted wait would need to corrupt a slot.
       (a) 20 iterations of GGS_optimize (the ring wraps ~19 x 20 times per wave): nine slots spread over all XCDs are compared BITWISE
           with the same sequence run alone (a launch of ONE workgroup on an idle chip: DMA latency at its minimum); against the oracle's
-          GGS_optimize the teacher-forced bound 2e-5 is asserted after 6 iterations of the same launch shape (measured 1e-6); the deviation
-          after the 20 is printed only -- a free-running trajectory through a hard threshold, and the CPU oracle's own sums depend on the
-          box's thread count: one slot read 8.1e-5 on one box and 1.6e-4 on another with the engine's bits unchanged;
+          GGS_optimize in fp64 the teacher-forced bound 2e-5 is asserted after 6 iterations of the same launch shape (measured 5.3e-6); the
+          deviation after the 20 is printed only -- a free-running trajectory through a hard threshold.  The oracle runs in fp64 because
+          an fp32 oracle's sums depend on the host's thread count: with ~57 000 Sampson values per iteration one always lies within fp32
+          rounding of sampson_max, and slot 255 after 6 iterations read 9e-7 or 9.3e-5 from the same engine bits depending on that count;
       (b) a full geometry_guided_sampling (5 stages, 700 iterations: ~13 000 ring turns per wave): the same nine slots bitwise with the
           sequence run alone, every slot finite with all 700 iterations stepped, and the whole launch repeated: bitwise the same."""
     eng, mds, x0_all = headline_batch
@@ -97,10 +98,10 @@ def test_lane_kernel_at_the_headline_launch(engine, headline_batch, B):
         assert torch.equal(a20[0], o20[b]) and torch.equal(sa20[0], st20[b]), f"slot {b} of the {B}-sequence launch differs from the sequence run alone (20 iterations)"
         assert torch.equal(af[0], of[b]) and torch.equal(saf[0], stf[b]), f"slot {b} of the {B}-sequence launch differs from the sequence run alone (700 iterations)"
         pm = O.prepare_matches(md["kp1"], md["kp2"], md["i12"], md["img_shape"])
-        ref, _, steps = O.ggs_optimize(x0[b:b + 1].cpu().clone(), pm, iter_num=10)
+        ref, _, steps = O.ggs_optimize(x0[b:b + 1].cpu().double(), pm, iter_num=10)
         assert steps == 20
         worst = max(worst, rel_err(o20[b:b + 1], ref))
-        ref6, _, steps6 = O.ggs_optimize(x0[b:b + 1].cpu().clone(), pm, iter_num=3)
+        ref6, _, steps6 = O.ggs_optimize(x0[b:b + 1].cpu().double(), pm, iter_num=3)
         assert steps6 == 6 == int(st6[b, 1])
         worst6 = max(worst6, pose_err(o6[b:b + 1], ref6, f"lane_headline_launch_{B}_6_iterations"))
     print(f"lane kernel, {B}-sequence launch: slots {slots} bitwise = alone (20 and 700 iterations); worst deviation from the oracle after 6 / 20 iterations "

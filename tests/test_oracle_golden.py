@@ -1,5 +1,5 @@
 """CPU: the oracle restatement against (a) the committed golden vectors produced by the reference's own
-files and (b) -- when /root/reference is present -- the live reference.  Tolerances are fp32 rounding
+files and (b) the reference's outputs on small cases, recorded by oracle/make_golden.py (live_reference.npz).  Tolerances are fp32 rounding
 class (the oracle runs 8 threads / different BLAS blocking than the single-threaded fixture run)."""
 import numpy as np
 import pytest
@@ -7,7 +7,6 @@ import torch
 
 from conftest import rel_err
 from oracle import pd_oracle as O
-from oracle import ref_stubs as RS
 from posediffusion_amd import synth
 
 FLAGS = {"all": (True, True, True), "fl": (False, False, True), "r": (True, False, False), "t": (False, True, False)}
@@ -193,28 +192,17 @@ def test_noise_replay_matches_reference_order(golden):
     assert np.array_equal(noises[99].numpy(), tr["noise"][1]) and noises[0] is None
 
 
-@pytest.mark.skipif(not RS.available(), reason="/root/reference not present (GPU box)")
-def test_oracle_against_live_reference(seeded_diffuser):
-    """Where the reference is mounted, re-derive two fixtures from it and compare the oracle directly."""
-    import contextlib
-    import io
-    from posediffusion_amd import synth
-    ref = RS.load_reference()
-    diff = RS.build_reference_diffuser(seed=0)
-    synth.randomize_norm_and_bias_(diff.model)
-    sd = O.cast_state_dict(diff.model.state_dict(), torch.float32)
-    x = torch.randn(2, 9, 9, generator=torch.Generator().manual_seed(3))
-    z = synth.make_z(2, 9)
-    tt = torch.full((2,), 17, dtype=torch.long)
-    with torch.no_grad():
-        assert rel_err(O.denoiser_forward(sd, x, tt, z), diff.model(x, tt, z)) < 5e-6
-    enc = synth.make_cameras(6, seed=1)
-    md = synth.make_matches(enc, 224, 224, per_pair=30, seed=1)
-    x0 = synth.perturb_pose(enc, seed=2)
-    cfg = dict(synth.GGS_CFG, iter_num=4)
-    with contextlib.redirect_stdout(io.StringIO()):
-        xr = ref.geometry_guided_sampling(x0.clone(), 1, md, cfg)
-    assert rel_err(O.geometry_guided_sampling(x0.clone(), 1, md, cfg), xr) < 2e-5
+def test_oracle_against_live_reference(golden, oracle_weights):
+    """The oracle against the reference executed in place on two small cases -- Denoiser.forward and a whole geometry_guided_sampling --
+    whose inputs and outputs oracle/make_golden.py (`live_reference`) recorded in tests/golden/live_reference.npz."""
+    g = golden["live_reference"]
+    np.testing.assert_allclose(g["den_weight_checksum"], golden["denoiser"]["weight_checksum"], rtol=1e-9)
+    x, z, tt = (torch.from_numpy(g[k]) for k in ("den_x", "den_z", "den_t"))
+    assert rel_err(O.denoiser_forward(oracle_weights, x, tt, z), torch.from_numpy(g["den_eps"])) < 5e-6
+    md = {"kp1": g["ggs_kp1"], "kp2": g["ggs_kp2"], "i12": g["ggs_i12"], "img_shape": tuple(int(v) for v in g["ggs_img_shape"])}
+    cfg = dict(synth.GGS_CFG, iter_num=int(g["ggs_iter_num"]))
+    x0 = torch.from_numpy(g["ggs_x0"])
+    assert rel_err(O.geometry_guided_sampling(x0.clone(), int(g["ggs_t"]), md, cfg), torch.from_numpy(g["ggs_out"])) < 2e-5
 
 
 # ---------------------------------------------------------------------------------------------- third-party helpers
@@ -298,21 +286,18 @@ def test_camera_alignment_recovers_a_similarity_exactly():
 
 
 # ---------------------------------------------------------------------------------------------- N1: image features
-def test_multiscale_wrapper_against_live_reference():
+def test_multiscale_wrapper_against_live_reference(golden):
     """oracle/vit_oracle.multiscale_features (normalise, rescale by 1, 1/2, 1/3, average) against the reference's own
-    models/image_feature_extractor.py executed in place around the same (restated) ViT."""
-    from oracle import ref_stubs as RS
+    models/image_feature_extractor.py executed in place around the same (restated) ViT, in fp64 (recorded by oracle/make_golden.py
+    `live_reference`; fp64 so that the stored features do not depend on the host's BLAS and thread count)."""
     from oracle import vit_oracle as VO
-    if not RS.available():
-        pytest.skip("reference tree not mounted")
-    net = VO.make_vit(seed=3)
-    ext = RS.load_reference_extractor(net)
-    x = torch.rand(2, 3, 224, 224, generator=torch.Generator().manual_seed(4))
+    ref = torch.from_numpy(golden["live_reference"]["vit_features64"])
+    net = VO.make_vit(seed=3, dtype=torch.float64)
+    x = torch.rand(2, 3, 224, 224, generator=torch.Generator().manual_seed(4), dtype=torch.float64)
     with torch.no_grad():
-        ref = ext(x)
-    ours = VO.multiscale_features(net, x, (1, 1 / 2, 1 / 3))
-    assert ext.get_output_dim() == 384 and tuple(ref.shape) == (2, 384)
-    assert torch.equal(ref, ours)
+        ours = VO.multiscale_features(net, x, (1, 1 / 2, 1 / 3))
+    assert tuple(ref.shape) == (2, 384) and ours.dtype == torch.float64
+    assert rel_err(ours, ref) < 1e-12
 
 
 def test_vit_oracle_loads_dino_state_dict_names():

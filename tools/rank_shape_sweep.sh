@@ -5,7 +5,7 @@
 # instead of 2 x 1 600), --min-passes 3 / 4 as shorter passes.  NOT YET MEASURED with the lane kernel (round 3, wave kernels: 475 as one pass
 # of 160 against 465 as 2 x 80).  usage (on the GPU box): bash tools/rank_shape_sweep.sh > gpurun_out/rank_shape_sweep.txt
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
-Q="--scaling weak --steps 20 --warmup 5 --no-per-config --no-fresh-inputs --no-fast-mode --cpu-budget-s 0 --no-stream-probe"
+Q="--full --scaling weak --steps 20 --warmup 5 --no-per-config --no-fresh-inputs --no-fast-mode --cpu-budget-s 0 --no-stream-probe"
 run() {
   local label=$1; shift
   timeout 300 python bench.py $Q "$@" 2>/dev/null | tail -1 | python -c "

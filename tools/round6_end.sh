@@ -10,9 +10,9 @@ timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1 | 
 bash tools/collect_pmc.sh > /dev/null 2>&1; cp gpurun_out/pmc_summary.json $F/pmc_summary.json
 mkdir -p profiles; cp gpurun_out/pmc_summary.json profiles/round6_pmc_summary.json      # bench.py reads the traffic figures from here (hash-checked)
 [ -d _ref_stage/pose_diffusion ] && export PD_REFERENCE_ROOT=$R/_ref_stage
-T0=$SECONDS; timeout 1200 python bench.py --dry-dist > $F/bench_line.json 2> $F/bench.err; echo "default bench.py run: $((SECONDS - T0)) s wall" | tee $F/bench_wall.txt; tail -2 $F/bench.err
+T0=$SECONDS; timeout 1200 python bench.py --full --dry-dist > $F/bench_line.json 2> $F/bench.err; echo "default bench.py run: $((SECONDS - T0)) s wall" | tee $F/bench_wall.txt; tail -2 $F/bench.err
 cd /tmp && export TMPDIR=/tmp
-timeout 500 rocprofv3 --kernel-trace --stats -d $R/$F/trace -o bench -- python $R/bench.py --no-per-config --no-fresh-inputs --no-fast-mode --cpu-budget-s 0 --no-from-images --no-rank-emulation --no-stream-probe > $R/$F/bench_traced.json 2>/dev/null
+timeout 500 rocprofv3 --kernel-trace --stats -d $R/$F/trace -o bench -- python $R/bench.py --full --no-per-config --no-fresh-inputs --no-fast-mode --cpu-budget-s 0 --no-from-images --no-rank-emulation --no-stream-probe > $R/$F/bench_traced.json 2>/dev/null
 cd $R; python tools/rocpd_stats.py $F/trace/bench_results.db 16 > $F/kernel_stats.txt
 python tools/coresident_from_trace.py $F/trace/bench_results.db $(python -c "import json; print(json.load(open('$F/bench_traced.json'))['roofline']['algorithmic_flops_per_launch'])") > $F/coresident.txt 2>&1; cat $F/coresident.txt; rm -rf $F/trace
 cd /tmp

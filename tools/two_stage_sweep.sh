@@ -5,7 +5,7 @@
 # meet, and an engine pass of 192 sequences leaves 64 CUs to the other contexts' denoiser kernels while a launch iterates.
 # usage (on the GPU box): bash tools/two_stage_sweep.sh > gpurun_out/two_stage_sweep.txt
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
-Q="--no-per-config --no-fresh-inputs --no-fast-mode --cpu-budget-s 0 --no-stream-probe"
+Q="--full --no-per-config --no-fresh-inputs --no-fast-mode --cpu-budget-s 0 --no-stream-probe"
 run() {   # label, then bench flags
   local label=$1; shift
   timeout 300 python bench.py $Q "$@" 2>/dev/null | tail -1 | python -c "
