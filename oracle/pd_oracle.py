@@ -385,16 +385,18 @@ def ggs_optimize(x: torch.Tensor, pm: Dict, update_R=True, update_T=True, update
 
 
 def geometry_guided_sampling(model_mean: torch.Tensor, t: int, matches_dict: Dict, GGS_cfg: Dict,
-                             stats: Optional[list] = None) -> torch.Tensor:
-    """The five sequential optimisations of geometry_guided_sampling.py:48-63."""
+                             stats: Optional[list] = None, steps: Optional[list] = None) -> torch.Tensor:
+    """The five sequential optimisations of geometry_guided_sampling.py:48-63 (``steps`` receives each stage's iteration count)."""
     pm = prepare_matches(matches_dict["kp1"], matches_dict["kp2"], matches_dict["i12"], matches_dict["img_shape"])
     cfg = {k: v for k, v in GGS_cfg.items() if k in ("alpha", "learning_rate", "iter_num", "sampson_max", "min_matches")}
     flags = [(True, True, True), (False, False, True), (True, False, False), (False, True, False), (True, True, True)]
     x = model_mean
     for (uR, uT, uF) in flags:                                                        # (R, T, FL)
-        x, pr, _ = ggs_optimize(x, pm, update_R=uR, update_T=uT, update_FL=uF, **cfg)
+        x, pr, n = ggs_optimize(x, pm, update_R=uR, update_T=uT, update_FL=uF, **cfg)
         if stats is not None:
             stats.append(float(pr))
+        if steps is not None:
+            steps.append(n)
     return x
 
 

@@ -15,6 +15,7 @@ import pytest
 import torch
 
 from conftest import camera_errs, pose_err, rel_err
+from ggs_checks import check_loss_grad, check_steps, oracle_optimize
 from oracle import pd_oracle as O
 from posediffusion_amd import _lib, synth
 from posediffusion_amd.engine import make_ggs_cfg
@@ -363,10 +364,12 @@ def test_ggs_ragged_and_ordered_pairs(engine):
     loss, grad = engine.ggs_loss_grad(x0.to(DEV))
     assert int(loss[0, 1].item()) == len(v)
     assert rel_err(grad, go) < 1e-4
+    check_loss_grad(loss[0].cpu(), grad.cpu(), x0, pm, "ragged_ordered")          # per column group against fp64 (tests/ggs_checks.py)
     assert (grad[0, 6, :7] == 0).all()          # isolated frame: no T/R gradient (focal is shared via the mean)
     ref, _, _ = O.ggs_optimize(x0.clone(), pm, iter_num=5)
     out, _, _ = engine.ggs_optimize(x0.to(DEV), cfg=make_ggs_cfg(iter_num=5))
     assert rel_err(out, ref) < TOL
+    check_steps(out, x0, oracle_optimize(x0, pm, iter_num=5)[0], ref, "ragged_ordered")
     assert torch.equal(out[0, 6, :7].cpu(), x0[0, 6, :7])                                  # never stepped
 
 
@@ -472,21 +475,24 @@ def test_long_sequence_n50(engine):
     # k = 1 and the forced single-exchange kernel replicate the whole backward; the default for N > 32 is the two-hop
     # kernel (backward distributed over the workgroups, per-frame sums by frame owners): same arithmetic per pair, a
     # different (row-ordered) per-frame summation -> equal to rounding, not bitwise
-    outs = {}
+    outs, cache = {}, {}
     for label, wgs, flags in (("k1", 1, 0), ("one_hop", 0, 1), ("two_hop", 0, 0), ("two_hop_k40", 40, 0)):
         cfg1 = make_ggs_cfg(wgs_per_seq=wgs, reserved=flags)
         loss, grad = engine.ggs_loss_grad(x0.to(DEV), cfg=cfg1)
         engine.check_async()
         assert int(loss[0, 1].item()) == len(v)
         assert rel_err(grad, go) < 1e-4
+        check_loss_grad(loss[0].cpu(), grad.cpu(), x0, pm, f"n50/{label}", cache)
         o, st, _ = engine.ggs_optimize(x0.to(DEV), cfg=make_ggs_cfg(iter_num=3, wgs_per_seq=wgs, reserved=flags))
         engine.check_async()
         assert int(st[0, 1].item()) == 6
         outs[label] = o
     ref, _, _ = O.ggs_optimize(x0.clone(), pm, iter_num=3)
+    ref64, _ = oracle_optimize(x0, pm, iter_num=3)
     assert torch.equal(outs["k1"], outs["one_hop"])
     for label in outs:
         assert rel_err(outs[label], ref) < TOL, label
+        check_steps(outs[label], x0, ref64, ref, f"n50/{label}")
     assert rel_err(outs["two_hop"], outs["k1"]) < 1e-5 and rel_err(outs["two_hop_k40"], outs["k1"]) < 1e-5
     # the frame owner sums a frame's rows in a fixed order (four partial sums over every fourth row, round 5): the bits do not depend on
     # how many workgroups share the sequence
@@ -697,6 +703,8 @@ def test_ggs_random_match_structures(engine, case):
     v, _ = O.compute_sampson_distance(xo, pm)
     (go,) = torch.autograd.grad(v.mean(), xo)
     ref, _, _ = O.ggs_optimize(x0.clone(), pm, iter_num=2, min_matches=0)
+    ref64, _ = oracle_optimize(x0, pm, iter_num=2, min_matches=0)
+    cache = {}
     configs = ((0, 0), (0, 1), (1, 0), (3, 0), (17, 0))
     if case == 6:
         # 2 450 work items: only the two-hop kernel (own items in LDS) can hold them; the single-exchange kernel says so
@@ -709,9 +717,11 @@ def test_ggs_random_match_structures(engine, case):
         engine.check_async()
         assert int(loss[0, 1].item()) == len(v), (wgs, flags)
         assert rel_err(grad, go) < 1e-4, (wgs, flags, rel_err(grad, go))
+        check_loss_grad(loss[0].cpu(), grad.cpu(), x0, pm, f"random_{case}/k{wgs}/f{flags}", cache)
         out, _, _ = engine.ggs_optimize(x0.to(DEV), cfg=make_ggs_cfg(iter_num=2, wgs_per_seq=wgs, reserved=flags, min_matches=0))
         engine.check_async()
         assert rel_err(out, ref) < 5e-5, (wgs, flags, rel_err(out, ref))
+        check_steps(out, x0, ref64, ref, f"random_{case}/k{wgs}/f{flags}")
 
 
 # ------------------------------------------------------------------------------------------------ N3: evaluation metrics

@@ -11,6 +11,7 @@ import pytest
 import torch
 
 from conftest import pose_err, rel_err
+from ggs_checks import check_loss_grad, check_steps, oracle_optimize
 from oracle import pd_oracle as O
 from posediffusion_amd import synth
 from posediffusion_amd.engine import make_ggs_cfg
@@ -54,8 +55,9 @@ def test_long_sequence_n50_full_size_m367500(engine):
 
     ref, _, ref_steps = O.ggs_optimize(x0.clone(), pm, iter_num=3)
     assert ref_steps == 6
+    ref64, _ = oracle_optimize(x0, pm, iter_num=3)
     lo_n, hi_n = int((s_all < 10 * (1 - 1e-4)).sum()), int((s_all < 10 * (1 + 1e-4)).sum())
-    outs, cache = {}, {}
+    outs, cache, cache64 = {}, {}, {}
     for label, wgs, flags in (("two_hop", 0, 0), ("two_hop_k64", 64, 0), ("one_hop", 0, 1), ("k1", 1, 0)):
         cfg = make_ggs_cfg(wgs_per_seq=wgs, reserved=flags)
         loss, grad = engine.ggs_loss_grad(x0.to(DEV), cfg=cfg)
@@ -67,11 +69,13 @@ def test_long_sequence_n50_full_size_m367500(engine):
         mean_o, go = cache[n_valid]
         assert abs(loss[0, 0].item() - mean_o) < TOL * mean_o, label
         assert rel_err(grad, go) < 1e-4, (label, rel_err(grad, go))
+        check_loss_grad(loss[0].cpu(), grad.cpu(), x0, pm, f"configs4_full/{label}", cache64)     # (fp64, threshold-adjusted like oracle_at)
         o, st, _ = engine.ggs_optimize(x0.to(DEV), cfg=make_ggs_cfg(iter_num=3, wgs_per_seq=wgs, reserved=flags))
         engine.check_async()
         assert int(st[0, 1].item()) == 6, label
         # 6 free-running iterations: a straddling match moves the result by ~1e-5 of |x| per iteration it flips in
         assert pose_err(o, ref, "configs4_full_size_6_iterations") < (TOL if n_valid == n_oracle else 1e-4), (label, rel_err(o, ref))
+        check_steps(o, x0, ref64, ref, f"configs4_full/{label}")
         outs[label] = o
     print("configs[4] full size: engine valid counts", sorted(cache), "oracle", n_oracle)
     assert torch.equal(outs["k1"], outs["one_hop"])

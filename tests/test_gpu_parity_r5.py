@@ -11,6 +11,7 @@ import pytest
 import torch
 
 from conftest import pose_err, rel_err
+from ggs_checks import check_steps, oracle_optimize
 from oracle import pd_oracle as O
 from posediffusion_amd import _lib, synth
 from posediffusion_amd.engine import PoseEngine, make_ggs_cfg
@@ -104,6 +105,7 @@ def test_lane_kernel_at_the_headline_launch(engine, headline_batch, B):
         ref6, _, steps6 = O.ggs_optimize(x0[b:b + 1].cpu().double(), pm, iter_num=3)
         assert steps6 == 6 == int(st6[b, 1])
         worst6 = max(worst6, pose_err(o6[b:b + 1], ref6, f"lane_headline_launch_{B}_6_iterations"))
+        check_steps(o6[b:b + 1], x0[b:b + 1], ref6, oracle_optimize(x0[b:b + 1], pm, torch.float32, iter_num=3)[0], f"headline_{B}/slot{b}")
     print(f"lane kernel, {B}-sequence launch: slots {slots} bitwise = alone (20 and 700 iterations); worst deviation from the oracle after 6 / 20 iterations "
           f"{worst6:.2e} / {worst:.2e}")
     assert worst6 < TOL, (worst6, worst)      # (the 20-iteration figure is printed, not asserted: see the docstring)

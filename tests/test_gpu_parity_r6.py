@@ -9,6 +9,8 @@ import pytest
 import torch
 
 from conftest import pose_err, rel_err
+from ggs_checks import K_STEP, FLOOR_STEP, bounds, check_loss_grad, check_steps, oracle_optimize, step_group_errs, within
+from oracle import pd_oracle as O
 from posediffusion_amd import _lib, synth
 from posediffusion_amd.engine import make_ggs_cfg
 
@@ -94,6 +96,17 @@ def test_mixed_waves_masked_pairs_match_the_wave_kernels(engine):
     assert torch.equal(l[0][:, 1], w[0][:, 1]) and torch.equal(l[3][:, 1], w[3][:, 1])          # valid counts, iterations stepped
     assert rel_err(l[0][:, 0], w[0][:, 0]) < 2e-6 and rel_err(l[1], w[1]) < 2e-5
     assert pose_err(l[2], w[2], "mixed_waves_lane_vs_wave_6_iterations") < 2e-5
+    # per column group on the STEP: lane against wave, and each against fp64 (bound: K x the fp32 oracle's own distance, or the floor)
+    x0c = x0.cpu()
+    pm = O.prepare_matches(md["kp1"], md["kp2"], md["i12"], md["img_shape"])
+    ref64, s64 = oracle_optimize(x0c, pm, iter_num=3)
+    ref32, _ = oracle_optimize(x0c, pm, torch.float32, iter_num=3)
+    assert s64 == int(l[3][0, 1])
+    bnd = bounds(step_group_errs(ref32, x0c, ref64), K_STEP, FLOOR_STEP)
+    assert not within(step_group_errs(l[2], x0c, w[2]), bnd), ("lane vs wave step", within(step_group_errs(l[2], x0c, w[2]), bnd))
+    for tag, r in (("lane", l), ("wave", w)):
+        check_loss_grad(r[0][0], r[1], x0c, pm, f"mixed_waves/{tag}")
+        check_steps(r[2], x0c, ref64, ref32, f"mixed_waves/{tag}")
 
 
 def test_ggs_launch_stamps_and_stage_table(engine, golden):
