@@ -53,8 +53,18 @@ typedef struct pd_layer_weights {
  * (models/denoiser.py:23-51, util/embedding.py:13-37, models/gaussian_diffuser.py:157-182).
  * All pointers DEVICE fp32; the engine repacks/copies them at create time and keeps no
  * reference to the caller's storage afterwards. */
+/* Shapes: the default configuration (the values below) runs the engine's specialised kernels; every other configuration of this
+ * family runs the shape-generic denoiser path (exact fp32 as well; no split-precision modes, PD_OPT_DENOISER_SPLIT stays 0):
+ *   d_model     a multiple of 32 in [32, 2048]
+ *   nhead       divides d_model; head dim d_model / nhead a multiple of 4 in [8, 256]
+ *   dim_ff      [1, 8192]
+ *   num_layers  [1, PD_MAX_LAYERS]
+ *   z_dim       [1, 4096]
+ *   mlp_hidden  [1, 1024]
+ *   n_harmonic 10 and t_emb_dim 256 only; pre-norm or post-norm (PD_WEIGHTS_POST_NORM), with or without the pivot column
+ *   (PD_WEIGHTS_NO_PIVOT).  Anything else: PD_ERR_UNSUPPORTED with a message naming the limit. */
 typedef struct pd_weights {
-    int32_t d_model;        /* 512  */
+    int32_t d_model;        /* 512  (see the ranges above)                               */
     int32_t nhead;          /* 4    */
     int32_t dim_ff;         /* 1024 */
     int32_t num_layers;     /* 8    */
@@ -63,14 +73,15 @@ typedef struct pd_weights {
     int32_t t_emb_dim;      /* 256  (TimeStepEmbedding.dim; output is dim/2 = 128)       */
     int32_t mlp_hidden;     /* 128  (Denoiser.mlp_hidden_dim)                            */
     int32_t timesteps;      /* 100                                                       */
-    int32_t reserved;       /* flags; 0 = objective "pred_noise" (cfgs/default.yaml), PD_WEIGHTS_PRED_X0 = "pred_x0" */
+    int32_t reserved;       /* flags; 0 = objective "pred_noise" (cfgs/default.yaml), pre-norm, pivot column.  PD_WEIGHTS_PRED_X0 =
+                             * "pred_x0"; PD_WEIGHTS_POST_NORM, PD_WEIGHTS_NO_PIVOT, PD_WEIGHTS_GENERIC below */
     const float *time_w0, *time_b0;     /* time_embed.linear.0  [128,256],[128]          */
     const float *time_w2, *time_b2;     /* time_embed.linear.2  [128,128],[128]          */
-    const float *first_w, *first_b;     /* _first  [d, 189+128+z_dim+1 = 702], [d]       */
+    const float *first_w, *first_b;     /* _first  [d, 189+128+z_dim+pivot (702 by default)], [d]; columns in the reference's order */
     pd_layer_weights layers[PD_MAX_LAYERS];
-    const float *last0_w, *last0_b;     /* _last.0 [128, d], [128]                       */
-    const float *last_ln_w, *last_ln_b; /* _last.1 LayerNorm [128]                       */
-    const float *last3_w, *last3_b;     /* _last.3 [9,128], [9]                          */
+    const float *last0_w, *last0_b;     /* _last.0 [hidden, d], [hidden]                 */
+    const float *last_ln_w, *last_ln_b; /* _last.1 LayerNorm [hidden]                    */
+    const float *last3_w, *last3_b;     /* _last.3 [9,hidden], [9]                       */
     /* schedule tables, each [timesteps] (gaussian_diffuser.py:167-182) */
     const float *sqrt_recip_alphas_cumprod;
     const float *sqrt_recipm1_alphas_cumprod;
@@ -82,6 +93,11 @@ typedef struct pd_weights {
 #define PD_WEIGHTS_PRED_X0 1   /* pd_weights.reserved: GaussianDiffusion(objective="pred_x0") -- the denoiser's output IS x_start
                                 * (models/gaussian_diffuser.py:225-227); pd_p_mean / pd_sample then skip predict_start_from_noise
                                 * and pd_denoise_step still returns the raw model output */
+#define PD_WEIGHTS_POST_NORM 2 /* pd_weights.reserved: TransformerEncoderWrapper(norm_first=False): x = LN1(x + SA(x)); x = LN2(x + FF(x))
+                                * (shape-generic path) */
+#define PD_WEIGHTS_NO_PIVOT 4  /* pd_weights.reserved: Denoiser(pivot_cam_onehot=False): _first has no pivot column, K = 189 + 128 + z_dim
+                                * (shape-generic path) */
+#define PD_WEIGHTS_GENERIC 8   /* pd_weights.reserved: run the shape-generic denoiser path even at the default shape (comparison / testing) */
 
 /* GGS knobs: cfgs/default.yaml:6-13 as passed through **GGS_cfg to GGS_optimize
  * (geometry_guided_sampling.py:67-81). */

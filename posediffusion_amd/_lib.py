@@ -55,6 +55,9 @@ PD_GGS_CFG_FORCE_ONE_HOP = 1
 PD_GGS_CFG_NO_LDS_STAGING = 2
 PD_GGS_CFG_WAVES8 = 4
 PD_WEIGHTS_PRED_X0 = 1
+PD_WEIGHTS_POST_NORM = 2     # TransformerEncoderWrapper(norm_first=False) (shape-generic denoiser path)
+PD_WEIGHTS_NO_PIVOT = 4      # Denoiser(pivot_cam_onehot=False) (shape-generic denoiser path)
+PD_WEIGHTS_GENERIC = 8       # the shape-generic denoiser path even at the default shape (comparison / testing)
 PD_GGS_CFG_LANE_ITEMS = 8       # lane-per-item kernel (the throughput shape) whatever the batch size
 PD_GGS_CFG_NO_LANE_ITEMS = 16   # never the lane-per-item kernel
 PD_GGS_CFG_XCHG_SPREAD = 32     # k > 1: no XCD-local placement of a sequence's workgroups (comparison)

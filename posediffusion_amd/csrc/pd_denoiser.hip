@@ -843,13 +843,26 @@ static int set_lds(KernelT kern, size_t bytes) {
     return PD_OK;
 }
 
-int pd_denoiser_create(pd_engine *eng, const pd_weights *w) {
-    if (w->d_model != DM || w->nhead != NH || w->dim_ff != DFF || w->z_dim != ZD || w->n_harmonic != 10 ||
-        w->t_emb_dim != 256 || w->mlp_hidden != HID || w->num_layers < 1 || w->num_layers > PD_MAX_LAYERS) {
-        pd_set_error("pd_engine_create: unsupported denoiser shape (built for d_model=512 nhead=4 ff=1024 z=384 "
-                     "harmonics=10 t_emb=256 hidden=128, 1..%d layers)", PD_MAX_LAYERS);
-        return PD_ERR_UNSUPPORTED;
+int pd_time_table(const pd_weights *w, float *table) {
+    if (!w->time_w0 || !w->time_b0 || !w->time_w2 || !w->time_b2) {
+        pd_set_error("pd_engine_create: a weight pointer is NULL");
+        return PD_ERR_INVALID_ARG;
     }
+    hipLaunchKernelGGL(pd_time_table_kernel, dim3(w->timesteps), dim3(128), 0, 0, w->time_w0, w->time_b0, w->time_w2, w->time_b2, table);
+    PD_HIP_CHECK(hipGetLastError());
+    return PD_OK;
+}
+
+// the shape the kernels of this file are built for (cfgs/default.yaml); every other legal configuration -- and this one under
+// PD_WEIGHTS_GENERIC -- takes the shape-generic path of pd_denoiser_generic.hip
+static bool pd_denoiser_default_shape(const pd_weights *w) {
+    return w->d_model == DM && w->nhead == NH && w->dim_ff == DFF && w->z_dim == ZD && w->n_harmonic == 10 && w->t_emb_dim == 256 &&
+           w->mlp_hidden == HID && w->num_layers >= 1 && w->num_layers <= PD_MAX_LAYERS &&
+           !(w->reserved & (PD_WEIGHTS_POST_NORM | PD_WEIGHTS_NO_PIVOT | PD_WEIGHTS_GENERIC));
+}
+
+int pd_denoiser_create(pd_engine *eng, const pd_weights *w) {
+    if (!pd_denoiser_default_shape(w)) return pd_denoiser_generic_create(eng, w);
     PdDenoiserDev *d = new PdDenoiserDev();
     eng->den = d;
     d->num_layers = w->num_layers;
@@ -1051,10 +1064,15 @@ static int pd_denoiser_build_split_h(pd_engine *eng) {
     d->split_h_ready = true;
     return PD_OK;
 }
-bool pd_denoiser_has_streamed_path(const pd_engine *eng) { return eng->den && eng->den->hn; }
+bool pd_denoiser_has_streamed_path(const pd_engine *eng) { return eng->den && eng->den->hn; }   // (a generic engine has no den: none)
 bool pd_denoiser_weights_non_finite(const pd_engine *eng) { return eng->den && eng->den->non_finite; }
 
 int pd_denoiser_build_split(pd_engine *eng, int mode) {
+    if (eng->gden) {
+        pd_set_error("split-precision denoiser: this engine runs the shape-generic denoiser path (a non-default configuration or "
+                     "PD_WEIGHTS_GENERIC), which has only the exact-fp32 kernels: PD_OPT_DENOISER_SPLIT stays 0");
+        return PD_ERR_UNSUPPORTED;
+    }
     PdDenoiserDev *d = eng->den;
     if (!d->hn) {
         pd_set_error("split-precision denoiser: the engine was created for fewer than %d token rows (max_B x max_N); the mode "
@@ -1091,6 +1109,7 @@ int pd_denoiser_build_split(pd_engine *eng, int mode) {
 }
 
 void pd_denoiser_destroy(pd_engine *eng) {
+    pd_denoiser_generic_destroy(eng);
     if (!eng->den) return;
     for (void *p : eng->den->allocs) (void)hipFree(p);
     delete eng->den;
@@ -1143,10 +1162,12 @@ static void launch_gemm(GemmArgs &g, float *const wp[2], int MT, int wide_min, h
 // zproj[m] = z[m] W_z^T + b_first, once per sampling call.  Every step then adds its row of the time table and its 192-column GEMM.
 int pd_denoiser_prepare(pd_engine *eng, const float *z, int B, int N, hipStream_t s) {
     PdDenoiserDev *d = eng->den;
+    if (eng->gden) d = nullptr;          // the generic path hoists nothing (pd_denoiser_generic.hip): only the arguments are checked
     if (!z || B <= 0 || N <= 0 || B > eng->max_B || N > eng->max_N) {
         pd_set_error("denoiser: invalid arguments (B=%d N=%d; max_B=%d max_N=%d)", B, N, eng->max_B, eng->max_N);
         return PD_ERR_INVALID_ARG;
     }
+    if (!d) return PD_OK;
     const int M = B * N;
     // (below PD_STREAM_MIN_ROWS token rows _first stays ONE fused launch -- embedding staged in the GEMM's A rows, K = 704: a step there is a
     // chain of 43 latency-bound launches in which the shorter K buys 1 %, and the small-batch results stay bitwise those of rounds 1-4)
@@ -1158,6 +1179,7 @@ int pd_denoiser_prepare(pd_engine *eng, const float *z, int B, int N, hipStream_
 // z_prepared: pd_denoiser_prepare ran for this z (the sampling loop calls it once); otherwise it is issued here (the step-level API)
 int pd_denoiser_launch(pd_engine *eng, const float *x, const float *z, int t, int B, int N, float *eps_out,
                        float *mean_out, float *x0_out, const float *noise, float *x_next_out, hipStream_t s, bool z_prepared) {
+    if (eng->gden) return pd_denoiser_generic_launch(eng, x, z, t, B, N, eps_out, mean_out, x0_out, noise, x_next_out, s);
     PdDenoiserDev *d = eng->den;
     if (!x || !z || B <= 0 || N <= 0 || B > eng->max_B || N > eng->max_N || N > 64 || t < 0 || t >= d->timesteps) {
         pd_set_error("denoiser: invalid arguments (B=%d N=%d t=%d; max_B=%d max_N=%d, N <= 64, 0 <= t < %d)", B, N, t,

@@ -94,7 +94,7 @@ extern "C" int pd_engine_create(const pd_weights *w, int max_B, int max_N, pd_en
         return PD_ERR_INVALID_ARG;
     }
     *out = nullptr;
-    if (w->reserved & ~PD_WEIGHTS_PRED_X0) {
+    if (w->reserved & ~(PD_WEIGHTS_PRED_X0 | PD_WEIGHTS_POST_NORM | PD_WEIGHTS_NO_PIVOT | PD_WEIGHTS_GENERIC)) {
         pd_set_error("pd_engine_create: unknown pd_weights.reserved flags 0x%x", (unsigned)w->reserved);
         return PD_ERR_INVALID_ARG;
     }

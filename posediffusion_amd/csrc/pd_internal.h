@@ -194,13 +194,15 @@ struct PdSeqHost {
 
 // ---- denoiser -----------------------------------------------------------------------------------
 struct PdDenoiserDev;   // defined in pd_denoiser.hip
+struct PdGenericDen;    // defined in pd_denoiser_generic.hip
 
 struct pd_engine {
     int device = 0;
     int num_cus = 0;           // multiProcessorCount (bounds the resident workgroups of the GGS exchange)
     int max_B = 0, max_N = 0;
     int d_model = 0, nhead = 0, dim_ff = 0, num_layers = 0, z_dim = 0, timesteps = 0;
-    PdDenoiserDev *den = nullptr;
+    PdDenoiserDev *den = nullptr;        // the default-shape denoiser's kernels and weights ...
+    PdGenericDen *gden = nullptr;        // ... or the shape-generic path's (exactly one of the two is set)
     // schedule tables (host copies; kernels take the per-step scalars by value)
     std::vector<float> c_recip, c_recipm1, coef1, coef2, logvar;
     int pred_x0 = 0;                      // pd_weights.reserved & PD_WEIGHTS_PRED_X0
@@ -255,6 +257,15 @@ int pd_denoiser_launch(pd_engine *eng, const float *x, const float *z, int t, in
                        float *mean_out, float *x0_out, const float *noise, float *x_next_out, hipStream_t s, bool z_prepared = false);
 // the step-invariant piece of _first for this z (once per sampling call; pd_denoiser_launch(..., z_prepared = true) then skips it)
 int pd_denoiser_prepare(pd_engine *eng, const float *z, int B, int N, hipStream_t s);
+
+// the denoiser's time-embedding table [timesteps, 128] (pd_denoiser.hip; both denoiser paths build it)
+int pd_time_table(const pd_weights *w, float *table);
+// pd_denoiser_generic.hip: the shape-generic path (every engine whose weights are not the default shape, or carry PD_WEIGHTS_GENERIC)
+bool pd_denoiser_generic_shape_ok(const pd_weights *w, char *why, size_t why_len);
+int pd_denoiser_generic_create(pd_engine *eng, const pd_weights *w);
+void pd_denoiser_generic_destroy(pd_engine *eng);
+int pd_denoiser_generic_launch(pd_engine *eng, const float *x, const float *z, int t, int B, int N, float *eps_out, float *mean_out,
+                               float *x0_out, const float *noise, float *x_next_out, hipStream_t s);
 
 // pd_ggs.hip
 int pd_ggs_init();

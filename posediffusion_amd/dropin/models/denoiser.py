@@ -1,8 +1,14 @@
 """Drop-in `Denoiser` / `TransformerEncoderWrapper` (pose_diffusion/models/denoiser.py:22-98).
 
 Same constructor arguments, same parameter names (checkpoints load with strict=True), same
-``forward(x [B,N,9], t [B], z [B,N,384]) -> [B,N,9]`` -- but forward runs the hand-written HIP
-kernels (posediffusion_amd/csrc/pd_denoiser.hip) instead of ~970 ATen launches."""
+``forward(x [B,N,9], t [B], z [B,N,z_dim]) -> [B,N,9]`` -- but forward runs the hand-written HIP
+kernels (posediffusion_amd/csrc/pd_denoiser.hip; pd_denoiser_generic.hip for every configuration
+other than cfgs/default.yaml's) instead of ~970 ATen launches.
+
+The configurations the engine runs (anything else raises ValueError at construction, before any GPU work):
+d_model a multiple of 32 in [32, 2048]; nhead dividing it with a head dim that is a multiple of 4 in [8, 256];
+dim_feedforward in [1, 8192]; 1 to 16 encoder layers; pre- or post-norm; z_dim in [1, 4096]; mlp_hidden_dim in
+[1, 1024]; with or without the pivot one-hot; target_dim 9; batch_first encoders."""
 from typing import Dict
 
 import torch
@@ -12,11 +18,30 @@ from posediffusion_amd.compat import instantiate
 from util.embedding import PoseEmbedding, TimeStepEmbedding
 
 
+MAX_LAYERS = 16     # PD_MAX_LAYERS (include/pd_engine.h)
+
+
+def check_trunk_cfg(d_model: int, nhead: int, num_encoder_layers: int, dim_feedforward: int, batch_first: bool = True):
+    """ValueError naming the limit when the HIP engine cannot run this encoder (the ranges of include/pd_engine.h)."""
+    if not batch_first:
+        raise ValueError("the HIP engine implements batch_first=True encoders only")
+    if d_model % 32 or not 32 <= d_model <= 2048:
+        raise ValueError(f"d_model must be a multiple of 32 in [32, 2048], got {d_model}")
+    if nhead < 1 or d_model % nhead:
+        raise ValueError(f"nhead must divide d_model ({d_model}), got {nhead}")
+    hd = d_model // nhead
+    if hd % 4 or not 8 <= hd <= 256:
+        raise ValueError(f"the head dim d_model / nhead must be a multiple of 4 in [8, 256], got {hd}")
+    if not 1 <= dim_feedforward <= 8192:
+        raise ValueError(f"dim_feedforward must be in [1, 8192], got {dim_feedforward}")
+    if not 1 <= num_encoder_layers <= MAX_LAYERS:
+        raise ValueError(f"num_encoder_layers must be in [1, {MAX_LAYERS}], got {num_encoder_layers}")
+
+
 def TransformerEncoderWrapper(d_model: int, nhead: int, num_encoder_layers: int, dim_feedforward: int = 2048,
                               dropout: float = 0.1, norm_first: bool = True, batch_first: bool = True):
     """Weight container with nn.TransformerEncoder's parameter names (denoiser.py:79-98)."""
-    if not (norm_first and batch_first):
-        raise ValueError("the HIP engine implements the pre-norm, batch-first encoder of cfgs/default.yaml")
+    check_trunk_cfg(d_model, nhead, num_encoder_layers, dim_feedforward, batch_first)
     layer = nn.TransformerEncoderLayer(d_model=d_model, nhead=nhead, dim_feedforward=dim_feedforward, dropout=dropout,
                                        batch_first=batch_first, norm_first=norm_first)
     return nn.TransformerEncoder(layer, num_encoder_layers)
@@ -26,8 +51,12 @@ class Denoiser(nn.Module):
     def __init__(self, TRANSFORMER: Dict, target_dim: int = 9, pivot_cam_onehot: bool = True, z_dim: int = 384,
                  mlp_hidden_dim: int = 128):
         super().__init__()
-        if target_dim != 9 or not pivot_cam_onehot:
-            raise ValueError("the HIP engine is built for target_dim=9 with the pivot one-hot")
+        if target_dim != 9:
+            raise ValueError(f"the HIP engine is built for target_dim=9 (the 9-wide pose encoding), got {target_dim}")
+        if not 1 <= z_dim <= 4096:
+            raise ValueError(f"z_dim must be in [1, 4096], got {z_dim}")
+        if not 1 <= mlp_hidden_dim <= 1024:
+            raise ValueError(f"mlp_hidden_dim must be in [1, 1024], got {mlp_hidden_dim}")
         self.pivot_cam_onehot, self.target_dim = pivot_cam_onehot, target_dim
         self.time_embed = TimeStepEmbedding()
         self.pose_embed = PoseEmbedding(target_dim=target_dim)

@@ -37,10 +37,13 @@ def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
 
 class PoseEngine:
     """One engine per device.  ``denoiser_sd`` uses the reference Denoiser's state_dict keys
-    (``time_embed.linear.0.weight`` ... ``_last.3.bias``); ``tables`` the GaussianDiffusion buffers."""
+    (``time_embed.linear.0.weight`` ... ``_last.3.bias``); ``tables`` the GaussianDiffusion buffers.  ``norm_first`` /
+    ``pivot``: TransformerEncoderWrapper(norm_first=...) and Denoiser(pivot_cam_onehot=...); ``generic``: run the shape-generic
+    denoiser kernels even at the default shape (PD_WEIGHTS_GENERIC, comparison / testing)."""
 
     def __init__(self, denoiser_sd: Dict[str, torch.Tensor], tables: Dict[str, torch.Tensor], device=None,
-                 max_B: int = 8, max_N: int = 20, num_layers: int = 8, nhead: int = 4, objective: str = "pred_noise"):
+                 max_B: int = 8, max_N: int = 20, num_layers: int = 8, nhead: int = 4, objective: str = "pred_noise",
+                 norm_first: bool = True, pivot: bool = True, generic: bool = False):
         if objective not in ("pred_noise", "pred_x0"):                     # models/gaussian_diffuser.py:105-108
             raise AssertionError("objective must be either pred_noise (predict noise) or pred_x0 (predict image start)")
         if not torch.cuda.is_available():
@@ -67,9 +70,10 @@ class PoseEngine:
         w.mlp_hidden = sd["_last.0.weight"].shape[0]
         w.t_emb_dim = sd["time_embed.linear.0.weight"].shape[1]
         w.n_harmonic = 10
-        w.z_dim = sd["_first.weight"].shape[1] - (9 * 21 + w.t_emb_dim // 2 + 1)
+        w.z_dim = sd["_first.weight"].shape[1] - (9 * 21 + w.t_emb_dim // 2 + int(bool(pivot)))
         w.timesteps = int(tables[_TABLES[0]].shape[0])
-        w.reserved = _lib.PD_WEIGHTS_PRED_X0 if objective == "pred_x0" else 0
+        w.reserved = ((_lib.PD_WEIGHTS_PRED_X0 if objective == "pred_x0" else 0) | (0 if norm_first else _lib.PD_WEIGHTS_POST_NORM)
+                      | (0 if pivot else _lib.PD_WEIGHTS_NO_PIVOT) | (_lib.PD_WEIGHTS_GENERIC if generic else 0))
         self.objective = objective
         w.time_w0, w.time_b0 = dev(sd["time_embed.linear.0.weight"]), dev(sd["time_embed.linear.0.bias"])
         w.time_w2, w.time_b2 = dev(sd["time_embed.linear.2.weight"]), dev(sd["time_embed.linear.2.bias"])

@@ -59,8 +59,10 @@ def get_engine(denoiser: torch.nn.Module, diffuser: Optional[torch.nn.Module], B
         tables = diffusion_buffers()
     layers = len(denoiser._trunk.layers)
     nhead = denoiser._trunk.layers[0].self_attn.num_heads
+    norm_first = bool(denoiser._trunk.layers[0].norm_first)
+    pivot = bool(getattr(denoiser, "pivot_cam_onehot", True))
     eng = PoseEngine(denoiser_state(denoiser), tables, device=dev, max_B=max(B, 1), max_N=max(N, 1),
-                     num_layers=layers, nhead=nhead, objective=objective or "pred_noise")
+                     num_layers=layers, nhead=nhead, objective=objective or "pred_noise", norm_first=norm_first, pivot=pivot)
     cache["e"] = (fp, eng)
     _ENGINES[dev.index if dev.index is not None else torch.cuda.current_device()] = eng
     return eng
