@@ -42,45 +42,6 @@
 #include <stdlib.h>
 #include <string.h>
 
-// --------------------------------------------------------------------------------------------
-// weight repack: W[Nout][K] row-major -> MFMA-fragment order (zero padded), optionally with a
-// LayerNorm gamma folded in as a column scale (W' = W diag(gamma): LN(x) W^T = xhat (W diag(gamma))^T + W beta)
-//   NT = 32 (v_mfma_f32_32x32x2_f32):  Wp[nt][kc][lane][4] = W[nt*32 + (l & 31)][kc*8  + 4*(l >> 5) + e]
-//   NT = 16 (v_mfma_f32_16x16x4_f32):  Wp[nt][kc][lane][4] = W[nt*16 + (l & 15)][kc*16 + 4*(l >> 4) + e]
-// --------------------------------------------------------------------------------------------
-__global__ void pd_repack_kernel(const float *__restrict__ W, int Nout, int K, int KC, float *__restrict__ Wp, size_t total,
-                                 int first_perm, int nt_width, const float *__restrict__ colscale) {
-    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
-        const int e = idx & 3;
-        const int l = (idx >> 2) & 63;
-        const size_t rest = idx >> 8;
-        const int kc = (int)(rest % KC);
-        const int nt = (int)(rest / KC);
-        int n, k;
-        if (nt_width == 32) {
-            n = nt * 32 + (l & 31);
-            k = kc * 8 + 4 * (l >> 5) + e;
-        } else {
-            n = nt * 16 + (l & 15);
-            k = kc * 16 + 4 * (l >> 4) + e;
-        }
-        if (first_perm) k = pd_first_col_all(k);
-        float v = (n < Nout && k < K) ? W[(size_t)n * K + k] : 0.0f;
-        if (colscale && k < K) v *= colscale[k];
-        Wp[idx] = v;
-    }
-}
-
-// b'[n] = b[n] + sum_k W[n][k] beta[k]   (the LayerNorm shift folded into the following bias)
-__global__ void pd_fold_bias_kernel(const float *__restrict__ W, const float *__restrict__ beta, const float *__restrict__ b,
-                                    int Nout, int K, float *__restrict__ out) {
-    const int n = blockIdx.x * blockDim.x + threadIdx.x;
-    if (n >= Nout) return;
-    float a = 0.0f;
-    for (int k = 0; k < K; ++k) a = fmaf(W[(size_t)n * K + k], beta[k], a);
-    out[n] = b[n] + a;
-}
-
 // _first's STEP rows for the streamed path (>= PD_STREAM_MIN_ROWS token rows): [harmonic(x) (180) | x (9) | pivot | 0 0] = KFIRST_D
 // columns (piece PD_FIRST_D of pd_denoiser_dev.h), one wave per row, written once per step and read by pd_gemm_dma like any activation
 // (denoiser.py:60-68; the same expressions as the AMODE 2 staging of the small-batch pd_gemm_kernel).  z and t_emb never enter the loop: their products
@@ -775,74 +736,6 @@ __global__ __launch_bounds__(256) void pd_tail_kernel(HeadArgs g) {
 // --------------------------------------------------------------------------------------------
 // host side
 // --------------------------------------------------------------------------------------------
-static int dev_alloc(PdDenoiserDev *d, float **p, size_t n_floats) {
-    PD_HIP_CHECK(hipMalloc((void **)p, n_floats * sizeof(float)));
-    d->allocs.push_back(*p);
-    return PD_OK;
-}
-static int dev_copy(PdDenoiserDev *d, float **dst, const float *src, size_t n) {
-    if (!src) {
-        pd_set_error("pd_engine_create: a weight pointer is NULL");
-        return PD_ERR_INVALID_ARG;
-    }
-    int rc = dev_alloc(d, dst, n);
-    if (rc) return rc;
-    PD_HIP_CHECK(hipMemcpy(*dst, src, n * sizeof(float), hipMemcpyDeviceToDevice));
-    return PD_OK;
-}
-// pack W for tile width nt (32 or 16); gamma (nullable) is folded in as a column scale
-static int dev_pack(PdDenoiserDev *d, float **dst, const float *W, int Nout, int K, int Kpad, int nt, int first_perm = 0,
-                    const float *gamma = nullptr) {
-    if (!W) {
-        pd_set_error("pd_engine_create: a weight pointer is NULL");
-        return PD_ERR_INVALID_ARG;
-    }
-    const int NT = (Nout + nt - 1) / nt, KC = Kpad / (nt == 32 ? 8 : 16);
-    const size_t total = (size_t)NT * KC * 256;
-    int rc = dev_alloc(d, dst, total);
-    if (rc) return rc;
-    hipLaunchKernelGGL(pd_repack_kernel, dim3(512), dim3(256), 0, 0, W, Nout, K, KC, *dst, total, first_perm, nt, gamma);
-    PD_HIP_CHECK(hipGetLastError());
-    return PD_OK;
-}
-// row-major copy with gamma (nullable) folded in as a column scale, for pd_gemm_stream
-static int dev_rowmajor(PdDenoiserDev *d, float **dst, const float *W, int Nout, int K, const float *gamma) {
-    if (!W) {
-        pd_set_error("pd_engine_create: a weight pointer is NULL");
-        return PD_ERR_INVALID_ARG;
-    }
-    const size_t total = (size_t)Nout * K;
-    int rc = dev_alloc(d, dst, total);
-    if (rc) return rc;
-    hipLaunchKernelGGL(pd_scale_cols_kernel, dim3(512), dim3(256), 0, 0, W, gamma, K, total, *dst);
-    PD_HIP_CHECK(hipGetLastError());
-    return PD_OK;
-}
-// b' = b + W beta
-static int dev_fold_bias(PdDenoiserDev *d, float **dst, const float *W, const float *beta, const float *b, int Nout, int K) {
-    if (!W || !beta || !b) {
-        pd_set_error("pd_engine_create: a weight pointer is NULL");
-        return PD_ERR_INVALID_ARG;
-    }
-    int rc = dev_alloc(d, dst, Nout);
-    if (rc) return rc;
-    hipLaunchKernelGGL(pd_fold_bias_kernel, dim3((Nout + 127) / 128), dim3(128), 0, 0, W, beta, b, Nout, K, *dst);
-    PD_HIP_CHECK(hipGetLastError());
-    return PD_OK;
-}
-
-#define PD_TRY(expr)        \
-    do {                    \
-        int _rc = (expr);   \
-        if (_rc) return _rc; \
-    } while (0)
-
-template <typename KernelT>
-static int set_lds(KernelT kern, size_t bytes) {
-    PD_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    return PD_OK;
-}
-
 int pd_time_table(const pd_weights *w, float *table) {
     if (!w->time_w0 || !w->time_b0 || !w->time_w2 || !w->time_b2) {
         pd_set_error("pd_engine_create: a weight pointer is NULL");
@@ -865,35 +758,27 @@ int pd_denoiser_create(pd_engine *eng, const pd_weights *w) {
     if (!pd_denoiser_default_shape(w)) return pd_denoiser_generic_create(eng, w);
     PdDenoiserDev *d = new PdDenoiserDev();
     eng->den = d;
+    PdDevAllocs &m = d->mem;
     d->num_layers = w->num_layers;
     d->timesteps = w->timesteps;
     d->m_cap = ((eng->max_B * eng->max_N + 31) / 32) * 32;
-    // time embedding table
-    {
-        float *w0, *b0, *w2, *b2;
-        PD_TRY(dev_copy(d, &w0, w->time_w0, 128 * 256));
-        PD_TRY(dev_copy(d, &b0, w->time_b0, 128));
-        PD_TRY(dev_copy(d, &w2, w->time_w2, 128 * 128));
-        PD_TRY(dev_copy(d, &b2, w->time_b2, 128));
-        PD_TRY(dev_alloc(d, &d->t_table, (size_t)w->timesteps * 128));
-        hipLaunchKernelGGL(pd_time_table_kernel, dim3(w->timesteps), dim3(128), 0, 0, w0, b0, w2, b2, d->t_table);
-        PD_HIP_CHECK(hipGetLastError());
-    }
+    PD_TRY(m.alloc(&d->t_table, (size_t)w->timesteps * 128));
+    PD_TRY(pd_time_table(w, d->t_table));
     for (int v = 0; v < 2; ++v) {   // v = 0: 32-wide tiles, v = 1: 16-wide tiles
         const int nt = v ? 16 : 32;
-        PD_TRY(dev_pack(d, &d->first_wp[v], w->first_w, DM, KFIRST, KFIRST_PAD, nt, 1));
-        PD_TRY(dev_pack(d, &d->last0_wp[v], w->last0_w, HID, DM, DM, nt));
+        PD_TRY(m.pack(&d->first_wp[v], w->first_w, DM, KFIRST, KFIRST_PAD, nt, nullptr, 1));
+        PD_TRY(m.pack(&d->last0_wp[v], w->last0_w, HID, DM, DM, nt, nullptr));
         for (int l = 0; l < w->num_layers; ++l) {
             const pd_layer_weights &s = w->layers[l];
             PdLayerDev &L = d->layers[l];
             // LayerNorm affine folded: W' = W diag(gamma) (packed), b' = b + W beta
-            PD_TRY(dev_pack(d, &L.qkv_wp[v], s.in_proj_w, 3 * DM, DM, DM, nt, 0, s.norm1_w));
-            PD_TRY(dev_pack(d, &L.out_wp[v], s.out_proj_w, DM, DM, DM, nt));
-            PD_TRY(dev_pack(d, &L.ff1_wp[v], s.linear1_w, DFF, DM, DM, nt, 0, s.norm2_w));
-            PD_TRY(dev_pack(d, &L.ff2_wp[v], s.linear2_w, DM, DFF, DFF, nt));
+            PD_TRY(m.pack(&L.qkv_wp[v], s.in_proj_w, 3 * DM, DM, DM, nt, s.norm1_w));
+            PD_TRY(m.pack(&L.out_wp[v], s.out_proj_w, DM, DM, DM, nt, nullptr));
+            PD_TRY(m.pack(&L.ff1_wp[v], s.linear1_w, DFF, DM, DM, nt, s.norm2_w));
+            PD_TRY(m.pack(&L.ff2_wp[v], s.linear2_w, DM, DFF, DFF, nt, nullptr));
         }
     }
-    PD_TRY(dev_copy(d, &d->first_b, w->first_b, DM));
+    PD_TRY(m.copy(&d->first_b, w->first_b, DM));
     for (int l = 0; l < w->num_layers; ++l) {
         const pd_layer_weights &s = w->layers[l];
         PdLayerDev &L = d->layers[l];
@@ -901,172 +786,80 @@ int pd_denoiser_create(pd_engine *eng, const pd_weights *w) {
             pd_set_error("pd_engine_create: a LayerNorm weight pointer is NULL");
             return PD_ERR_INVALID_ARG;
         }
-        PD_TRY(dev_fold_bias(d, &L.qkv_b, s.in_proj_w, s.norm1_b, s.in_proj_b, 3 * DM, DM));
-        PD_TRY(dev_copy(d, &L.out_b, s.out_proj_b, DM));
-        PD_TRY(dev_fold_bias(d, &L.ff1_b, s.linear1_w, s.norm2_b, s.linear1_b, DFF, DM));
-        PD_TRY(dev_copy(d, &L.ff2_b, s.linear2_b, DM));
-        PD_TRY(dev_rowmajor(d, &L.qkv_wf, s.in_proj_w, 3 * DM, DM, s.norm1_w));
-        PD_TRY(dev_rowmajor(d, &L.out_wf, s.out_proj_w, DM, DM, nullptr));
-        PD_TRY(dev_rowmajor(d, &L.ff1_wf, s.linear1_w, DFF, DM, s.norm2_w));
-        PD_TRY(dev_rowmajor(d, &L.ff2_wf, s.linear2_w, DM, DFF, nullptr));
+        PD_TRY(m.fold_bias(&L.qkv_b, s.in_proj_w, s.norm1_b, s.in_proj_b, 3 * DM, DM));
+        PD_TRY(m.copy(&L.out_b, s.out_proj_b, DM));
+        PD_TRY(m.fold_bias(&L.ff1_b, s.linear1_w, s.norm2_b, s.linear1_b, DFF, DM));
+        PD_TRY(m.copy(&L.ff2_b, s.linear2_b, DM));
+        PD_TRY(m.rowmajor(&L.qkv_wf, s.in_proj_w, 3 * DM, DM, s.norm1_w));
+        PD_TRY(m.rowmajor(&L.out_wf, s.out_proj_w, DM, DM, nullptr));
+        PD_TRY(m.rowmajor(&L.ff1_wf, s.linear1_w, DFF, DM, s.norm2_w));
+        PD_TRY(m.rowmajor(&L.ff2_wf, s.linear2_w, DM, DFF, nullptr));
     }
-    PD_TRY(dev_copy(d, &d->last0_b, w->last0_b, HID));
-    PD_TRY(dev_copy(d, &d->last_ln_w, w->last_ln_w, HID));
-    PD_TRY(dev_copy(d, &d->last_ln_b, w->last_ln_b, HID));
-    PD_TRY(dev_copy(d, &d->last3_w, w->last3_w, 9 * HID));
-    PD_TRY(dev_copy(d, &d->last3_b, w->last3_b, 9));
+    PD_TRY(m.copy(&d->last0_b, w->last0_b, HID));
+    PD_TRY(m.copy(&d->last_ln_w, w->last_ln_w, HID));
+    PD_TRY(m.copy(&d->last_ln_b, w->last_ln_b, HID));
+    PD_TRY(m.copy(&d->last3_w, w->last3_w, 9 * HID));
+    PD_TRY(m.copy(&d->last3_b, w->last3_b, 9));
     const size_t rows = (size_t)d->m_cap;
-    PD_TRY(dev_alloc(d, &d->h, rows * DM));
-    PD_TRY(dev_alloc(d, &d->qkv, rows * 3 * DM));
-    PD_TRY(dev_alloc(d, &d->ctx, rows * DM));
-    PD_TRY(dev_alloc(d, &d->ff, rows * DFF));
-    PD_TRY(dev_alloc(d, &d->hid, rows * HID));
-    if (rows >= PD_STREAM_MIN_ROWS) PD_TRY(dev_alloc(d, &d->hn, rows * DM));
+    PD_TRY(m.alloc(&d->h, rows * DM));
+    PD_TRY(m.alloc(&d->qkv, rows * 3 * DM));
+    PD_TRY(m.alloc(&d->ctx, rows * DM));
+    PD_TRY(m.alloc(&d->ff, rows * DFF));
+    PD_TRY(m.alloc(&d->hid, rows * HID));
+    if (rows >= PD_STREAM_MIN_ROWS) PD_TRY(m.alloc(&d->hn, rows * DM));
     // _first's input rows (materialised by pd_embed_rows_kernel on the streamed path, formerly also by the parked persistent kernel) and the
     // row-major _first / _last.0 the two paths pack from
     if (d->hn) {      // the streamed path evaluates _first in three pieces (pd_denoiser_dev.h): two of them outside the diffusion steps
-        PD_TRY(dev_alloc(d, &d->emb, rows * KFIRST_D));
-        PD_TRY(dev_alloc(d, &d->zproj, rows * DM));
-        PD_TRY(dev_alloc(d, &d->first_df, (size_t)DM * KFIRST_D));
-        PD_TRY(dev_alloc(d, &d->first_zf, (size_t)DM * ZD));
+        PD_TRY(m.alloc(&d->emb, rows * KFIRST_D));
+        PD_TRY(m.alloc(&d->zproj, rows * DM));
+        PD_TRY(m.alloc(&d->first_df, (size_t)DM * KFIRST_D));
+        PD_TRY(m.alloc(&d->first_zf, (size_t)DM * ZD));
         hipLaunchKernelGGL(pd_first_rowmajor_kernel, dim3((DM * KFIRST_D + 255) / 256), dim3(256), 0, 0, w->first_w, d->first_df, PD_FIRST_D, KFIRST_D);
         hipLaunchKernelGGL(pd_first_rowmajor_kernel, dim3((DM * ZD + 255) / 256), dim3(256), 0, 0, w->first_w, d->first_zf, PD_FIRST_Z, ZD);
         PD_HIP_CHECK(hipGetLastError());
         // the time piece of _first for every step: ttab[t] = W_t t_emb(t)
-        PD_TRY(dev_alloc(d, &d->ttab, (size_t)w->timesteps * DM));
+        PD_TRY(m.alloc(&d->ttab, (size_t)w->timesteps * DM));
         hipLaunchKernelGGL(pd_first_ttab_kernel, dim3(w->timesteps), dim3(DM), 0, 0, w->first_w, d->t_table, d->ttab);
         PD_HIP_CHECK(hipGetLastError());
     }
-    PD_TRY(dev_rowmajor(d, &d->last0_wf, w->last0_w, HID, DM, nullptr));
-    PD_TRY(set_lds(pd_gemm_kernel<KFIRST_PAD, 2, 0, 32>, 32 * (KFIRST_PAD + 4) * 4));
-    PD_TRY(set_lds(pd_gemm_kernel<KFIRST_PAD, 2, 0, 16>, 32 * (KFIRST_PAD + 4) * 4));
-    PD_TRY(set_lds(pd_gemm_kernel<DM, 1, 0, 32>, 32 * (DM + 4) * 4));
-    PD_TRY(set_lds(pd_gemm_kernel<DM, 1, 0, 16>, 32 * (DM + 4) * 4));
-    PD_TRY(set_lds(pd_gemm_kernel<DM, 1, 1, 32>, 32 * (DM + 4) * 4));
-    PD_TRY(set_lds(pd_gemm_kernel<DM, 1, 1, 16>, 32 * (DM + 4) * 4));
-    PD_TRY(set_lds(pd_gemm_kernel<DM, 0, 2, 32>, 32 * (DM + 4) * 4));
-    PD_TRY(set_lds(pd_gemm_kernel<DM, 0, 2, 16>, 32 * (DM + 4) * 4));
-    PD_TRY(set_lds(pd_gemm_kernel<DFF, 0, 2, 32>, 32 * (DFF + 4) * 4));
-    PD_TRY(set_lds(pd_gemm_kernel<DFF, 0, 2, 16>, 32 * (DFF + 4) * 4));
-    PD_TRY(set_lds(pd_gemm_kernel<DM, 0, 0, 32>, 32 * (DM + 4) * 4));
-    PD_TRY(set_lds(pd_gemm_kernel<DM, 0, 0, 16>, 32 * (DM + 4) * 4));
-    PD_TRY(set_lds(pd_attn_kernel<false>, ((2 * 64 + 4) * (DH + 4) + 4 * 64) * 4));
-    PD_TRY(set_lds(pd_attn_kernel<true>, ((2 * 64 + 4) * (DH + 4) + 4 * 64) * 4));
-    PD_TRY(set_lds(pd_attn_seq_kernel<0>, attn_seq_lds(64)));
-    PD_TRY(set_lds(pd_attn_seq_kernel<1>, attn_seq_lds(64)));
-    PD_TRY(set_lds(pd_attn_seq_kernel<2>, attn_seq_lds(64)));
-    PD_TRY(set_lds(pd_attn_mma_kernel<2>, attn_mma_lds(32)));
-    PD_TRY(set_lds((pd_qkv_attn_kernel<0, PD_QA_DEEP_DEFAULT != 0>), 160 * 1024));
+    PD_TRY(m.rowmajor(&d->last0_wf, w->last0_w, HID, DM, nullptr));
+    PD_TRY(pd_set_lds(pd_gemm_kernel<KFIRST_PAD, 2, 0, 32>, 32 * (KFIRST_PAD + 4) * 4));
+    PD_TRY(pd_set_lds(pd_gemm_kernel<KFIRST_PAD, 2, 0, 16>, 32 * (KFIRST_PAD + 4) * 4));
+    PD_TRY(pd_set_lds(pd_gemm_kernel<DM, 1, 0, 32>, 32 * (DM + 4) * 4));
+    PD_TRY(pd_set_lds(pd_gemm_kernel<DM, 1, 0, 16>, 32 * (DM + 4) * 4));
+    PD_TRY(pd_set_lds(pd_gemm_kernel<DM, 1, 1, 32>, 32 * (DM + 4) * 4));
+    PD_TRY(pd_set_lds(pd_gemm_kernel<DM, 1, 1, 16>, 32 * (DM + 4) * 4));
+    PD_TRY(pd_set_lds(pd_gemm_kernel<DM, 0, 2, 32>, 32 * (DM + 4) * 4));
+    PD_TRY(pd_set_lds(pd_gemm_kernel<DM, 0, 2, 16>, 32 * (DM + 4) * 4));
+    PD_TRY(pd_set_lds(pd_gemm_kernel<DFF, 0, 2, 32>, 32 * (DFF + 4) * 4));
+    PD_TRY(pd_set_lds(pd_gemm_kernel<DFF, 0, 2, 16>, 32 * (DFF + 4) * 4));
+    PD_TRY(pd_set_lds(pd_gemm_kernel<DM, 0, 0, 32>, 32 * (DM + 4) * 4));
+    PD_TRY(pd_set_lds(pd_gemm_kernel<DM, 0, 0, 16>, 32 * (DM + 4) * 4));
+    PD_TRY(pd_set_lds(pd_attn_kernel<false>, ((2 * 64 + 4) * (DH + 4) + 4 * 64) * 4));
+    PD_TRY(pd_set_lds(pd_attn_kernel<true>, ((2 * 64 + 4) * (DH + 4) + 4 * 64) * 4));
+    PD_TRY(pd_set_lds(pd_attn_seq_kernel<0>, attn_seq_lds(64)));
+    PD_TRY(pd_set_lds(pd_attn_seq_kernel<1>, attn_seq_lds(64)));
+    PD_TRY(pd_set_lds(pd_attn_seq_kernel<2>, attn_seq_lds(64)));
+    PD_TRY(pd_set_lds(pd_attn_mma_kernel<2>, attn_mma_lds(32)));
+    PD_TRY(pd_set_lds((pd_qkv_attn_kernel<0, PD_QA_DEEP_DEFAULT != 0>), 160 * 1024));
 #ifdef PD_DEV_KNOBS
-    PD_TRY(set_lds((pd_qkv_attn_kernel<0, PD_QA_DEEP_DEFAULT == 0>), 160 * 1024));
-    PD_TRY(set_lds(pd_qkv_attn_kernel<1>, 160 * 1024));
-    PD_TRY(set_lds(pd_qkv_attn_kernel<2>, 160 * 1024));
-    PD_TRY(set_lds(pd_qkv_attn_kernel<3>, 160 * 1024));
-    PD_TRY(set_lds(pd_qkv_attn_kernel<4>, 160 * 1024));
-    PD_TRY(set_lds(pd_qkv_attn_kernel<5>, 160 * 1024));
+    PD_TRY(pd_set_lds((pd_qkv_attn_kernel<0, PD_QA_DEEP_DEFAULT == 0>), 160 * 1024));
+    PD_TRY(pd_set_lds(pd_qkv_attn_kernel<1>, 160 * 1024));
+    PD_TRY(pd_set_lds(pd_qkv_attn_kernel<2>, 160 * 1024));
+    PD_TRY(pd_set_lds(pd_qkv_attn_kernel<3>, 160 * 1024));
+    PD_TRY(pd_set_lds(pd_qkv_attn_kernel<4>, 160 * 1024));
+    PD_TRY(pd_set_lds(pd_qkv_attn_kernel<5>, 160 * 1024));
 #endif
     PD_HIP_CHECK(hipDeviceSynchronize());
     return PD_OK;
 }
 
-// The fast mode's weights: every encoder Linear split into bf16 hi / lo in MFMA fragment order (LayerNorm scale folded as for
-// the other packings).  Built when the mode is first switched on, from the row-major fp32 copies kept for the streamed GEMMs.
-// mode 2, fp16 planes: fp16 keeps 11 bits and five exponent bits, so every operand gets a POWER-OF-TWO scale (exact to apply and
-// to undo) fixed here from bounds that hold for every input:
-//   * LayerNorm output without affine: sum of squares <= D, so |x^| <= sqrt(D) = 22.6;           scale 2^9  (<= 11 585)
-//   * a Linear fed by it:  |x^ . w + b| <= sqrt(D) ||w||_2 + |b|   (Cauchy-Schwarz) -- the V rows the attention averages
-//     (a convex combination: same bound) and the FF hidden rows after ReLU;                       scale 2^floor(log2(32768 / bound))
-//   * weights: 2^floor(log2(16384 / max |w|)).
-// Nothing can overflow (fp16 max 65 504), and hi + lo keeps 22 bits for every value above 2^-18 of its bound.
-static int floor_log2_ratio(double cap, double v) {       // v finite (pd_denoiser_build_scales rejects anything else)
-    if (!(v > 0.0)) return 0;
-    double e = floor(log2(cap / v));                       // clamped as a double: the cast below is always defined
-    e = e < -60.0 ? -60.0 : (e > 60.0 ? 60.0 : e);
-    return (int)e;
-}
-static int pd_denoiser_build_scales(pd_engine *eng) {
-    PdDenoiserDev *d = eng->den;
-    if (d->scales_ready) return PD_OK;
-    std::vector<float> w, b;
-    auto fetch = [&](const float *Wf, const float *bias, int Nout, int K) -> int {
-        w.resize((size_t)Nout * K);
-        b.resize(Nout);
-        PD_HIP_CHECK(hipMemcpy(w.data(), Wf, w.size() * sizeof(float), hipMemcpyDeviceToHost));
-        PD_HIP_CHECK(hipMemcpy(b.data(), bias, b.size() * sizeof(float), hipMemcpyDeviceToHost));
-        return PD_OK;
-    };
-    // a checkpoint with inf / NaN has no static bound: the fp16-plane mode is refused (PD_ERR_INVALID_ARG) and the engine stays on
-    // the exact-fp32 kernels, which propagate the values like the reference does
-    bool finite = true;
-    auto max_abs = [&]() { double m = 0; for (float v : w) { finite = finite && isfinite(v); m = fmax(m, fabs((double)v)); } return m; };
-    auto row_bound = [&](int r0, int r1, int K) {            // max over rows of sqrt(D) ||w_r||_2 + |b_r|
-        double bound = 0;
-        for (int r = r0; r < r1; ++r) {
-            double q = 0;
-            for (int k = 0; k < K; ++k) q += (double)w[(size_t)r * K + k] * w[(size_t)r * K + k];
-            bound = fmax(bound, sqrt((double)DM) * sqrt(q) + fabs((double)b[r]));
-            finite = finite && isfinite(q) && isfinite(b[r]);
-        }
-        return bound;
-    };
-    const int e_ln = 9;
-    PD_HIP_CHECK(hipDeviceSynchronize());
-    for (int l = 0; l < d->num_layers; ++l) {
-        PdLayerDev &L = d->layers[l];
-        PD_TRY(fetch(L.qkv_wf, L.qkv_b, 3 * DM, DM));
-        const int e_ctx = floor_log2_ratio(32768.0, row_bound(2 * DM, 3 * DM, DM));
-        L.e_wqkv = floor_log2_ratio(16384.0, max_abs());
-        PD_TRY(fetch(L.out_wf, L.out_b, DM, DM));
-        L.e_wo = floor_log2_ratio(16384.0, max_abs());
-        PD_TRY(fetch(L.ff1_wf, L.ff1_b, DFF, DM));
-        const int e_ff = floor_log2_ratio(32768.0, row_bound(0, DFF, DM));
-        L.e_w1 = floor_log2_ratio(16384.0, max_abs());
-        PD_TRY(fetch(L.ff2_wf, L.ff2_b, DM, DFF));
-        L.e_w2 = floor_log2_ratio(16384.0, max_abs());
-        L.qkv_cs = ldexpf(1.0f, -(e_ln + L.e_wqkv));
-        L.out_cs = ldexpf(1.0f, -(e_ctx + L.e_wo));
-        L.ff1_cs = ldexpf(1.0f, -(e_ln + L.e_w1));
-        L.ff2_cs = ldexpf(1.0f, -(e_ff + L.e_w2));
-        L.ctx_scale = ldexpf(1.0f, e_ctx);
-        L.ff_scale = ldexpf(1.0f, e_ff);
-        if (!finite) {
-            d->non_finite = true;
-            pd_set_error("denoiser: encoder layer %d holds non-finite weights or biases: no static operand bound exists, the fp16-plane "
-                         "mode (PD_OPT_DENOISER_SPLIT = 2) is not available for these weights", l);
-            return PD_ERR_INVALID_ARG;
-        }
-    }
-    d->scales_ready = true;
-    return PD_OK;
-}
-static int pd_denoiser_build_split_h(pd_engine *eng) {
-    PdDenoiserDev *d = eng->den;
-    if (d->split_h_ready) return PD_OK;
-    PD_TRY(pd_denoiser_build_scales(eng));
-    auto split = [&](unsigned **dst, const float *Wf, int Nout, int K, int ew) -> int {
-        float *p = nullptr;
-        int rc = dev_alloc(d, &p, (size_t)Nout * K);
-        if (rc) return rc;
-        *dst = (unsigned *)p;
-        const size_t total = (size_t)(Nout / 32) * (K / 16) * 64;
-        hipLaunchKernelGGL(vit_frag_split_kernel, dim3(512), dim3(256), 0, 0, Wf, (const float *)nullptr, K, total, (uint4 *)p, 1, ldexpf(1.0f, ew));
-        PD_HIP_CHECK(hipGetLastError());
-        return PD_OK;
-    };
-    for (int l = 0; l < d->num_layers; ++l) {
-        PdLayerDev &L = d->layers[l];
-        PD_TRY(split(&L.qkv_wh, L.qkv_wf, 3 * DM, DM, L.e_wqkv));
-        PD_TRY(split(&L.out_wh, L.out_wf, DM, DM, L.e_wo));
-        PD_TRY(split(&L.ff1_wh, L.ff1_wf, DFF, DM, L.e_w1));
-        PD_TRY(split(&L.ff2_wh, L.ff2_wf, DM, DFF, L.e_w2));
-    }
-    PD_HIP_CHECK(hipDeviceSynchronize());
-    d->split_h_ready = true;
-    return PD_OK;
-}
 bool pd_denoiser_has_streamed_path(const pd_engine *eng) { return eng->den && eng->den->hn; }   // (a generic engine has no den: none)
 bool pd_denoiser_weights_non_finite(const pd_engine *eng) { return eng->den && eng->den->non_finite; }
 
+// The split-precision modes' weights, built when the mode is first switched on from the row-major fp32 copies kept for the streamed
+// GEMMs (LayerNorm scale folded): every encoder Linear split into bf16 hi / lo (mode 1, the fast mode) or into fp16 hi / lo of w * 2^e
+// (mode 2) in MFMA fragment order.  Mode 2's power-of-two scales come from pd_plane_exponents; the LayerNorm operand takes 2^9.
 int pd_denoiser_build_split(pd_engine *eng, int mode) {
     if (eng->gden) {
         pd_set_error("split-precision denoiser: this engine runs the shape-generic denoiser path (a non-default configuration or "
@@ -1079,39 +872,45 @@ int pd_denoiser_build_split(pd_engine *eng, int mode) {
                      "applies to the streamed large-batch path only", PD_STREAM_MIN_ROWS);
         return PD_ERR_UNSUPPORTED;
     }
-    if (mode == 2) return pd_denoiser_build_split_h(eng);
-    if (d->split_ready) return PD_OK;
-    if (!d->hn) {
-        pd_set_error("split-precision denoiser: the engine was created for fewer than %d token rows (max_B x max_N); the mode "
-                     "applies to the streamed large-batch path only", PD_STREAM_MIN_ROWS);
-        return PD_ERR_UNSUPPORTED;
+    const bool f16 = mode == 2;
+    bool &ready = f16 ? d->split_h_ready : d->split_ready;
+    if (ready) return PD_OK;
+    PdPlaneExps e[PD_MAX_LAYERS] = {};
+    for (int l = 0; f16 && l < d->num_layers; ++l) {
+        PdLayerDev &L = d->layers[l];
+        bool finite = true;
+        PD_TRY(pd_plane_exponents(L.qkv_wf, L.qkv_b, L.out_wf, L.ff1_wf, L.ff1_b, L.ff2_wf, DM, DFF, &e[l], &finite));
+        // a checkpoint with inf / NaN has no static bound: the fp16-plane mode is refused (PD_ERR_INVALID_ARG) and the engine stays on
+        // the exact-fp32 kernels, which propagate the values like the reference does
+        if (!finite) {
+            d->non_finite = true;
+            pd_set_error("denoiser: encoder layer %d holds non-finite weights or biases: no static operand bound exists, the fp16-plane "
+                         "mode (PD_OPT_DENOISER_SPLIT = 2) is not available for these weights", l);
+            return PD_ERR_INVALID_ARG;
+        }
     }
-    auto split = [&](unsigned **dst, const float *Wf, int Nout, int K) -> int {
-        float *p = nullptr;
-        int rc = dev_alloc(d, &p, (size_t)Nout * K);
-        if (rc) return rc;
-        *dst = (unsigned *)p;
-        const size_t total = (size_t)(Nout / 32) * (K / 16) * 64;
-        hipLaunchKernelGGL(vit_frag_split_kernel, dim3(512), dim3(256), 0, 0, Wf, (const float *)nullptr, K, total, (uint4 *)p);   // gamma is already folded into Wf
-        PD_HIP_CHECK(hipGetLastError());
-        return PD_OK;
-    };
+    const int e_ln = 9;
     for (int l = 0; l < d->num_layers; ++l) {
         PdLayerDev &L = d->layers[l];
-        PD_TRY(split(&L.qkv_ws, L.qkv_wf, 3 * DM, DM));
-        PD_TRY(split(&L.out_ws, L.out_wf, DM, DM));
-        PD_TRY(split(&L.ff1_ws, L.ff1_wf, DFF, DM));
-        PD_TRY(split(&L.ff2_ws, L.ff2_wf, DM, DFF));
+        PD_TRY(d->mem.planes(f16 ? &L.qkv_wh : &L.qkv_ws, L.qkv_wf, 3 * DM, DM, nullptr, f16, e[l].qkv));
+        PD_TRY(d->mem.planes(f16 ? &L.out_wh : &L.out_ws, L.out_wf, DM, DM, nullptr, f16, e[l].out));
+        PD_TRY(d->mem.planes(f16 ? &L.ff1_wh : &L.ff1_ws, L.ff1_wf, DFF, DM, nullptr, f16, e[l].ff1));
+        PD_TRY(d->mem.planes(f16 ? &L.ff2_wh : &L.ff2_ws, L.ff2_wf, DM, DFF, nullptr, f16, e[l].ff2));
+        if (!f16) continue;
+        L.qkv_cs = ldexpf(1.0f, -(e_ln + e[l].qkv));
+        L.out_cs = ldexpf(1.0f, -(e[l].ctx + e[l].out));
+        L.ff1_cs = ldexpf(1.0f, -(e_ln + e[l].ff1));
+        L.ff2_cs = ldexpf(1.0f, -(e[l].hid + e[l].ff2));
+        L.ctx_scale = ldexpf(1.0f, e[l].ctx);
+        L.ff_scale = ldexpf(1.0f, e[l].hid);
     }
     PD_HIP_CHECK(hipDeviceSynchronize());
-    d->split_ready = true;
+    ready = true;
     return PD_OK;
 }
 
 void pd_denoiser_destroy(pd_engine *eng) {
     pd_denoiser_generic_destroy(eng);
-    if (!eng->den) return;
-    for (void *p : eng->den->allocs) (void)hipFree(p);
     delete eng->den;
     eng->den = nullptr;
 }

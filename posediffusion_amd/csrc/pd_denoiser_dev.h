@@ -1,7 +1,7 @@
 // pd_denoiser_dev.h -- shapes, device-side weight tables and small wave helpers shared by the
 // denoiser kernels (pd_denoiser.hip, pd_gemm_stream.h).
 #pragma once
-#include "pd_internal.h"
+#include "pd_weight_prep.h"
 
 #include <vector>
 
@@ -55,7 +55,6 @@ struct PdLayerDev {          // [0] = 32-wide-tile packing, [1] = 16-wide-tile p
     // pd_denoiser_build_split: accumulator scales 2^-(ea + ew) per GEMM, operand scales of the attention output and the FF hidden rows
     unsigned *qkv_wh, *out_wh, *ff1_wh, *ff2_wh;
     float qkv_cs, out_cs, ff1_cs, ff2_cs, ctx_scale, ff_scale;
-    int e_wqkv, e_wo, e_w1, e_w2;                  // the weights' scale exponents (pd_denoiser_build_scales)
 };
 
 struct PdDenoiserDev {
@@ -72,9 +71,8 @@ struct PdDenoiserDev {
     float *emb = nullptr, *first_df = nullptr, *first_zf = nullptr, *last0_wf = nullptr;   // streamed path: _first's step rows [rows, 192], row-major _first pieces / _last.0 weights
     bool split_ready = false;          // the fast mode's split weights exist
     bool split_h_ready = false;        // the fp16-plane mode's weights exist
-    bool scales_ready = false;         // the fp16-plane scales exist (pd_denoiser_build_scales)
-    bool non_finite = false;           // pd_denoiser_build_scales met inf / NaN in an encoder weight or bias: the ONLY failure pd_engine_create downgrades on
-    std::vector<void *> allocs;
+    bool non_finite = false;           // pd_denoiser_build_split met inf / NaN in an encoder weight or bias: the ONLY failure pd_engine_create downgrades on
+    PdDevAllocs mem{"pd_engine_create"};   // every buffer above
 };
 
 // 8-lane (one activation row) sum on the DPP network: xor-1, xor-2 quad permutes + half-row mirror

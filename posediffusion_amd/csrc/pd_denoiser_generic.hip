@@ -50,7 +50,7 @@ struct PdGenericDen {
     float *last0_w = nullptr, *last0_b = nullptr;   // [Hp, Dp], [Hp]
     float *last_ln_w = nullptr, *last_ln_b = nullptr, *last3_w = nullptr, *last3_b = nullptr;   // [hid], [hid], [9, hid], [9]
     float *emb = nullptr, *h = nullptr, *hn = nullptr, *qkv = nullptr, *ctx = nullptr, *ffa = nullptr, *hida = nullptr;
-    std::vector<void *> allocs;
+    PdDevAllocs mem{"pd_engine_create"};            // every buffer above, zero-filled
 };
 
 // --------------------------------------------------------------------------------------------
@@ -244,12 +244,6 @@ __global__ __launch_bounds__(256) void pd_gen_tail_kernel(PdGenTailArgs g) {
 // --------------------------------------------------------------------------------------------
 // host side
 // --------------------------------------------------------------------------------------------
-static int gen_alloc(PdGenericDen *G, float **p, size_t n_floats) {
-    PD_HIP_CHECK(hipMalloc((void **)p, n_floats * sizeof(float)));
-    G->allocs.push_back(*p);
-    PD_HIP_CHECK(hipMemset(*p, 0, n_floats * sizeof(float)));
-    return PD_OK;
-}
 // [sections x src_rows, K] -> [sections x dst_rows, Kp], zero padded (a bias: K = Kp = 1)
 static int gen_pad(PdGenericDen *G, float **dst, const float *W, int src_rows, int K, int dst_rows, int Kp, int sections = 1) {
     if (!W) {
@@ -257,17 +251,11 @@ static int gen_pad(PdGenericDen *G, float **dst, const float *W, int src_rows, i
         return PD_ERR_INVALID_ARG;
     }
     const size_t total = (size_t)sections * dst_rows * Kp;
-    int rc = gen_alloc(G, dst, total);
-    if (rc) return rc;
+    PD_TRY(G->mem.alloc(dst, total, true));
     hipLaunchKernelGGL(pd_gen_pad_kernel, dim3(512), dim3(256), 0, 0, W, src_rows, K, *dst, dst_rows, Kp, sections);
     PD_HIP_CHECK(hipGetLastError());
     return PD_OK;
 }
-#define PD_GEN_TRY(expr)     \
-    do {                     \
-        int _rc = (expr);    \
-        if (_rc) return _rc; \
-    } while (0)
 
 bool pd_denoiser_generic_shape_ok(const pd_weights *w, char *why, size_t why_len) {
     const int d = w->d_model, nh = w->nhead;
@@ -318,50 +306,48 @@ int pd_denoiser_generic_create(pd_engine *eng, const pd_weights *w) {
     }
     // the LDS of the attention kernel at the engine's frame capacity
     const size_t attn_lds = pd_gen_attn_lds(eng->max_N, G->hd);
-    PD_HIP_CHECK(hipFuncSetAttribute((const void *)pd_gen_attn_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)attn_lds));
+    PD_TRY(pd_set_lds(pd_gen_attn_kernel, attn_lds));
 
-    PD_GEN_TRY(gen_alloc(G, &G->t_table, (size_t)w->timesteps * 128));
-    PD_GEN_TRY(pd_time_table(w, G->t_table));
+    PD_TRY(G->mem.alloc(&G->t_table, (size_t)w->timesteps * 128, true));
+    PD_TRY(pd_time_table(w, G->t_table));
     const int d = G->d, Dp = G->Dp, Fp = G->Fp;
-    PD_GEN_TRY(gen_pad(G, &G->first_w, w->first_w, d, G->Kf, Dp, G->Kfp));
-    PD_GEN_TRY(gen_pad(G, &G->first_b, w->first_b, d, 1, Dp, 1));
+    PD_TRY(gen_pad(G, &G->first_w, w->first_w, d, G->Kf, Dp, G->Kfp));
+    PD_TRY(gen_pad(G, &G->first_b, w->first_b, d, 1, Dp, 1));
     for (int l = 0; l < G->layers; ++l) {
         const pd_layer_weights &s = w->layers[l];
         PdGenLayer &L = G->L[l];
-        PD_GEN_TRY(gen_pad(G, &L.norm1_w, s.norm1_w, d, 1, d, 1));
-        PD_GEN_TRY(gen_pad(G, &L.norm1_b, s.norm1_b, d, 1, d, 1));
-        PD_GEN_TRY(gen_pad(G, &L.norm2_w, s.norm2_w, d, 1, d, 1));
-        PD_GEN_TRY(gen_pad(G, &L.norm2_b, s.norm2_b, d, 1, d, 1));
-        PD_GEN_TRY(gen_pad(G, &L.qkv_w, s.in_proj_w, d, d, Dp, Dp, 3));     // q | k | v: three sections of d rows -> Dp rows
-        PD_GEN_TRY(gen_pad(G, &L.qkv_b, s.in_proj_b, d, 1, Dp, 1, 3));
-        PD_GEN_TRY(gen_pad(G, &L.out_w, s.out_proj_w, d, d, Dp, Dp));
-        PD_GEN_TRY(gen_pad(G, &L.out_b, s.out_proj_b, d, 1, Dp, 1));
-        PD_GEN_TRY(gen_pad(G, &L.ff1_w, s.linear1_w, G->ff, d, Fp, Dp));
-        PD_GEN_TRY(gen_pad(G, &L.ff1_b, s.linear1_b, G->ff, 1, Fp, 1));
-        PD_GEN_TRY(gen_pad(G, &L.ff2_w, s.linear2_w, d, G->ff, Dp, Fp));
-        PD_GEN_TRY(gen_pad(G, &L.ff2_b, s.linear2_b, d, 1, Dp, 1));
+        PD_TRY(gen_pad(G, &L.norm1_w, s.norm1_w, d, 1, d, 1));
+        PD_TRY(gen_pad(G, &L.norm1_b, s.norm1_b, d, 1, d, 1));
+        PD_TRY(gen_pad(G, &L.norm2_w, s.norm2_w, d, 1, d, 1));
+        PD_TRY(gen_pad(G, &L.norm2_b, s.norm2_b, d, 1, d, 1));
+        PD_TRY(gen_pad(G, &L.qkv_w, s.in_proj_w, d, d, Dp, Dp, 3));     // q | k | v: three sections of d rows -> Dp rows
+        PD_TRY(gen_pad(G, &L.qkv_b, s.in_proj_b, d, 1, Dp, 1, 3));
+        PD_TRY(gen_pad(G, &L.out_w, s.out_proj_w, d, d, Dp, Dp));
+        PD_TRY(gen_pad(G, &L.out_b, s.out_proj_b, d, 1, Dp, 1));
+        PD_TRY(gen_pad(G, &L.ff1_w, s.linear1_w, G->ff, d, Fp, Dp));
+        PD_TRY(gen_pad(G, &L.ff1_b, s.linear1_b, G->ff, 1, Fp, 1));
+        PD_TRY(gen_pad(G, &L.ff2_w, s.linear2_w, d, G->ff, Dp, Fp));
+        PD_TRY(gen_pad(G, &L.ff2_b, s.linear2_b, d, 1, Dp, 1));
     }
-    PD_GEN_TRY(gen_pad(G, &G->last0_w, w->last0_w, G->hid, d, G->Hp, Dp));
-    PD_GEN_TRY(gen_pad(G, &G->last0_b, w->last0_b, G->hid, 1, G->Hp, 1));
-    PD_GEN_TRY(gen_pad(G, &G->last_ln_w, w->last_ln_w, G->hid, 1, G->hid, 1));
-    PD_GEN_TRY(gen_pad(G, &G->last_ln_b, w->last_ln_b, G->hid, 1, G->hid, 1));
-    PD_GEN_TRY(gen_pad(G, &G->last3_w, w->last3_w, 9, G->hid, 9, G->hid));
-    PD_GEN_TRY(gen_pad(G, &G->last3_b, w->last3_b, 9, 1, 9, 1));
+    PD_TRY(gen_pad(G, &G->last0_w, w->last0_w, G->hid, d, G->Hp, Dp));
+    PD_TRY(gen_pad(G, &G->last0_b, w->last0_b, G->hid, 1, G->Hp, 1));
+    PD_TRY(gen_pad(G, &G->last_ln_w, w->last_ln_w, G->hid, 1, G->hid, 1));
+    PD_TRY(gen_pad(G, &G->last_ln_b, w->last_ln_b, G->hid, 1, G->hid, 1));
+    PD_TRY(gen_pad(G, &G->last3_w, w->last3_w, 9, G->hid, 9, G->hid));
+    PD_TRY(gen_pad(G, &G->last3_b, w->last3_b, 9, 1, 9, 1));
     const size_t rows = (size_t)G->m_cap;
-    PD_GEN_TRY(gen_alloc(G, &G->emb, rows * G->Kfp));
-    PD_GEN_TRY(gen_alloc(G, &G->h, rows * Dp));
-    PD_GEN_TRY(gen_alloc(G, &G->hn, rows * Dp));
-    PD_GEN_TRY(gen_alloc(G, &G->qkv, rows * 3 * Dp));
-    PD_GEN_TRY(gen_alloc(G, &G->ctx, rows * Dp));
-    PD_GEN_TRY(gen_alloc(G, &G->ffa, rows * Fp));
-    PD_GEN_TRY(gen_alloc(G, &G->hida, rows * G->Hp));
+    PD_TRY(G->mem.alloc(&G->emb, rows * G->Kfp, true));
+    PD_TRY(G->mem.alloc(&G->h, rows * Dp, true));
+    PD_TRY(G->mem.alloc(&G->hn, rows * Dp, true));
+    PD_TRY(G->mem.alloc(&G->qkv, rows * 3 * Dp, true));
+    PD_TRY(G->mem.alloc(&G->ctx, rows * Dp, true));
+    PD_TRY(G->mem.alloc(&G->ffa, rows * Fp, true));
+    PD_TRY(G->mem.alloc(&G->hida, rows * G->Hp, true));
     PD_HIP_CHECK(hipDeviceSynchronize());
     return PD_OK;
 }
 
 void pd_denoiser_generic_destroy(pd_engine *eng) {
-    if (!eng->gden) return;
-    for (void *p : eng->gden->allocs) (void)hipFree(p);
     delete eng->gden;
     eng->gden = nullptr;
 }

@@ -27,35 +27,8 @@ __device__ __forceinline__ float vit_gelu_fast(float v) {
     return v * (v >= 0.0f ? 1.0f - q : q);
 }
 
-// W[n][k] * gamma[k] -> split and packed in MFMA fragment order: [n / 32][k / 16][hi | lo][lane] x 16 B, lane = (n % 32) +
-// 32 * ((k / 8) % 2), 8 consecutive k per lane: one wave-wide 16-byte load is 1 KB contiguous
-// f16: fp16 halves of w * scale instead of bf16 halves of w
-static __global__ void vit_frag_split_kernel(const float *__restrict__ W, const float *__restrict__ gamma, int K, size_t total, uint4 *__restrict__ out,
-                                             int f16 = 0, float scale = 1.0f) {
-    const int KS = K / 16;
-    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
-        const int lane = (int)(idx & 63);
-        const size_t t = idx >> 6;
-        const int ks = (int)(t % KS), nt = (int)(t / KS);
-        const int n = nt * 32 + (lane & 31), k0 = ks * 16 + 8 * (lane >> 5);
-        unsigned w[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const float v = W[(size_t)n * K + k0 + e];
-            w[e] = f16 ? pd_split_word_h(v * scale) : pd_split_word(gamma ? v * gamma[k0 + e] : v);
-        }
-        uint4 hi, lo;
-        hi.x = __builtin_amdgcn_perm(w[1], w[0], 0x05040100u); lo.x = __builtin_amdgcn_perm(w[1], w[0], 0x07060302u);
-        hi.y = __builtin_amdgcn_perm(w[3], w[2], 0x05040100u); lo.y = __builtin_amdgcn_perm(w[3], w[2], 0x07060302u);
-        hi.z = __builtin_amdgcn_perm(w[5], w[4], 0x05040100u); lo.z = __builtin_amdgcn_perm(w[5], w[4], 0x07060302u);
-        hi.w = __builtin_amdgcn_perm(w[7], w[6], 0x05040100u); lo.w = __builtin_amdgcn_perm(w[7], w[6], 0x07060302u);
-        out[(t * 2) * 64 + lane] = hi;
-        out[(t * 2 + 1) * 64 + lane] = lo;
-    }
-}
-
 struct VitSplitArgs {
-    const unsigned *A, *W;      // A: split words [M][lda]; W: vit_frag_split_kernel's fragment order
+    const unsigned *A, *W;      // A: split words [M][lda]; W: pd_frag_split_kernel's fragment order (pd_weight_prep.hip)
     const float *bias;
     void *C;                    // EPI 0 / 2: fp32 [M][Nout]; EPI 3 (gelu) / 4 (relu): split words [M][Nout]
     int M, Nout, K, lda;

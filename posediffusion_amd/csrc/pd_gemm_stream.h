@@ -101,11 +101,6 @@ __global__ __launch_bounds__(256) void pd_ln_stats_kernel(const float *__restric
     for (int off = 32; off >= 1; off >>= 1) q += __shfl_xor(q, off, 64);
     if (lane == 0) stats[row] = make_float2(mean, 1.0f / sqrtf(q * (1.0f / D) + eps));
 }
-// W[n][k] * gamma[k] -> Wf (row-major copy with the LayerNorm scale folded in)
-static __global__ void pd_scale_cols_kernel(const float *__restrict__ W, const float *__restrict__ gamma, int K, size_t total, float *__restrict__ Wf) {
-    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x)
-        Wf[idx] = gamma ? W[idx] * gamma[idx % K] : W[idx];
-}
 
 //   C[m, n] = epi( sum_k A[m, k] W[n, k] + bias[n] ): a (64 WM) x (64 WN) tile per workgroup, one (32 WM) x (32 WN) quadrant
 //   per wave over the whole K; A and W (both row-major, k contiguous) stream through LDS in 32-deep chunks, double buffered

@@ -60,6 +60,13 @@ __device__ __forceinline__ float pd_relu(float v) { return v < 0.0f ? 0.0f : v; 
         }                                                                                      \
     } while (0)
 
+// return a nonzero status code at once
+#define PD_TRY(expr)         \
+    do {                     \
+        int _rc = (expr);    \
+        if (_rc) return _rc; \
+    } while (0)
+
 // ---- GGS match container (device view) ---------------------------------------------------------
 // Matches of one sequence, sorted by frame pair so that a wavefront owns one pair at a time
 // (geometry_guided_sampling.py:26-27 builds pair_idx = i*N + j; hloc already groups by pair).

@@ -31,7 +31,7 @@
 
 struct PdQkvAttnArgs {
     const unsigned *A;        // LayerNorm output as split words [M][DM] (pd_ln_rows_kernel<DM, 2>)
-    const unsigned *W;        // in_proj weights, fp16 planes in fragment order (vit_frag_split_kernel): [1536 / 32][DM / 16][hi | lo][lane] x 16 B
+    const unsigned *W;        // in_proj weights, fp16 planes in fragment order (pd_frag_split_kernel): [1536 / 32][DM / 16][hi | lo][lane] x 16 B
     const float *bias;        // [1536] (LayerNorm shift folded in)
     unsigned *ctx;            // [M][DM] split words of ctx * out_scale
     int B, N, G;              // sequences, frames per sequence, sequences per workgroup (G N < PD_QA_ROWS)

@@ -14,7 +14,7 @@
 // FC2 GEMM + residual (two 768-deep halves)] -> LayerNorm of the CLS rows, accumulated over the scales.
 // The GEMM is the denoiser's small-tile kernel shape (32 x 32 output tile, 4 waves split K, activation tile staged once in
 // LDS with the LayerNorm fused, weights pre-packed in MFMA fragment order) generalised to K = 384 / 768.
-#include "pd_internal.h"
+#include "pd_weight_prep.h"
 
 #include <math.h>
 #include <string.h>
@@ -41,7 +41,7 @@ struct pd_vit {
     struct Layer {
         float *qkv_wp, *qkv_b, *proj_wp, *proj_b, *fc1_wp, *fc1_b, *fc2a_wp, *fc2b_wp, *fc2_b;
         float *qkv_wf, *proj_wf, *fc1_wf, *fc2_wf;      // row-major copies (LayerNorm scale folded) for the streamed GEMM
-        unsigned *qkv_ws, *proj_ws, *fc1_ws, *fc2_ws;   // split into bf16 hi / lo, in MFMA fragment order (vit_frag_split_kernel)
+        unsigned *qkv_ws, *proj_ws, *fc1_ws, *fc2_ws;   // split into bf16 hi / lo, in MFMA fragment order (pd_frag_split_kernel)
         unsigned *qkv_wh, *proj_wh, *fc1_wh, *fc2_wh;   // fp16 hi / lo planes of w * 2^e (round 6: the denoiser's fp16-plane mode, pd_gemm_strip_kernel<.., F16>)
         float qkv_cs, proj_cs, fc1_cs, fc2_cs;          // accumulator scales 2^-(e_operand + e_weight)
         float ctx_scale, hid_scale;                     // 2^e of the attention output / the GELU hidden rows (split-word operands of proj / fc2)
@@ -50,33 +50,10 @@ struct pd_vit {
     // workspaces, sized at the first forward / grown on demand
     size_t cap_tokens = 0, cap_pixels = 0;
     float *x = nullptr, *xn = nullptr, *qkv = nullptr, *ctx = nullptr, *hid = nullptr, *img = nullptr;
-    std::vector<void *> allocs;
+    PdDevAllocs mem{"pd_vit_create"};            // every buffer above
 };
 
 // ---- small kernels -----------------------------------------------------------------------------------
-// W[Nout][K] (row stride ldw, column offset koff) -> fragment order for v_mfma_f32_32x32x2_f32, optional per-column scale
-__global__ void vit_repack_kernel(const float *__restrict__ W, int Nout, int K, int ldw, int koff, float *__restrict__ Wp, size_t total,
-                                  const float *__restrict__ colscale) {
-    const int KC = K / 8;
-    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
-        const int e = idx & 3, l = (idx >> 2) & 63;
-        const size_t rest = idx >> 8;
-        const int kc = (int)(rest % KC), nt = (int)(rest / KC);
-        const int n = nt * 32 + (l & 31), k = kc * 8 + 4 * (l >> 5) + e;
-        float v = (n < Nout) ? W[(size_t)n * ldw + koff + k] : 0.0f;
-        if (colscale) v *= colscale[k];
-        Wp[idx] = v;
-    }
-}
-// b'[n] = b[n] + sum_k W[n][k] beta[k]
-__global__ void vit_fold_bias_kernel(const float *__restrict__ W, const float *__restrict__ beta, const float *__restrict__ b, int Nout,
-                                     int K, float *__restrict__ out) {
-    const int n = blockIdx.x * blockDim.x + threadIdx.x;
-    if (n >= Nout) return;
-    float a = 0.0f;
-    for (int k = 0; k < K; ++k) a = fmaf(W[(size_t)n * K + k], beta[k], a);
-    out[n] = b[n] + a;
-}
 
 // (image - mean) / std (image_feature_extractor.py:62-63), then F.interpolate(scale_factor, bilinear, align_corners=False)
 // (:86-87): source index (dst + 0.5) / scale_factor - 0.5 clamped at 0.  [n,3,H,W] -> [n,3,Hs,Ws]
@@ -509,156 +486,83 @@ static size_t vit_attn_lds(int T) {
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------
-#define VIT_TRY(expr)        \
-    do {                     \
-        int _rc = (expr);    \
-        if (_rc) return _rc; \
-    } while (0)
-
-static int vit_alloc(pd_vit *v, float **p, size_t n) {
-    PD_HIP_CHECK(hipMalloc((void **)p, n * sizeof(float)));
-    v->allocs.push_back(*p);
-    return PD_OK;
-}
-static int vit_copy(pd_vit *v, float **dst, const float *src, size_t n) {
-    if (!src) {
-        pd_set_error("pd_vit_create: a weight pointer is NULL");
-        return PD_ERR_INVALID_ARG;
-    }
-    VIT_TRY(vit_alloc(v, dst, n));
-    PD_HIP_CHECK(hipMemcpy(*dst, src, n * sizeof(float), hipMemcpyDeviceToDevice));
-    return PD_OK;
-}
-static int vit_pack(pd_vit *v, float **dst, const float *W, int Nout, int K, int ldw, int koff, const float *gamma) {
-    if (!W) {
-        pd_set_error("pd_vit_create: a weight pointer is NULL");
-        return PD_ERR_INVALID_ARG;
-    }
-    const size_t total = (size_t)(Nout / 32) * (K / 8) * 256;
-    VIT_TRY(vit_alloc(v, dst, total));
-    hipLaunchKernelGGL(vit_repack_kernel, dim3(512), dim3(256), 0, 0, W, Nout, K, ldw, koff, *dst, total, gamma);
-    PD_HIP_CHECK(hipGetLastError());
-    return PD_OK;
-}
-static int vit_fold(pd_vit *v, float **dst, const float *W, const float *beta, const float *b, int Nout, int K) {
-    if (!W || !beta || !b) {
-        pd_set_error("pd_vit_create: a weight pointer is NULL");
-        return PD_ERR_INVALID_ARG;
-    }
-    VIT_TRY(vit_alloc(v, dst, Nout));
-    hipLaunchKernelGGL(vit_fold_bias_kernel, dim3((Nout + 127) / 128), dim3(128), 0, 0, W, beta, b, Nout, K, *dst);
-    PD_HIP_CHECK(hipGetLastError());
-    return PD_OK;
-}
-
-static int vit_rowmajor(pd_vit *v, float **dst, const float *W, int Nout, int K, const float *gamma) {
-    const size_t total = (size_t)Nout * K;
-    VIT_TRY(vit_alloc(v, dst, total));
-    hipLaunchKernelGGL(pd_scale_cols_kernel, dim3(512), dim3(256), 0, 0, W, gamma, K, total, *dst);
-    PD_HIP_CHECK(hipGetLastError());
-    return PD_OK;
-}
-
-static int vit_grouped(pd_vit *v, unsigned **dst, const float *W, int Nout, int K, const float *gamma) {
-    const size_t total = (size_t)(Nout / 32) * (K / 16) * 64;        // one thread per (32-column tile, 16-k step, lane)
-    float *p = nullptr;
-    VIT_TRY(vit_alloc(v, &p, (size_t)Nout * K));
-    *dst = (unsigned *)p;
-    hipLaunchKernelGGL(vit_frag_split_kernel, dim3(512), dim3(256), 0, 0, W, gamma, K, total, (uint4 *)p);
-    PD_HIP_CHECK(hipGetLastError());
-    return PD_OK;
-}
-
-template <typename KernelT>
-static int vit_set_lds(KernelT kern, size_t bytes) {
-    PD_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    return PD_OK;
-}
-
 extern "C" void pd_vit_destroy(pd_vit *v) {
     if (!v) return;
     (void)hipSetDevice(v->device);
     (void)hipDeviceSynchronize();
-    for (void *p : v->allocs) (void)hipFree(p);
     delete v;
 }
 
-// The fp16-plane mode of the four Linear layers (round 6; the denoiser's pd_denoiser_build_scales, for dim 384): fp16 keeps 11 bits and five
-// exponent bits, so every operand gets a POWER-OF-TWO scale (exact to apply and to undo) fixed here from bounds that hold for every input:
-//   * LayerNorm output without affine: sum of squares <= D, so |x^| <= sqrt(384) = 19.6;                       scale 2^floor(log2(32768 / 19.6)) = 2^10
-//   * a Linear fed by it: |x^ . w + b| <= sqrt(D) ||w||_2 + |b| (Cauchy-Schwarz) -- the V rows the attention averages (a convex combination:
-//     same bound) and the FC1 rows, of which GELU keeps |gelu(v)| <= |v|;                                          scale 2^floor(log2(32768 / bound))
-//   * weights (LayerNorm gamma folded): 2^floor(log2(16384 / max |w|)).
-// Nothing can overflow (fp16 max 65 504); hi + lo keeps 22 bits.  Non-finite weights have no bound: h_ready stays false and the engine
-// runs the exact-fp32 kernels (which propagate inf / NaN like the reference).
-static int vit_floor_log2_ratio(double cap, double v) {
-    if (!(v > 0.0)) return 0;
-    double e = floor(log2(cap / v));
-    e = e < -60.0 ? -60.0 : (e > 60.0 ? 60.0 : e);
-    return (int)e;
-}
+// The fp16-plane mode of the four Linear layers (round 6): static power-of-two scales from pd_plane_exponents, 2^10 for the LayerNorm
+// operand (|x^| <= sqrt(384) = 19.6).  Non-finite weights have no bound: h_ready stays false and the engine runs the exact-fp32 kernels.
 static int vit_build_planes_h(pd_vit *v) {
-    std::vector<float> w, b;
-    bool finite = true;
-    auto fetch = [&](const float *Wf, const float *bias, int Nout, int K) -> int {
-        w.resize((size_t)Nout * K);
-        b.resize(Nout);
-        PD_HIP_CHECK(hipMemcpy(w.data(), Wf, w.size() * sizeof(float), hipMemcpyDeviceToHost));
-        PD_HIP_CHECK(hipMemcpy(b.data(), bias, b.size() * sizeof(float), hipMemcpyDeviceToHost));
-        return PD_OK;
-    };
-    auto max_abs = [&]() { double m = 0; for (float x : w) { finite = finite && isfinite(x); m = fmax(m, fabs((double)x)); } return m; };
-    auto row_bound = [&](int r0, int r1, int K) {            // max over rows of sqrt(D) ||w_r||_2 + |b_r|
-        double bound = 0;
-        for (int r = r0; r < r1; ++r) {
-            double q = 0;
-            for (int k = 0; k < K; ++k) q += (double)w[(size_t)r * K + k] * w[(size_t)r * K + k];
-            bound = fmax(bound, sqrt((double)VD) * sqrt(q) + fabs((double)b[r]));
-            finite = finite && isfinite(q) && isfinite(b[r]);
-        }
-        return bound;
-    };
-    auto planes = [&](unsigned **dst, const float *Wf, int Nout, int K, int ew) -> int {
-        float *p = nullptr;
-        VIT_TRY(vit_alloc(v, &p, (size_t)Nout * K));
-        *dst = (unsigned *)p;
-        const size_t total = (size_t)(Nout / 32) * (K / 16) * 64;
-        hipLaunchKernelGGL(vit_frag_split_kernel, dim3(512), dim3(256), 0, 0, Wf, (const float *)nullptr, K, total, (uint4 *)p, 1, ldexpf(1.0f, ew));   // gamma is in Wf
-        PD_HIP_CHECK(hipGetLastError());
-        return PD_OK;
-    };
-    PD_HIP_CHECK(hipDeviceSynchronize());
-    const int e_ln = vit_floor_log2_ratio(32768.0, sqrt((double)VD));
-    struct E { int qkv, proj, fc1, fc2, ctx, hid; } e[VDEPTH_MAX];
+    const int e_ln = pd_floor_log2_ratio(32768.0, sqrt((double)VD));
+    PdPlaneExps e[VDEPTH_MAX];
     for (int l = 0; l < v->depth; ++l) {
         pd_vit::Layer &L = v->L[l];
-        VIT_TRY(fetch(L.qkv_wf, L.qkv_b, 3 * VD, VD));
-        e[l].ctx = vit_floor_log2_ratio(32768.0, row_bound(2 * VD, 3 * VD, VD));
-        e[l].qkv = vit_floor_log2_ratio(16384.0, max_abs());
-        VIT_TRY(fetch(L.proj_wf, L.proj_b, VD, VD));
-        e[l].proj = vit_floor_log2_ratio(16384.0, max_abs());
-        VIT_TRY(fetch(L.fc1_wf, L.fc1_b, VFF, VD));
-        e[l].hid = vit_floor_log2_ratio(32768.0, row_bound(0, VFF, VD));
-        e[l].fc1 = vit_floor_log2_ratio(16384.0, max_abs());
-        VIT_TRY(fetch(L.fc2_wf, L.fc2_b, VD, VFF));
-        e[l].fc2 = vit_floor_log2_ratio(16384.0, max_abs());
+        bool finite = true;
+        PD_TRY(pd_plane_exponents(L.qkv_wf, L.qkv_b, L.proj_wf, L.fc1_wf, L.fc1_b, L.fc2_wf, VD, VFF, &e[l], &finite));
         if (!finite) return PD_OK;                 // (not an error: the exact-fp32 kernels take such a network)
     }
     for (int l = 0; l < v->depth; ++l) {
         pd_vit::Layer &L = v->L[l];
-        VIT_TRY(planes(&L.qkv_wh, L.qkv_wf, 3 * VD, VD, e[l].qkv));
-        VIT_TRY(planes(&L.proj_wh, L.proj_wf, VD, VD, e[l].proj));
-        VIT_TRY(planes(&L.fc1_wh, L.fc1_wf, VFF, VD, e[l].fc1));
-        VIT_TRY(planes(&L.fc2_wh, L.fc2_wf, VD, VFF, e[l].fc2));
+        PD_TRY(v->mem.planes(&L.qkv_wh, L.qkv_wf, 3 * VD, VD, nullptr, true, e[l].qkv));   // gamma is in the row-major copies
+        PD_TRY(v->mem.planes(&L.proj_wh, L.proj_wf, VD, VD, nullptr, true, e[l].out));
+        PD_TRY(v->mem.planes(&L.fc1_wh, L.fc1_wf, VFF, VD, nullptr, true, e[l].ff1));
+        PD_TRY(v->mem.planes(&L.fc2_wh, L.fc2_wf, VD, VFF, nullptr, true, e[l].ff2));
         L.qkv_cs = ldexpf(1.0f, -(e_ln + e[l].qkv));
-        L.proj_cs = ldexpf(1.0f, -(e[l].ctx + e[l].proj));
-        L.fc1_cs = ldexpf(1.0f, -(e_ln + e[l].fc1));
-        L.fc2_cs = ldexpf(1.0f, -(e[l].hid + e[l].fc2));
+        L.proj_cs = ldexpf(1.0f, -(e[l].ctx + e[l].out));
+        L.fc1_cs = ldexpf(1.0f, -(e_ln + e[l].ff1));
+        L.fc2_cs = ldexpf(1.0f, -(e[l].hid + e[l].ff2));
         L.ctx_scale = ldexpf(1.0f, e[l].ctx);
         L.hid_scale = ldexpf(1.0f, e[l].hid);
     }
     v->ln_scale = ldexpf(1.0f, e_ln);
     v->h_ready = true;
+    return PD_OK;
+}
+
+static int vit_create(pd_vit *v, const pd_vit_weights *w) {
+    PdDevAllocs &m = v->mem;
+    PD_TRY(m.pack(&v->patch_wp, w->patch_w, VD, VKP, VKP, 32, nullptr));
+    PD_TRY(m.copy(&v->patch_b, w->patch_b, VD));
+    PD_TRY(m.copy(&v->cls, w->cls_token, VD));
+    PD_TRY(m.copy(&v->pos, w->pos_embed, (size_t)(1 + w->pos_grid * w->pos_grid) * VD));
+    PD_TRY(m.copy(&v->norm_w, w->norm_w, VD));
+    PD_TRY(m.copy(&v->norm_b, w->norm_b, VD));
+    PD_TRY(m.alloc(&v->zero_b, VD, true));
+    for (int l = 0; l < w->depth; ++l) {
+        const pd_vit_layer_weights &s = w->layers[l];
+        pd_vit::Layer &L = v->L[l];
+        // LayerNorm affine folded: W' = W diag(gamma), b' = b + W beta
+        PD_TRY(m.pack(&L.qkv_wp, s.qkv_w, 3 * VD, VD, VD, 32, s.norm1_w));
+        PD_TRY(m.fold_bias(&L.qkv_b, s.qkv_w, s.norm1_b, s.qkv_b, 3 * VD, VD));
+        PD_TRY(m.pack(&L.proj_wp, s.proj_w, VD, VD, VD, 32, nullptr));
+        PD_TRY(m.copy(&L.proj_b, s.proj_b, VD));
+        PD_TRY(m.pack(&L.fc1_wp, s.fc1_w, VFF, VD, VD, 32, s.norm2_w));
+        PD_TRY(m.fold_bias(&L.fc1_b, s.fc1_w, s.norm2_b, s.fc1_b, VFF, VD));
+        PD_TRY(m.pack(&L.fc2a_wp, s.fc2_w, VD, VKP, VKP, 32, nullptr, 0, VFF, 0));     // K columns [0, 768)
+        PD_TRY(m.pack(&L.fc2b_wp, s.fc2_w, VD, VKP, VKP, 32, nullptr, 0, VFF, VKP));   // K columns [768, 1536)
+        PD_TRY(m.copy(&L.fc2_b, s.fc2_b, VD));
+        PD_TRY(m.rowmajor(&L.qkv_wf, s.qkv_w, 3 * VD, VD, s.norm1_w));
+        PD_TRY(m.rowmajor(&L.proj_wf, s.proj_w, VD, VD, nullptr));
+        PD_TRY(m.rowmajor(&L.fc1_wf, s.fc1_w, VFF, VD, s.norm2_w));
+        PD_TRY(m.rowmajor(&L.fc2_wf, s.fc2_w, VD, VFF, nullptr));
+        PD_TRY(m.planes(&L.qkv_ws, s.qkv_w, 3 * VD, VD, s.norm1_w));
+        PD_TRY(m.planes(&L.proj_ws, s.proj_w, VD, VD, nullptr));
+        PD_TRY(m.planes(&L.fc1_ws, s.fc1_w, VFF, VD, s.norm2_w));
+        PD_TRY(m.planes(&L.fc2_ws, s.fc2_w, VD, VFF, nullptr));
+    }
+    PD_TRY(pd_set_lds(vit_gemm_kernel<VKP, 3, 4>, 32 * (VKP + 4) * 4));
+    PD_TRY(pd_set_lds(vit_gemm_kernel<VD, 1, 0>, 32 * (VD + 4) * 4));
+    PD_TRY(pd_set_lds(vit_gemm_kernel<VD, 0, 2>, 32 * (VD + 4) * 4));
+    PD_TRY(pd_set_lds(vit_gemm_kernel<VD, 1, 3>, 32 * (VD + 4) * 4));
+    PD_TRY(pd_set_lds(vit_gemm_kernel<VKP, 0, 2>, 32 * (VKP + 4) * 4));
+    PD_TRY(pd_set_lds(vit_attn_kernel<0>, vit_attn_lds(VT_MAX)));
+    PD_TRY(pd_set_lds(vit_attn_kernel<1>, vit_attn_lds(VT_MAX)));
+    PD_TRY(pd_set_lds(vit_attn_kernel<2>, vit_attn_lds(VT_MAX)));
+    PD_TRY(vit_build_planes_h(v));
+    PD_HIP_CHECK(hipDeviceSynchronize());
     return PD_OK;
 }
 
@@ -678,53 +582,7 @@ extern "C" int pd_vit_create(const pd_vit_weights *w, pd_vit **out) {
     PD_HIP_CHECK(hipGetDevice(&v->device));
     v->depth = w->depth;
     v->grid0 = w->pos_grid;
-    int rc = PD_OK;
-    do {
-        if ((rc = vit_pack(v, &v->patch_wp, w->patch_w, VD, VKP, VKP, 0, nullptr))) break;
-        if ((rc = vit_copy(v, &v->patch_b, w->patch_b, VD))) break;
-        if ((rc = vit_copy(v, &v->cls, w->cls_token, VD))) break;
-        if ((rc = vit_copy(v, &v->pos, w->pos_embed, (size_t)(1 + w->pos_grid * w->pos_grid) * VD))) break;
-        if ((rc = vit_copy(v, &v->norm_w, w->norm_w, VD))) break;
-        if ((rc = vit_copy(v, &v->norm_b, w->norm_b, VD))) break;
-        if ((rc = vit_alloc(v, &v->zero_b, VD))) break;
-        if (hipMemset(v->zero_b, 0, VD * sizeof(float)) != hipSuccess) {
-            rc = PD_ERR_HIP;
-            break;
-        }
-        for (int l = 0; l < w->depth && !rc; ++l) {
-            const pd_vit_layer_weights &s = w->layers[l];
-            pd_vit::Layer &L = v->L[l];
-            // LayerNorm affine folded: W' = W diag(gamma), b' = b + W beta
-            if ((rc = vit_pack(v, &L.qkv_wp, s.qkv_w, 3 * VD, VD, VD, 0, s.norm1_w))) break;
-            if ((rc = vit_fold(v, &L.qkv_b, s.qkv_w, s.norm1_b, s.qkv_b, 3 * VD, VD))) break;
-            if ((rc = vit_pack(v, &L.proj_wp, s.proj_w, VD, VD, VD, 0, nullptr))) break;
-            if ((rc = vit_copy(v, &L.proj_b, s.proj_b, VD))) break;
-            if ((rc = vit_pack(v, &L.fc1_wp, s.fc1_w, VFF, VD, VD, 0, s.norm2_w))) break;
-            if ((rc = vit_fold(v, &L.fc1_b, s.fc1_w, s.norm2_b, s.fc1_b, VFF, VD))) break;
-            if ((rc = vit_pack(v, &L.fc2a_wp, s.fc2_w, VD, VKP, VFF, 0, nullptr))) break;     // K columns [0, 768)
-            if ((rc = vit_pack(v, &L.fc2b_wp, s.fc2_w, VD, VKP, VFF, VKP, nullptr))) break;   // K columns [768, 1536)
-            if ((rc = vit_copy(v, &L.fc2_b, s.fc2_b, VD))) break;
-            if ((rc = vit_rowmajor(v, &L.qkv_wf, s.qkv_w, 3 * VD, VD, s.norm1_w))) break;
-            if ((rc = vit_rowmajor(v, &L.proj_wf, s.proj_w, VD, VD, nullptr))) break;
-            if ((rc = vit_rowmajor(v, &L.fc1_wf, s.fc1_w, VFF, VD, s.norm2_w))) break;
-            if ((rc = vit_rowmajor(v, &L.fc2_wf, s.fc2_w, VD, VFF, nullptr))) break;
-            if ((rc = vit_grouped(v, &L.qkv_ws, s.qkv_w, 3 * VD, VD, s.norm1_w))) break;
-            if ((rc = vit_grouped(v, &L.proj_ws, s.proj_w, VD, VD, nullptr))) break;
-            if ((rc = vit_grouped(v, &L.fc1_ws, s.fc1_w, VFF, VD, s.norm2_w))) break;
-            if ((rc = vit_grouped(v, &L.fc2_ws, s.fc2_w, VD, VFF, nullptr))) break;
-        }
-        if (rc) break;
-        if ((rc = vit_set_lds(vit_gemm_kernel<VKP, 3, 4>, 32 * (VKP + 4) * 4))) break;
-        if ((rc = vit_set_lds(vit_gemm_kernel<VD, 1, 0>, 32 * (VD + 4) * 4))) break;
-        if ((rc = vit_set_lds(vit_gemm_kernel<VD, 0, 2>, 32 * (VD + 4) * 4))) break;
-        if ((rc = vit_set_lds(vit_gemm_kernel<VD, 1, 3>, 32 * (VD + 4) * 4))) break;
-        if ((rc = vit_set_lds(vit_gemm_kernel<VKP, 0, 2>, 32 * (VKP + 4) * 4))) break;
-        if ((rc = vit_set_lds(vit_attn_kernel<0>, vit_attn_lds(VT_MAX)))) break;
-        if ((rc = vit_set_lds(vit_attn_kernel<1>, vit_attn_lds(VT_MAX)))) break;
-        if ((rc = vit_set_lds(vit_attn_kernel<2>, vit_attn_lds(VT_MAX)))) break;
-        if ((rc = vit_build_planes_h(v))) break;
-        if (hipDeviceSynchronize() != hipSuccess) rc = PD_ERR_HIP;
-    } while (0);
+    const int rc = vit_create(v, w);
     if (rc) {
         pd_vit_destroy(v);
         return rc;
@@ -735,25 +593,21 @@ extern "C" int pd_vit_create(const pd_vit_weights *w, pd_vit **out) {
 
 static int vit_reserve(pd_vit *v, size_t tokens, size_t pixels) {
     auto grow = [&](float **p, size_t n) -> int {
-        if (*p) {
-            (void)hipFree(*p);
-            for (auto &q : v->allocs)
-                if (q == *p) q = nullptr;
-        }
-        return vit_alloc(v, p, n);
+        v->mem.release(*p);
+        return v->mem.alloc(p, n);
     };
     if (tokens > v->cap_tokens) {
         PD_HIP_CHECK(hipDeviceSynchronize());
-        VIT_TRY(grow(&v->x, tokens * VD));
-        VIT_TRY(grow(&v->xn, tokens * VD));
-        VIT_TRY(grow(&v->qkv, tokens * 3 * VD));
-        VIT_TRY(grow(&v->ctx, tokens * VD));
-        VIT_TRY(grow(&v->hid, tokens * VFF));
+        PD_TRY(grow(&v->x, tokens * VD));
+        PD_TRY(grow(&v->xn, tokens * VD));
+        PD_TRY(grow(&v->qkv, tokens * 3 * VD));
+        PD_TRY(grow(&v->ctx, tokens * VD));
+        PD_TRY(grow(&v->hid, tokens * VFF));
         v->cap_tokens = tokens;
     }
     if (pixels > v->cap_pixels) {
         PD_HIP_CHECK(hipDeviceSynchronize());
-        VIT_TRY(grow(&v->img, pixels));
+        PD_TRY(grow(&v->img, pixels));
         v->cap_pixels = pixels;
     }
     return PD_OK;
@@ -799,7 +653,7 @@ extern "C" int pd_vit_forward_scale(pd_vit *v, const float *images, int n_img, i
     }
     hipStream_t s = (hipStream_t)stream;
     const size_t tokens = (size_t)n_img * T;
-    VIT_TRY(vit_reserve(v, tokens, (size_t)n_img * 3 * Hs * Ws));
+    PD_TRY(vit_reserve(v, tokens, (size_t)n_img * 3 * Hs * Ws));
     const float *pos = native && !pos_scaled ? v->pos : pos_scaled;
     {
         const size_t total = (size_t)n_img * 3 * Hs * Ws;

@@ -104,7 +104,7 @@ def _adversarial_state(diff, kind):
 @pytest.mark.parametrize("kind", ["outlier_weight_per_row", "bias_30x_activation", "one_hot_layernorm_rows", "tiny_relu_outputs"])
 def test_fp16_plane_mode_under_adversarial_operands(seeded_diffuser, kind):
     """PD_OPT_DENOISER_SPLIT = 2 (the default at >= 1 024 token rows) rests on static power-of-two operand scales derived from bounds
-    (pd_denoiser_build_scales): here the bounds are loose or the values sit far below them.  One step against the fp64 oracle at three
+    (pd_plane_exponents): here the bounds are loose or the values sit far below them.  One step against the fp64 oracle at three
     timesteps, error within 2 x the exact-fp32 mode's (floor 2e-6), nothing non-finite."""
     dev = torch.device(DEV)
     diff = seeded_diffuser.to(dev)
