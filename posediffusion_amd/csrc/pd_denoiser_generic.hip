@@ -178,6 +178,7 @@ __global__ __launch_bounds__(PD_GEN_ATTN_THREADS) void pd_gen_attn_kernel(const 
     }
 }
 static size_t pd_gen_attn_lds(int N, int hd) { return (size_t)2 * N * (hd + 4) * sizeof(float); }
+#define PD_GEN_MAX_HD 256           // the family's head-dim bound (pd_denoiser_generic_shape_ok)
 
 // --------------------------------------------------------------------------------------------
 // tail: LayerNorm(hidden) -> ReLU -> Linear(hidden, 9) (_last.1 .. 3) fused with predict_start_from_noise / q_posterior / the sample
@@ -304,9 +305,10 @@ int pd_denoiser_generic_create(pd_engine *eng, const pd_weights *w) {
                      "per-array limit", G->m_cap, widest);
         return PD_ERR_UNSUPPORTED;
     }
-    // the LDS of the attention kernel at the engine's frame capacity
-    const size_t attn_lds = pd_gen_attn_lds(eng->max_N, G->hd);
-    PD_TRY(pd_set_lds(pd_gen_attn_kernel, attn_lds));
+    // the attention kernel's dynamic-LDS limit is a per-process attribute of the kernel, shared by every engine: it is set to the family's
+    // bound (N = 64 frames, head dim 256: 133 120 bytes), never from this engine's shape, so a later engine cannot lower it below what an
+    // earlier one launches with
+    PD_TRY(pd_set_lds(pd_gen_attn_kernel, pd_gen_attn_lds(PD_MAX_FRAMES, PD_GEN_MAX_HD)));
 
     PD_TRY(G->mem.alloc(&G->t_table, (size_t)w->timesteps * 128, true));
     PD_TRY(pd_time_table(w, G->t_table));
@@ -377,6 +379,7 @@ int pd_denoiser_generic_launch(pd_engine *eng, const float *x, const float *z, i
             hipLaunchKernelGGL(pd_gen_ln_kernel, dim3(rows_blocks), dim3(256), 0, s, G->h, G->hn, L.norm1_w, L.norm1_b, M, G->d, Dp);
             pd_gemm_dma<0>(G->hn, Dp, L.qkv_w, Dp, L.qkv_b, G->qkv, M, 3 * Dp, s);
             hipLaunchKernelGGL(pd_gen_attn_kernel, dim3(B * G->nhead), dim3(PD_GEN_ATTN_THREADS), attn_lds, s, G->qkv, G->ctx, N, G->nhead, G->hd, Dp, scale);
+            PD_HIP_CHECK(hipGetLastError());      // the one launch whose dynamic LDS depends on the call's shape: its status, not a later one's
             pd_gemm_dma<2>(G->ctx, Dp, L.out_w, Dp, L.out_b, G->h, M, Dp, s);
             hipLaunchKernelGGL(pd_gen_ln_kernel, dim3(rows_blocks), dim3(256), 0, s, G->h, G->hn, L.norm2_w, L.norm2_b, M, G->d, Dp);
             pd_gemm_dma<1>(G->hn, Dp, L.ff1_w, Dp, L.ff1_b, G->ffa, M, Fp, s);
@@ -385,6 +388,7 @@ int pd_denoiser_generic_launch(pd_engine *eng, const float *x, const float *z, i
             // h = LN1(h + out_proj(attn(h)));  h = LN2(h + W2 relu(W1 h))
             pd_gemm_dma<0>(G->h, Dp, L.qkv_w, Dp, L.qkv_b, G->qkv, M, 3 * Dp, s);
             hipLaunchKernelGGL(pd_gen_attn_kernel, dim3(B * G->nhead), dim3(PD_GEN_ATTN_THREADS), attn_lds, s, G->qkv, G->ctx, N, G->nhead, G->hd, Dp, scale);
+            PD_HIP_CHECK(hipGetLastError());
             pd_gemm_dma<2>(G->ctx, Dp, L.out_w, Dp, L.out_b, G->h, M, Dp, s);
             hipLaunchKernelGGL(pd_gen_ln_kernel, dim3(rows_blocks), dim3(256), 0, s, G->h, G->h, L.norm1_w, L.norm1_b, M, G->d, Dp);
             pd_gemm_dma<1>(G->h, Dp, L.ff1_w, Dp, L.ff1_b, G->ffa, M, Fp, s);

@@ -1,6 +1,6 @@
 """Non-default Denoiser configurations (the shape-generic denoiser path, posediffusion_amd/csrc/pd_denoiser_generic.hip): the seed
 protocol that builds their weights through the drop-in modules, and the fp64 forward the GPU tests compare against.  Shared by
-tests/test_denoiser_cfgs_cpu.py, tests/test_gpu_denoiser_cfgs.py and tools/make_denoiser_cfg_golden.py."""
+tests/test_denoiser_cfgs_cpu.py, tests/test_gpu_denoiser_cfgs.py, tests/test_gpu_denoiser_ranges.py and tools/make_denoiser_cfg_golden.py."""
 from __future__ import annotations
 
 import copy
@@ -41,6 +41,23 @@ CONFIGS = [
     Cfg(384, 6, 2048, 2, 2048, 64, True, False),
     Cfg(96, 3, 160, 1, 10, 20, False, False),
 ]
+# the limits of the family and its padding boundaries (tests/test_gpu_denoiser_ranges.py): one or two axes at an edge, the rest small so
+# that the fp64 forward stays cheap.  Kf = 317 + z + pivot is _first's width (padded to a multiple of 32), Dp / Fp / Hp are d / ff /
+# hidden padded to a multiple of 64, head dim = d / heads (pd_gen_attn_kernel: output dims lane + 64 cc, cc = 0..3)
+EDGE_CFGS = [
+    Cfg(32, 4, 64, 2, 16, 32, True, True),           # smallest d (Dp = 64: 32 padding columns), head dim 8
+    Cfg(96, 8, 96, 2, 35, 24, False, True),          # head dim 12; Kf = 353 = 11 x 32 + 1
+    Cfg(160, 8, 65, 1, 34, 65, True, True),          # head dim 20; ff and hidden 65 (one past 64); Kf = 352 exactly
+    Cfg(544, 8, 128, 1, 8, 64, True, False),         # head dim 68 (output slot 1 partly used); Dp = 576
+    Cfg(256, 1, 256, 2, 64, 128, False, True),       # head dim 256 (all four output slots), one head
+    Cfg(2016, 8, 64, 1, 32, 64, True, True),         # head dim 252; Dp = 2048
+    Cfg(2048, 16, 64, 1, 16, 32, True, False),       # largest d
+    Cfg(64, 2, 8192, 1, 16, 32, True, True),         # largest ff
+    Cfg(64, 4, 1, 2, 1, 1, False, True),             # smallest ff, z and hidden (the tail's LayerNorm output is its beta)
+    Cfg(64, 4, 1, 2, 1, 20, False, True),            # smallest ff and z again, visible: at hidden 1 the output does not depend on them
+    Cfg(64, 4, 128, 1, 4096, 1024, True, True),      # largest z and hidden (all 16 hidden slots of pd_gen_tail_kernel)
+    Cfg(64, 8, 128, 16, 32, 64, True, False),        # 16 layers (PD_MAX_LAYERS), head dim 8
+]
 # the configurations of tests/golden/denoiser_cfgs.npz (outputs of the reference's own models/denoiser.py)
 GOLDEN_CFGS = [
     Cfg(96, 3, 160, 1, 10, 20, False, False),
@@ -75,12 +92,22 @@ def weight_checksum(sd: Dict[str, torch.Tensor], layers: int) -> np.ndarray:
     return np.array([float(sd[k].double().abs().sum()) for k in keys])
 
 
+def fp64_copy(den: torch.nn.Module) -> torch.nn.Module:
+    """A float64 CPU copy of `den` for fp64_forward (which otherwise copies `den` on every call)."""
+    return copy.deepcopy(den).cpu().double().eval()
+
+
+def is_fp64_copy(den: torch.nn.Module) -> bool:
+    p = den._first.weight
+    return p.dtype == torch.float64 and p.device.type == "cpu" and not den.training
+
+
 @torch.no_grad()
 def fp64_forward(den: torch.nn.Module, x: torch.Tensor, t: torch.Tensor, z: torch.Tensor) -> torch.Tensor:
     """Denoiser.forward in float64: the drop-in's own nn modules (_first, nn.TransformerEncoder, _last) cast to float64, with the
     oracle's harmonic and time embedding (models/denoiser.py:53-76)."""
     from oracle import pd_oracle as O
-    d64 = copy.deepcopy(den).cpu().double().eval()
+    d64 = den if is_fp64_copy(den) else fp64_copy(den)
     sd = {k: v for k, v in d64.state_dict().items()}
     x, z = x.detach().cpu().double(), z.detach().cpu().double()
     B, N, _ = x.shape

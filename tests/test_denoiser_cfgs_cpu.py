@@ -8,13 +8,13 @@ import pytest
 import torch
 import torch.nn as nn
 
-from denoiser_cfgs import CONFIGS, GOLDEN_CFGS, Cfg, build_dropin
+from denoiser_cfgs import CONFIGS, EDGE_CFGS, GOLDEN_CFGS, Cfg, build_dropin
 from posediffusion_amd import _lib, synth
 from posediffusion_amd.compat import AttrDict
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ODD = Cfg(160, 5, 333, 3, 77, 45, True, True)                # head dim 32, odd FF / z / hidden widths
-ALL = list(dict.fromkeys(CONFIGS + GOLDEN_CFGS + [ODD]))
+ALL = list(dict.fromkeys(CONFIGS + GOLDEN_CFGS + [ODD] + EDGE_CFGS))
 
 
 def _reference_layout(cfg: Cfg):
