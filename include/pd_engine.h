@@ -426,6 +426,10 @@ int pd_debug_lane_tables(pd_engine *eng, int seq, int *out, int n_out);
  * (2^10, 2^-20): 2^-6; (2^-20, 2^-4): 2^-20 (a subnormal times a normal, result far below fp16's range: fp32 accumulation);
  * (1, 1): 16 (control)}; a flushed operand gives 0.  Runs on `stream` and synchronises it. */
 int pd_debug_mfma_f16_subnormal(float *out4_host, void *stream);
+/* The residual stream of the LAST pd_vit_forward_scale call: rows [n_img * T, 384] after the last block, before the final LayerNorm,
+ * copied to dst (DEVICE fp32, n_floats = n_img * T * 384) on `stream`.  PD_ERR_INVALID_ARG when n_floats exceeds what that call wrote.
+ * The forward's own launches are the same with or without it; tests compare EVERY token row with the fp64 network through it. */
+int pd_debug_vit_tokens(pd_vit *v, float *dst, long long n_floats, void *stream);
 
 #ifdef __cplusplus
 }

@@ -148,6 +148,26 @@ def multiscale_features(net: nn.Module, image_rgb: torch.Tensor, scale_factors=(
     return feats / len(scale_factors)                                                   # :82-83
 
 
+@torch.no_grad()
+def token_rows(net: "DinoViT", image_rgb: torch.Tensor, scale_factor=1) -> torch.Tensor:
+    """Every token row [n, T, dim] of one scale after the last block, BEFORE the final LayerNorm (normalise, rescale, patch
+    embedding, CLS / position tokens, blocks): what ``DinoViT.forward`` normalises and takes row 0 of.  In the network's dtype."""
+    dt = net.cls_token.dtype
+    img = image_rgb.to(dt)
+    mean = torch.tensor(RESNET_MEAN, dtype=dt).view(1, 3, 1, 1)
+    std = torch.tensor(RESNET_STD, dtype=dt).view(1, 3, 1, 1)
+    img = (img - mean) / std
+    if scale_factor != 1:
+        img = F.interpolate(img, scale_factor=scale_factor, mode="bilinear", align_corners=False)
+    B, _, w, h = img.shape
+    t = net.patch_embed(img)
+    t = torch.cat((net.cls_token.expand(B, -1, -1), t), dim=1)
+    t = t + net.interpolate_pos_encoding(t, w, h)
+    for blk in net.blocks:
+        t = blk(t)
+    return t
+
+
 def to_hf_vit(net: "DinoViT", img_size: int = 224):
     """The same weights in HuggingFace ``transformers.ViTModel`` (ViT-S/16 configuration, LayerNorm eps 1e-6 as in DINO's
     ``partial(nn.LayerNorm, eps=1e-6)``, no pooler): DINO's fused ``attn.qkv`` rows split into q / k / v projections, every

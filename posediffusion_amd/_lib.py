@@ -118,6 +118,7 @@ SIGNATURES = {
     "pd_debug_ggs_prof": (_i, [_vp, _i, C.POINTER(C.c_longlong)]),
     "pd_debug_ggs_plan": (_i, [_vp, _i, _i, C.POINTER(pd_ggs_cfg), C.POINTER(C.c_int)]),
     "pd_debug_mfma_f16_subnormal": (_i, [C.POINTER(C.c_float), _vp]),
+    "pd_debug_vit_tokens": (_i, [_vp, _vp, C.c_longlong, _vp]),
 }
 
 _lib = None

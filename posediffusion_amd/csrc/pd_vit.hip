@@ -49,6 +49,7 @@ struct pd_vit {
     float *norm_w = nullptr, *norm_b = nullptr, *zero_b = nullptr;
     // workspaces, sized at the first forward / grown on demand
     size_t cap_tokens = 0, cap_pixels = 0;
+    size_t last_tokens = 0;                     // token rows the last forward wrote to x (pd_debug_vit_tokens)
     float *x = nullptr, *xn = nullptr, *qkv = nullptr, *ctx = nullptr, *hid = nullptr, *img = nullptr;
     PdDevAllocs mem{"pd_vit_create"};            // every buffer above
 };
@@ -722,5 +723,16 @@ extern "C" int pd_vit_forward_scale(pd_vit *v, const float *images, int n_img, i
     }
     hipLaunchKernelGGL(vit_final_kernel, dim3(n_img), dim3(64), 0, s, v->x, T, v->norm_w, v->norm_b, weight, accumulate, z_out);
     PD_HIP_CHECK(hipGetLastError());
+    v->last_tokens = tokens;
+    return PD_OK;
+}
+
+// debug: the residual stream of the last forward (every token row after the last block, before the final LayerNorm): a copy of x
+extern "C" int pd_debug_vit_tokens(pd_vit *v, float *dst, long long n_floats, void *stream) {
+    if (!v || !dst || n_floats <= 0 || (unsigned long long)n_floats > (unsigned long long)v->last_tokens * VD) {
+        pd_set_error("pd_debug_vit_tokens: invalid arguments (%lld floats asked, the last forward wrote %zu)", n_floats, v ? v->last_tokens * VD : (size_t)0);
+        return PD_ERR_INVALID_ARG;
+    }
+    PD_HIP_CHECK(hipMemcpyAsync(dst, v->x, (size_t)n_floats * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return PD_OK;
 }

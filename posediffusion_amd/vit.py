@@ -54,7 +54,7 @@ class VitEngine:
         p = lambda k: keep[k].data_ptr()   # noqa: E731
         w.patch_w, w.patch_b, w.cls_token, w.pos_embed = p("patch_embed.proj.weight"), p("patch_embed.proj.bias"), p("cls_token"), p("pos_embed")
         w.norm_w, w.norm_b = p("norm.weight"), p("norm.bias")
-        for l in range(self.depth):
+        for l in range(min(self.depth, len(w.layers))):      # (more blocks than the struct holds: pd_vit_create refuses the depth)
             L, b = w.layers[l], f"blocks.{l}."
             L.norm1_w, L.norm1_b, L.qkv_w, L.qkv_b = p(b + "norm1.weight"), p(b + "norm1.bias"), p(b + "attn.qkv.weight"), p(b + "attn.qkv.bias")
             L.proj_w, L.proj_b, L.norm2_w, L.norm2_b = p(b + "attn.proj.weight"), p(b + "attn.proj.bias"), p(b + "norm2.weight"), p(b + "norm2.bias")
@@ -114,3 +114,22 @@ class VitEngine:
                                                      None if pos is None else pos.data_ptr(), C.c_float(1.0 / len(scale_factors)),
                                                      int(i > 0), z.data_ptr(), stream), "pd_vit_forward_scale")
         return z
+
+    @torch.no_grad()
+    def tokens(self, image_rgb: torch.Tensor, scale_factor: float = 1) -> torch.Tensor:
+        """image_rgb [n,3,H,W] in [0,1] -> [n, T, 384]: EVERY token row after the last block, before the final LayerNorm, of one
+        forward at `scale_factor` (pd_debug_vit_tokens: a copy of the residual stream; the forward's launches are those of `multiscale`).
+        A debug / test view: the product output is the CLS feature of `multiscale`."""
+        x = image_rgb.to(device=self.device, dtype=torch.float32).contiguous()
+        n, _, H, W = x.shape
+        sf = scale_factor
+        hs, ws = (H, W) if sf == 1 else (int(math.floor(H * sf)), int(math.floor(W * sf)))
+        pos = self._pos_for(hs, ws)
+        z = torch.empty(n, self.pos_embed.shape[-1], device=self.device)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        _lib.check(self.lib.pd_vit_forward_scale(self._h, x.data_ptr(), n, H, W, C.c_double(float(sf)), None if pos is None else pos.data_ptr(),
+                                                 C.c_float(1.0), 0, z.data_ptr(), stream), "pd_vit_forward_scale")
+        T = 1 + (hs // PATCH) * (ws // PATCH)
+        out = torch.empty(n, T, self.pos_embed.shape[-1], device=self.device)
+        _lib.check(self.lib.pd_debug_vit_tokens(self._h, out.data_ptr(), out.numel(), stream), "pd_debug_vit_tokens")
+        return out
