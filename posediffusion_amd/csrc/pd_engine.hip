@@ -69,6 +69,63 @@ static int fetch_table(std::vector<float> &dst, const float *dev, int n) {
     return PD_OK;
 }
 
+// ---- stream-event bookkeeping of the match tables (pd_engine::uses / uploads / retired_blobs; destroyed with the engine below) ----
+bool pd_stream_capturing(hipStream_t s) {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    return hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
+}
+
+// (re)record the event a list keeps for stream `s`
+int pd_record_stream_event(std::vector<pd_engine::StreamEvent> &list, hipStream_t s) {
+    for (auto &e : list)
+        if (e.stream == s) {
+            PD_HIP_CHECK(hipEventRecord(e.event, s));
+            return PD_OK;
+        }
+    hipEvent_t ev = nullptr;
+    PD_HIP_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    list.push_back({s, ev});
+    PD_HIP_CHECK(hipEventRecord(ev, s));
+    return PD_OK;
+}
+
+// remember the point on `s` after which this engine's match tables are no longer read
+int pd_mark_use(pd_engine *eng, hipStream_t s) {
+    if (pd_stream_capturing(s)) return PD_OK;   // inside a graph capture: pd_sample_phase marks the replay instead
+    return pd_record_stream_event(eng->uses, s);
+}
+
+// every enqueue that reads the match tables, on whatever stream it ran: waited for on the device (stream s) or on the host
+int pd_wait_uses(pd_engine *eng, hipStream_t s, bool host) {
+    for (auto &e : eng->uses) {
+        if (host) PD_HIP_CHECK(hipEventSynchronize(e.event));
+        else if (e.stream != s) PD_HIP_CHECK(hipStreamWaitEvent(s, e.event, 0));
+    }
+    return PD_OK;
+}
+
+int pd_wait_uploads(pd_engine *eng, hipStream_t s) {
+    if (eng->uploads.empty()) return PD_OK;
+    if (pd_stream_capturing(s)) return PD_OK;   // pd_sample_phase waits before the replay
+    for (auto &e : eng->uploads)
+        if (e.stream != s) PD_HIP_CHECK(hipStreamWaitEvent(s, e.event, 0));      // (same stream: already ordered)
+    return PD_OK;
+}
+
+// outgrown blobs whose last readers have finished
+void pd_free_retired_blobs(pd_engine *eng) {
+    for (size_t i = 0; i < eng->retired_blobs.size();) {
+        if (hipEventQuery(eng->retired_blobs[i].done) == hipSuccess) {
+            (void)hipFree(eng->retired_blobs[i].ptr);
+            (void)hipEventDestroy(eng->retired_blobs[i].done);
+            eng->retired_blobs[i] = eng->retired_blobs.back();
+            eng->retired_blobs.pop_back();
+        } else {
+            ++i;
+        }
+    }
+}
+
 extern "C" void pd_engine_destroy(pd_engine *eng) {
     if (!eng) return;
     (void)hipSetDevice(eng->device);

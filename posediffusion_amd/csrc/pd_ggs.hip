@@ -26,6 +26,11 @@
 //   * blockIdx -> (sequence, workgroup) is XCD-aware: with B % 8 == 0 all workgroups of a sequence
 //     sit on one XCD (dispatcher places block b on XCD b % 8) so the exchange stays in one L2.
 //     That is a speed choice only; correctness uses agent-scope granules and bounded spins.
+//
+// This file: the three GGS kernels (pd_ggs_kernel, pd_ggs2_kernel, pd_ggs_lane_kernel) with their textual includes, the sizing of
+// their LDS images, and the host code bound to those: pd_ggs_init, pd_ggs_plan, pd_ggs_launch.  The match tables the kernels read
+// are built elsewhere: on the host by pd_ggs_tables.hip (pd_ggs_set_matches), on the device by pd_ggs_ingest.hip; the stream
+// events that order uploads against launches belong to pd_engine.hip.
 #include "pd_internal.h"
 
 #include <algorithm>
@@ -1610,371 +1615,8 @@ __global__ __launch_bounds__(PD_GGS_THREADS) void pd_ggs2_kernel(PdGgsParams P, 
 
 #include "pd_ggs_lane.inc"
 // --------------------------------------------------------------------------------------------
-// host side
+// host side: init, launch plan, launch
 // --------------------------------------------------------------------------------------------
-void pd_ggs_free_seq(PdSeqHost &h) {
-    if (h.blob) (void)hipFree(h.blob);
-    h.blob = nullptr;
-    h.blob_bytes = 0;
-    memset(&h.desc, 0, sizeof(h.desc));
-}
-
-// (re)record the event a list keeps for stream `s`
-int pd_record_stream_event(std::vector<pd_engine::StreamEvent> &list, hipStream_t s) {
-    for (auto &e : list)
-        if (e.stream == s) {
-            PD_HIP_CHECK(hipEventRecord(e.event, s));
-            return PD_OK;
-        }
-    hipEvent_t ev = nullptr;
-    PD_HIP_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    list.push_back({s, ev});
-    PD_HIP_CHECK(hipEventRecord(ev, s));
-    return PD_OK;
-}
-
-// remember the point on `s` after which this engine's match tables are no longer read
-int pd_mark_use(pd_engine *eng, hipStream_t s) {
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
-        return PD_OK;   // inside a graph capture: pd_sample_phase marks the replay instead
-    return pd_record_stream_event(eng->uses, s);
-}
-
-// every enqueue that reads the match tables, on whatever stream it ran: waited for on the device (stream s) or on the host
-int pd_wait_uses(pd_engine *eng, hipStream_t s, bool host) {
-    for (auto &e : eng->uses) {
-        if (host) PD_HIP_CHECK(hipEventSynchronize(e.event));
-        else if (e.stream != s) PD_HIP_CHECK(hipStreamWaitEvent(s, e.event, 0));
-    }
-    return PD_OK;
-}
-
-// one slot's descriptor -> device (other slots may hold descriptors the ingestion kernels wrote on the device)
-static int upload_seq_desc(pd_engine *eng, int seq) {
-    PD_HIP_CHECK(hipMemcpy(eng->d_seqs + seq, &eng->seqs[seq].desc, sizeof(PdSeqDesc), hipMemcpyHostToDevice));
-    return PD_OK;
-}
-
-int pd_wait_uploads(pd_engine *eng, hipStream_t s) {
-    if (eng->uploads.empty()) return PD_OK;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone) return PD_OK;   // pd_sample_phase waits before the replay
-    for (auto &e : eng->uploads)
-        if (e.stream != s) PD_HIP_CHECK(hipStreamWaitEvent(s, e.event, 0));      // (same stream: already ordered)
-    return PD_OK;
-}
-
-extern "C" int pd_ggs_set_matches(pd_engine *eng, int seq, const double *kp1, const double *kp2, const int64_t *i12,
-                                  int64_t M, int n_frames, int height, int width) {
-    if (!eng || seq < 0 || seq >= eng->max_B) {
-        pd_set_error("pd_ggs_set_matches: bad engine or sequence slot %d", seq);
-        return PD_ERR_INVALID_ARG;
-    }
-    PD_HIP_CHECK(hipSetDevice(eng->device));
-    // nothing of THIS engine in flight may still read the old tables; other engines (other batches of a pipeline) keep
-    // running: no device-wide synchronisation here, and the blob is re-used when the new tables fit
-    {
-        int rc = pd_wait_uses(eng, nullptr, true);
-        if (rc) return rc;
-    }
-    for (auto &e : eng->uploads) PD_HIP_CHECK(hipEventSynchronize(e.event));   // a pending device-side build of this slot
-    eng->seqs[seq].device_built = false;
-    if (M == 0) {
-        pd_ggs_free_seq(eng->seqs[seq]);
-        return upload_seq_desc(eng, seq);
-    }
-    if (!kp1 || !kp2 || !i12 || M < 0 || n_frames <= 0 || n_frames > PD_MAX_FRAMES || n_frames > eng->max_N ||
-        height <= 0 || width <= 0) {
-        pd_set_error("pd_ggs_set_matches: invalid arguments (M=%lld n_frames=%d h=%d w=%d; n_frames <= %d)",
-                     (long long)M, n_frames, height, width, std::min(PD_MAX_FRAMES, eng->max_N));
-        return PD_ERR_INVALID_ARG;
-    }
-    const int N = n_frames;
-    // stable counting sort by pair key = i * N + j   (geometry_guided_sampling.py:26-27)
-    std::vector<int> cnt((size_t)N * N + 1, 0);
-    for (int64_t m = 0; m < M; ++m) {
-        const int64_t a = i12[2 * m], c = i12[2 * m + 1];
-        if (a < 0 || a >= N || c < 0 || c >= N) {
-            pd_set_error("pd_ggs_set_matches: frame index (%lld,%lld) out of range [0,%d) at match %lld",
-                         (long long)a, (long long)c, N, (long long)m);
-            return PD_ERR_INVALID_ARG;
-        }
-        cnt[a * N + c + 1]++;
-    }
-    std::vector<int> key_off((size_t)N * N + 1, 0);
-    for (int q = 0; q < N * N; ++q) key_off[q + 1] = key_off[q] + cnt[q + 1];
-    std::vector<float4> pts((size_t)M);
-    {
-        std::vector<int> cur(key_off.begin(), key_off.end() - 1);
-        for (int64_t m = 0; m < M; ++m) {
-            const int key = (int)(i12[2 * m] * N + i12[2 * m + 1]);
-            // .float() cast of geometry_guided_sampling.py:167 (round-to-nearest fp64 -> fp32)
-            pts[cur[key]++] = make_float4((float)kp1[2 * m], (float)kp1[2 * m + 1], (float)kp2[2 * m], (float)kp2[2 * m + 1]);
-        }
-    }
-    std::vector<int2> pair_ij;
-    std::vector<int> pair_item_off;
-    std::vector<int4> items;
-    for (int q = 0; q < N * N; ++q) {
-        const int m = key_off[q + 1] - key_off[q];
-        if (m == 0) continue;
-        const int p = (int)pair_ij.size();
-        pair_ij.push_back(make_int2(q / N, q % N));
-        pair_item_off.push_back((int)items.size());
-        const int nch = (m + PD_ITEM_MAX_MATCHES - 1) / PD_ITEM_MAX_MATCHES;
-        int start = key_off[q];
-        for (int c = 0; c < nch; ++c) {
-            const int len = m / nch + (c < m % nch ? 1 : 0);
-            items.push_back(make_int4(p, start, len, 0));
-            start += len;
-        }
-    }
-    pair_item_off.push_back((int)items.size());
-    const int n_pairs = (int)pair_ij.size(), n_items = (int)items.size();
-    int max_item_len = 0;
-    for (const int4 &it : items) max_item_len = std::max(max_item_len, it.z);
-    for (int p = 0; p < n_pairs; ++p)
-        if (pair_item_off[p + 1] - pair_item_off[p] > 0xffff) {
-            pd_set_error("pd_ggs_set_matches: a frame pair holds too many matches");
-            return PD_ERR_UNSUPPORTED;
-        }
-    // per-pair table: positions of the pair's two incidences (side 0 under frame i, side 1 under frame j) among the
-    // incidences of its CHUNK of PD_GGS_THREADS pairs, sorted by frame; pchunk_off[chunk][n] = first position of frame n
-    const int n_pchunks = (n_pairs + PD_GGS_THREADS - 1) / PD_GGS_THREADS;
-    if (n_pchunks > PD_GGS_MAX_PCHUNKS) {
-        pd_set_error("pd_ggs_set_matches: %d frame pairs with matches (max %d)", n_pairs, PD_GGS_MAX_PCHUNKS * PD_GGS_THREADS);
-        return PD_ERR_UNSUPPORTED;
-    }
-    std::vector<int4> ptab(n_pairs);
-    std::vector<int> pchunk_off((size_t)n_pchunks * (N + 1), 0);
-    {
-        std::vector<int> pos0(n_pairs, 0), pos1(n_pairs, 0);
-        for (int ck = 0; ck < n_pchunks; ++ck) {
-            const int p_lo = ck * PD_GGS_THREADS, p_hi = std::min(n_pairs, p_lo + PD_GGS_THREADS);
-            int q = 0;
-            for (int n = 0; n < N; ++n) {
-                pchunk_off[(size_t)ck * (N + 1) + n] = q;
-                for (int p = p_lo; p < p_hi; ++p) {
-                    if (pair_ij[p].x == n) pos0[p] = q++;
-                    if (pair_ij[p].y == n) pos1[p] = q++;
-                }
-            }
-            pchunk_off[(size_t)ck * (N + 1) + N] = q;
-        }
-        for (int p = 0; p < n_pairs; ++p)
-            ptab[p] = make_int4(pair_ij[p].x | (pair_ij[p].y << 8), pair_item_off[p], pair_item_off[p + 1] - pair_item_off[p],
-                                pos0[p] | (pos1[p] << 16));
-    }
-    int max_deg = 0;                       // most pairs incident to one frame: the row stride of the fast per-frame sums (pd_ggs_kernel)
-    {
-        std::vector<int> deg(N, 0);
-        for (int p = 0; p < n_pairs; ++p) {
-            deg[pair_ij[p].x]++;
-            deg[pair_ij[p].y]++;
-        }
-        for (int n = 0; n < N; ++n) max_deg = std::max(max_deg, deg[n]);
-    }
-    // the same positions among ALL incidences (two-hop kernel: one exchange line per (pair, side), grouped by frame)
-    std::vector<int2> gpos(n_pairs);
-    std::vector<int> ginc_off(N + 1, 0);
-    int single_item_pairs = 1;
-    {
-        int q = 0;
-        for (int n = 0; n < N; ++n) {
-            ginc_off[n] = q;
-            for (int p = 0; p < n_pairs; ++p) {
-                if (pair_ij[p].x == n) gpos[p].x = q++;
-                if (pair_ij[p].y == n) gpos[p].y = q++;
-            }
-        }
-        ginc_off[N] = q;
-        for (int p = 0; p < n_pairs; ++p)
-            if (pair_item_off[p + 1] - pair_item_off[p] != 1) single_item_pairs = 0;
-    }
-
-    // lane-per-item tables (pd_ggs_lane_kernel): every pair is cut into ceil(m / len) lane items of balanced size, len = the smallest
-    // length that leaves a sequence at most PD_LANE_MAX_ITEMS items (+ one more cut for the pairs with the longest items while lanes are
-    // left, round 4); lane item q belongs to thread q, a wave's stream holds
-    // max-over-its-lanes steps of two matches per lane (a lane past its item's end re-reads its last match, masked in the kernel)
-    std::vector<int4> litems;
-    std::vector<int2> lwave, lptab(n_pairs);
-    std::vector<float4> lstream;
-    int l_item_len = 0, l_max_steps = 0;
-    if (n_pairs <= PD_LANE_MAX_ITEMS && n_pchunks == 1 && N <= PD_LANE_MAX_FRAMES) {
-        int lo = 1, hi = 1;
-        for (int q = 0; q < N * N; ++q) hi = std::max(hi, key_off[q + 1] - key_off[q]);
-        auto count_items = [&](int len) {
-            long long n = 0;
-            for (int q = 0; q < N * N; ++q) n += pd_lane_items_of(key_off[q + 1] - key_off[q], len);
-            return n;
-        };
-        while (lo < hi) {                                   // smallest len with <= PD_LANE_MAX_ITEMS items (n_pairs items at len = hi)
-            const int mid = (lo + hi) / 2;
-            if (count_items(mid) <= PD_LANE_MAX_ITEMS) hi = mid;
-            else lo = mid + 1;
-        }
-        l_item_len = lo;
-        // Cuts per pair at that length; the lanes this leaves over go, one more cut each, to the pairs whose items are longest (ties: the
-        // earlier pair).  Then the items are ORDERED by length (steps of the pair's longest item, descending; pair; cut), 64 per wave: a
-        // wave runs as many steps as its longest item, and waves w and w + 4 share a SIMD (tools/simd_probe.hip), so long and short waves
-        // pair up.  A pair's items stay adjacent and in cut order (the pair backward sums them in that order).
-        std::vector<int> l_m(n_pairs), l_nch(n_pairs), l_steps(n_pairs);
-        int l_total = 0;
-        for (int p = 0; p < n_pairs; ++p) {
-            const int q = pair_ij[p].x * N + pair_ij[p].y;
-            l_m[p] = key_off[q + 1] - key_off[q];
-            l_nch[p] = pd_lane_items_of(l_m[p], l_item_len);
-            l_total += l_nch[p];
-        }
-        const int spare = PD_LANE_MAX_ITEMS - l_total;
-        {
-            // round 6: k more cuts for the spare / k pairs with the longest items, k by the modelled match pass (pd_lane_pass_cost)
-            std::vector<int> rank(n_pairs, 0), nch_k(n_pairs), steps_k(n_pairs), best_nch = l_nch;
-            for (int p = 0; p < n_pairs; ++p)
-                if (l_nch[p] != 0 && l_m[p] > l_nch[p]) rank[p] = pd_lane_rank(l_m.data(), l_nch.data(), n_pairs, p, false);
-            int best_cost = 0x7fffffff;
-            for (int k = 1; k <= PD_LANE_MORE_MAX; ++k)
-                for (int d = 0; d < PD_LANE_MORE_SLACK && (d == 0 || spare / k - d > 0); ++d) {
-                    int n_items = 0;
-                    for (int p = 0; p < n_pairs; ++p) {
-                        const bool elig = l_nch[p] != 0 && l_m[p] > l_nch[p] && rank[p] < spare / k - d;
-                        nch_k[p] = l_nch[p] + (elig ? std::min(k, l_m[p] - l_nch[p]) : 0);
-                        steps_k[p] = nch_k[p] ? (pd_lane_items_of(l_m[p], nch_k[p]) + 1) / 2 : 0;
-                        n_items += nch_k[p];
-                    }
-                    int T[PD_LANE_WAVES] = {}, Tmin[PD_LANE_WAVES] = {};
-                    for (int p = 0; p < n_pairs; ++p) {
-                        if (!nch_k[p]) continue;
-                        const int first = pd_lane_rank(steps_k.data(), nch_k.data(), n_pairs, p, true), end = first + nch_k[p];
-                        for (int w = (first + 63) / 64; w < PD_LANE_WAVES && 64 * w < end; ++w) T[w] = steps_k[p];                       // item 64 w: the wave's longest
-                        for (int w = first / 64; w < PD_LANE_WAVES && 64 * w < end; ++w)
-                            if (std::min(64 * w + 63, n_items - 1) < end && std::min(64 * w + 63, n_items - 1) >= first) Tmin[w] = steps_k[p];   // its last item
-                    }
-                    const int cost = pd_lane_pass_cost(T, Tmin);
-                    if (cost < best_cost) {
-                        best_cost = cost;
-                        best_nch = nch_k;
-                    }
-                }
-            l_nch = best_nch;
-        }
-        for (int p = 0; p < n_pairs; ++p) l_steps[p] = l_nch[p] ? (pd_lane_items_of(l_m[p], l_nch[p]) + 1) / 2 : 0;
-        litems.assign((size_t)PD_LANE_MAX_ITEMS, make_int4(0, 0, 0, 0));
-        int n_lit = 0;
-        for (int p = 0; p < n_pairs; ++p) {
-            const int q = pair_ij[p].x * N + pair_ij[p].y, m = l_m[p], nch = l_nch[p];
-            const int first = pd_lane_rank(l_steps.data(), l_nch.data(), n_pairs, p, true);
-            lptab[p] = make_int2(first, nch);
-            int start = key_off[q];
-            for (int c = 0; c < nch; ++c) {
-                const int len = m / nch + (c < m % nch ? 1 : 0);
-                litems[(size_t)first + c] = make_int4(pair_ij[p].x | (pair_ij[p].y << 8), len, p, start);
-                start += len;
-            }
-            n_lit += nch;
-        }
-        litems.resize(n_lit);
-        const int n_lw = ((int)litems.size() + 63) / 64;
-        size_t base = 0;
-        for (int w = 0; w < n_lw; ++w) {
-            int steps = 0;
-            for (int l = 0; l < 64 && w * 64 + l < (int)litems.size(); ++l) steps = std::max(steps, (litems[w * 64 + l].y + 1) / 2);
-            lwave.push_back(make_int2((int)base, steps));
-            l_max_steps = std::max(l_max_steps, steps);
-            base += (size_t)steps * 128;
-        }
-        lstream.assign(base, make_float4(1.0f, 1.0f, 1.0f, 1.0f));
-        for (int w = 0; w < n_lw; ++w)
-            for (int t = 0; t < lwave[w].y; ++t)
-                for (int l = 0; l < 64 && w * 64 + l < (int)litems.size(); ++l) {
-                    const int4 it = litems[w * 64 + l];
-                    const float4 a = pts[(size_t)it.w + std::min(2 * t, it.y - 1)], b2 = pts[(size_t)it.w + std::min(2 * t + 1, it.y - 1)];
-                    float4 q0, q1;
-                    pd_interleave_pair(a, b2, q0, q1);
-                    lstream[(size_t)lwave[w].x + (size_t)(2 * t) * 64 + l] = q0;
-                    lstream[(size_t)lwave[w].x + (size_t)(2 * t + 1) * 64 + l] = q1;
-                }
-    }
-
-    // one blob: pts | pair_ij | pair_item_off | items | ptab | pchunk_off   (aligned pieces)
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t o_pts = 0;
-    const size_t o_pij = al(o_pts + sizeof(float4) * pts.size());
-    const size_t o_pio = al(o_pij + sizeof(int2) * pair_ij.size());
-    const size_t o_itm = al(o_pio + sizeof(int) * pair_item_off.size());
-    const size_t o_ptb = al(o_itm + sizeof(int4) * items.size());
-    const size_t o_pco = al(o_ptb + sizeof(int4) * ptab.size());
-    const size_t o_gps = al(o_pco + sizeof(int) * pchunk_off.size());
-    const size_t o_gio = al(o_gps + sizeof(int2) * gpos.size());
-    const size_t o_lit = al(o_gio + sizeof(int) * ginc_off.size());
-    const size_t o_lwv = al(o_lit + sizeof(int4) * litems.size());
-    const size_t o_lpt = al(o_lwv + sizeof(int2) * lwave.size());
-    const size_t o_lst = al(o_lpt + sizeof(int2) * lptab.size());
-    const size_t total = al(o_lst + sizeof(float4) * lstream.size());
-    std::vector<char> host(total, 0);
-    for (const int4 &it : items)                                  // full 128-match groups of every item: pair-interleaved (MatchRegs)
-        for (int g = 0; g + 128 <= it.z; g += 128)
-            for (int l = 0; l < 64; ++l) {
-                float4 &a = pts[(size_t)it.y + g + l], &b = pts[(size_t)it.y + g + 64 + l];
-                float4 q0, q1;
-                pd_interleave_pair(a, b, q0, q1);
-                a = q0;
-                b = q1;
-            }
-    memcpy(host.data() + o_pts, pts.data(), sizeof(float4) * pts.size());
-    memcpy(host.data() + o_pij, pair_ij.data(), sizeof(int2) * pair_ij.size());
-    memcpy(host.data() + o_pio, pair_item_off.data(), sizeof(int) * pair_item_off.size());
-    memcpy(host.data() + o_itm, items.data(), sizeof(int4) * items.size());
-    memcpy(host.data() + o_ptb, ptab.data(), sizeof(int4) * ptab.size());
-    memcpy(host.data() + o_pco, pchunk_off.data(), sizeof(int) * pchunk_off.size());
-    memcpy(host.data() + o_gps, gpos.data(), sizeof(int2) * gpos.size());
-    memcpy(host.data() + o_gio, ginc_off.data(), sizeof(int) * ginc_off.size());
-    if (!litems.empty()) {
-        memcpy(host.data() + o_lit, litems.data(), sizeof(int4) * litems.size());
-        memcpy(host.data() + o_lwv, lwave.data(), sizeof(int2) * lwave.size());
-        memcpy(host.data() + o_lpt, lptab.data(), sizeof(int2) * lptab.size());
-        memcpy(host.data() + o_lst, lstream.data(), sizeof(float4) * lstream.size());
-    }
-    PdSeqHost &h = eng->seqs[seq];
-    if (h.blob_bytes < total) {
-        pd_ggs_free_seq(h);
-        PD_HIP_CHECK(hipMalloc(&h.blob, total));
-        h.blob_bytes = total;
-    }
-    memset(&h.desc, 0, sizeof(h.desc));
-    PD_HIP_CHECK(hipMemcpy(h.blob, host.data(), total, hipMemcpyHostToDevice));
-    char *base = (char *)h.blob;
-    h.desc.pts = (const float4 *)(base + o_pts);
-    h.desc.pair_ij = (const int2 *)(base + o_pij);
-    h.desc.pair_item_off = (const int *)(base + o_pio);
-    h.desc.items = (const int4 *)(base + o_itm);
-    h.desc.ptab = (const int4 *)(base + o_ptb);
-    h.desc.pchunk_off = (const int *)(base + o_pco);
-    h.desc.n_pchunks = n_pchunks;
-    h.desc.gpos = (const int2 *)(base + o_gps);
-    h.desc.ginc_off = (const int *)(base + o_gio);
-    h.desc.single_item_pairs = single_item_pairs;
-    h.desc.lstream = (const float4 *)(base + o_lst);
-    h.desc.litems = (const int4 *)(base + o_lit);
-    h.desc.lwave = (const int2 *)(base + o_lwv);
-    h.desc.lptab = (const int2 *)(base + o_lpt);
-    h.desc.n_litems = (int)litems.size();
-    h.desc.n_lwaves = (int)lwave.size();
-    h.desc.l_item_len = l_item_len;
-    h.desc.l_max_steps = l_max_steps;
-    h.desc.M = (int)M;
-    h.desc.n_pairs = n_pairs;
-    h.desc.n_items = n_items;
-    h.desc.n_frames = N;
-    h.desc.sc = (float)std::min(height, width) / 2.0f;   // opencv_from_cameras_projection scale
-    h.desc.cx = (float)width / 2.0f;
-    h.desc.cy = (float)height / 2.0f;
-    h.max_item_len = max_item_len;
-    h.max_deg = max_deg;
-    return upload_seq_desc(eng, seq);
-}
-
 // Zeroes the exchange granules before every launch (tags restart at 1 per launch).  A KERNEL rather than
 // hipMemsetAsync: under hipGraph replay with a second graph running concurrently, the memset NODE was observed
 // not to be ordered against the neighbouring kernel nodes (stale tags of the previous launch were accepted ->
@@ -1993,16 +1635,13 @@ int pd_ggs_init() {
     return PD_OK;
 }
 
-// The launch shape of one GGS launch, derived from the uploaded match tables: workgroups per sequence, local item
-// slots, dynamic LDS and which kernel.  Captured hipGraphs bake these in, so pd_sample_phase keys its graph cache on
-// the plan (a re-upload with another item count must never replay the old shape: the kernel would index its LDS
-// tables past their size).  Also validates what pd_ggs_launch validates, so a graph replay cannot skip the checks.
-int pd_ggs_plan(pd_engine *eng, int B, int N, const pd_ggs_cfg *cfg, PdGgsPlan *out) {
+// pd_ggs_plan, part 1: the arguments, and that every slot of the launch holds tables for N frames; returns the most work items of a slot
+static int plan_check_slots(pd_engine *eng, int B, int N, const pd_ggs_cfg *cfg, PdGgsPlan *out, int &max_items) {
     if (!eng || !cfg || !out || B <= 0 || B > eng->max_B || N <= 0 || N > eng->max_N || N > PD_MAX_FRAMES) {
         pd_set_error("pd_ggs: invalid arguments (B=%d N=%d)", B, N);
         return PD_ERR_INVALID_ARG;
     }
-    int max_items = 0;
+    max_items = 0;
     for (int b = 0; b < B; ++b) {
         const PdSeqDesc &d = eng->seqs[b].desc;
         if (d.M <= 0 || !eng->seqs[b].blob) {
@@ -2015,44 +1654,47 @@ int pd_ggs_plan(pd_engine *eng, int B, int N, const pd_ggs_cfg *cfg, PdGgsPlan *
         }
         max_items = std::max(max_items, d.n_items);
     }
-    // workgroups per sequence: one item per wave if the chip has room (<= 256 resident workgroups)
-    int device_cus = eng->num_cus > 0 ? eng->num_cus : 256;
-    int k = cfg->wgs_per_seq > 0 ? cfg->wgs_per_seq : (max_items + PD_GGS_WAVES - 1) / PD_GGS_WAVES;
-    k = std::max(1, std::min(k, device_cus / B));
-    // the lane-per-item kernel: on request (PD_GGS_CFG_LANE_ITEMS: what the pipeline sets wherever it gives a sequence ONE workgroup), or when
-    // the engine picks the shape and the launch holds more sequences than half the CUs (nothing to gain from several workgroups per sequence).
-    // An explicit wgs_per_seq without the flag keeps the wave-per-item kernels, whose results are bitwise independent of the workgroup
-    // count (the lane kernel sums in another fixed order: rounding-level differences).  Round 4: its stream goes through an
-    // LDS ring fed by LDS-DMA that never stops (pd_ggs_lane.inc) and it is 10 - 14 % faster than the 12-wave wave-per-item kernel at
-    // the bench shape (18.6 against 21.6 ms per 256-sequence launch, profiles/round4_lane_ring.txt); fully resident sequences 1.5 - 2 x.
-    memset(out, 0, sizeof(*out));
-    if (!(cfg->reserved & PD_GGS_CFG_NO_LANE_ITEMS) &&
-        ((cfg->reserved & PD_GGS_CFG_LANE_ITEMS) || (cfg->wgs_per_seq == 0 && device_cus / B <= 1))) {
-        bool ok = N <= PD_GGS_FAST_FRAMES;
-        int pairs = 0, steps = 0, deg = 0;
-        for (int b = 0; b < B && ok; ++b) {
-            const PdSeqDesc &d = eng->seqs[b].desc;
-            ok = d.n_litems > 0 && d.n_pchunks == 1;
-            pairs = std::max(pairs, d.n_pairs);
-            steps = std::max(steps, d.l_max_steps);
-            deg = std::max(deg, eng->seqs[b].max_deg);
-        }
-        if (ok) {
-            // rows of the pair backward at the fixed per-frame stride of the fast serial phases (pd_ggs_p3b.inc)
-            const int pinc_rows = std::max(2 * std::min(PD_LANE_MAX_ITEMS, std::max(pairs, 1)), N * (((deg + 3) & ~3) + 1));
-            const size_t lds = lane_lds_bytes(pinc_rows);        // tables + the waves' rings (PD_LANE_RING steps of 2 KiB each)
-            if (lds <= 160 * 1024) {
-                out->lane = 1;
-                out->lane_rl = std::max(0, std::min(PD_LANE_RL, steps - PD_LANE_RV));     // (reported: steps of the longest wave that live in LDS for the launch, beside the ring)
-                out->k = 1;
-                out->waves = PD_LANE_WAVES;
-                out->pinc_rows = pinc_rows;
-                out->lds = (int)lds;
-                out->max_items = PD_LANE_MAX_ITEMS;
-                return PD_OK;
-            }
-        }
+    return PD_OK;
+}
+
+// pd_ggs_plan, part 2: does the lane-per-item kernel take the launch?  (true: *out is its plan.)  It does on request (PD_GGS_CFG_LANE_ITEMS:
+// what the pipeline sets wherever it gives a sequence ONE workgroup), or when the engine picks the shape and the launch holds more sequences
+// than half the CUs (nothing to gain from several workgroups per sequence).
+// An explicit wgs_per_seq without the flag keeps the wave-per-item kernels, whose results are bitwise independent of the workgroup
+// count (the lane kernel sums in another fixed order: rounding-level differences).  Round 4: its stream goes through an
+// LDS ring fed by LDS-DMA that never stops (pd_ggs_lane.inc) and it is 10 - 14 % faster than the 12-wave wave-per-item kernel at
+// the bench shape (18.6 against 21.6 ms per 256-sequence launch, profiles/round4_lane_ring.txt); fully resident sequences 1.5 - 2 x.
+static bool plan_lane(const pd_engine *eng, int B, int N, const pd_ggs_cfg *cfg, int device_cus, PdGgsPlan *out) {
+    if ((cfg->reserved & PD_GGS_CFG_NO_LANE_ITEMS) ||
+        !((cfg->reserved & PD_GGS_CFG_LANE_ITEMS) || (cfg->wgs_per_seq == 0 && device_cus / B <= 1)))
+        return false;
+    bool ok = N <= PD_GGS_FAST_FRAMES;
+    int pairs = 0, steps = 0, deg = 0;
+    for (int b = 0; b < B && ok; ++b) {
+        const PdSeqDesc &d = eng->seqs[b].desc;
+        ok = d.n_litems > 0 && d.n_pchunks == 1;
+        pairs = std::max(pairs, d.n_pairs);
+        steps = std::max(steps, d.l_max_steps);
+        deg = std::max(deg, eng->seqs[b].max_deg);
     }
+    if (!ok) return false;
+    // rows of the pair backward at the fixed per-frame stride of the fast serial phases (pd_ggs_p3b.inc)
+    const int pinc_rows = std::max(2 * std::min(PD_LANE_MAX_ITEMS, std::max(pairs, 1)), N * (((deg + 3) & ~3) + 1));
+    const size_t lds = lane_lds_bytes(pinc_rows);        // tables + the waves' rings (PD_LANE_RING steps of 2 KiB each)
+    if (lds > 160 * 1024) return false;
+    out->lane = 1;
+    out->lane_rl = std::max(0, std::min(PD_LANE_RL, steps - PD_LANE_RV));     // (reported: steps of the longest wave that live in LDS for the launch, beside the ring)
+    out->k = 1;
+    out->waves = PD_LANE_WAVES;
+    out->pinc_rows = pinc_rows;
+    out->lds = (int)lds;
+    out->max_items = PD_LANE_MAX_ITEMS;
+    return true;
+}
+
+// pd_ggs_plan, part 3: the wave-per-item kernels -- one-hop or two-hop, workgroups per sequence (from the wanted k), item slots, the LDS
+// image and the XCD-local placement of the exchange
+static int plan_wave_items(const pd_engine *eng, int B, int N, const pd_ggs_cfg *cfg, int device_cus, int k, int max_items, PdGgsPlan *out) {
     // k > 1: every workgroup publishes one exchange line per work item in the sequence's [epoch][item] region of d_xchg
     // (pd_ggs_kernel, `xchg + epoch * xchg_stride + item * PD_XCHG_LINE`): a sequence with more items than the region holds
     // (2 max_N^2 + 512 lines, pd_engine_create) would write into the other epoch's lines or the next slot's -- one workgroup
@@ -2166,6 +1808,22 @@ int pd_ggs_plan(pd_engine *eng, int B, int N, const pd_ggs_cfg *cfg, PdGgsPlan *
     out->two_hop = two_hop ? 1 : 0;
     out->max_items = max_items;
     return PD_OK;
+}
+
+// The launch shape of one GGS launch, derived from the uploaded match tables: workgroups per sequence, local item
+// slots, dynamic LDS and which kernel.  Captured hipGraphs bake these in, so pd_sample_phase keys its graph cache on
+// the plan (a re-upload with another item count must never replay the old shape: the kernel would index its LDS
+// tables past their size).  Also validates what pd_ggs_launch validates, so a graph replay cannot skip the checks.
+int pd_ggs_plan(pd_engine *eng, int B, int N, const pd_ggs_cfg *cfg, PdGgsPlan *out) {
+    int max_items = 0;
+    PD_TRY(plan_check_slots(eng, B, N, cfg, out, max_items));
+    // workgroups per sequence: one item per wave if the chip has room (<= 256 resident workgroups)
+    const int device_cus = eng->num_cus > 0 ? eng->num_cus : 256;
+    int k = cfg->wgs_per_seq > 0 ? cfg->wgs_per_seq : (max_items + PD_GGS_WAVES - 1) / PD_GGS_WAVES;
+    k = std::max(1, std::min(k, device_cus / B));
+    memset(out, 0, sizeof(*out));
+    if (plan_lane(eng, B, N, cfg, device_cus, out)) return PD_OK;
+    return plan_wave_items(eng, B, N, cfg, device_cus, k, max_items, out);
 }
 
 int pd_ggs_launch(pd_engine *eng, float *x, int B, int N, const PdGgsStage *stages, int n_stages,

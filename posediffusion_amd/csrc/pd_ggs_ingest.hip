@@ -46,11 +46,12 @@ struct IngestArgs {
     unsigned int *err_flag;
 };
 
-// blob layout, by capacity (so that it is known before the counts are)
-struct IngestLayout {
-    size_t pts, pij, pio, itm, ptb, pco, gps, gio, lit, lwv, lpt, lst, cnt, keys, hist, total;
+// blob layout, by capacity (so that it is known before the counts are): the arrays of the descriptor in the order and alignment of
+// pd_blob_layout (pd_internal.h), then the scratch of the sort.  The offsets are written out here rather than taken from pd_blob_layout:
+// this function is inlined into four kernels, whose code follows the order of these very expressions.
+struct IngestLayout : PdBlobArrays {
+    size_t cnt, keys, hist, total;   // [N * N + 1] first sorted row of a key | [M] | [n_tiles][N * N]
 };
-static inline size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
 __host__ __device__ static inline void ingest_layout(int M, int N, int P_cap, int I_cap, int C_cap, int LS_cap, IngestLayout &L) {
     auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
     const size_t n_tiles = ((size_t)M + ING_TILE - 1) / ING_TILE;
@@ -179,7 +180,7 @@ __global__ __launch_bounds__(ING_TABLE_THREADS) void ingest_tables_kernel(Ingest
                 ptab[p] = make_int4(i | (j << 8), it, nch, 0);
                 int start = off;
                 for (int c = 0; c < nch; ++c) {               // the host path's split: m / nch (+1 for the first m % nch)
-                    const int len = m / nch + (c < m % nch ? 1 : 0);
+                    const int len = pd_cut_len(m, nch, c);
                     items[it + c] = make_int4(p, start, len, 0);
                     start += len;
                 }
@@ -365,7 +366,7 @@ __global__ __launch_bounds__(ING_TABLE_THREADS) void ingest_tables_kernel(Ingest
                 lptab[p] = make_int2(first, nch);
                 int start = cnt[key];
                 for (int c = 0; c < nch; ++c) {
-                    const int len = m / nch + (c < m % nch ? 1 : 0);
+                    const int len = pd_cut_len(m, nch, c);
                     litems[first + c] = make_int4(i | (j << 8), len, p, start);
                     start += len;
                 }
@@ -579,8 +580,7 @@ extern "C" int pd_ggs_set_matches_csr_async(pd_engine *eng, int seq_first, int n
         sl.LS_cap = lane_ok ? (len_cap + 1) / 2 : 0;
         slices.push_back(sl);
     }
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    const bool capturing = hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
+    const bool capturing = pd_stream_capturing(s);
     // the engine's own in-flight work (on whatever streams) may still read the slots' tables: a DEVICE-side wait, the host does not
     // block; and earlier uploads on other streams are ordered before this one, so the event recorded at the end covers them too
     if (!capturing) {
@@ -589,17 +589,7 @@ extern "C" int pd_ggs_set_matches_csr_async(pd_engine *eng, int seq_first, int n
         for (auto &e : eng->uploads)
             if (e.stream != s) PD_HIP_CHECK(hipStreamWaitEvent(s, e.event, 0));
     }
-    // outgrown blobs whose last readers have finished
-    for (size_t i = 0; i < eng->retired_blobs.size();) {
-        if (hipEventQuery(eng->retired_blobs[i].done) == hipSuccess) {
-            (void)hipFree(eng->retired_blobs[i].ptr);
-            (void)hipEventDestroy(eng->retired_blobs[i].done);
-            eng->retired_blobs[i] = eng->retired_blobs.back();
-            eng->retired_blobs.pop_back();
-        } else {
-            ++i;
-        }
-    }
+    pd_free_retired_blobs(eng);
     bool enqueued = false;
     // every exit after the first enqueue records the upload event: later GGS launches on OTHER streams wait for it (pd_sample_phase /
     // pd_ggs_launch), on the device

@@ -146,6 +146,48 @@ struct PdGgsPlan {
 
 // lane items of one frame pair with m matches at lane-item length len: ceil(m / len) items of balanced size (host and device builders)
 __host__ __device__ inline int pd_lane_items_of(int m, int len) { return (m + len - 1) / len; }
+// length of piece c when m matches are cut into nch balanced pieces: the first m % nch are one longer (work items and lane items, both builders)
+__host__ __device__ inline int pd_cut_len(int m, int nch, int c) { return m / nch + (c < m % nch ? 1 : 0); }
+
+// The slot blob: the twelve arrays of a PdSeqDesc in ONE allocation, each piece 256-byte aligned, in the order written here.
+// PdBlobArrays holds one number per array: element counts going into pd_blob_layout, byte offsets coming out of it; the return value
+// is the aligned end.  The host builder (pd_ggs_tables.hip) sizes the blob by the exact counts.  The device builder sizes it by
+// capacities and puts its scratch behind; its ingest_layout (pd_ggs_ingest.hip) writes the same chain out once more, because it is
+// inlined into kernels whose code must not depend on how this function is phrased.
+struct PdBlobArrays {
+    size_t pts, pij, pio, itm, ptb, pco, gps, gio, lit, lwv, lpt, lst;
+};
+inline size_t pd_al256(size_t v) { return (v + 255) & ~(size_t)255; }
+inline size_t pd_blob_layout(const PdBlobArrays &n, PdBlobArrays &o) {
+    o.pts = 0;
+    o.pij = pd_al256(o.pts + sizeof(float4) * n.pts);
+    o.pio = pd_al256(o.pij + sizeof(int2) * n.pij);
+    o.itm = pd_al256(o.pio + sizeof(int) * n.pio);
+    o.ptb = pd_al256(o.itm + sizeof(int4) * n.itm);
+    o.pco = pd_al256(o.ptb + sizeof(int4) * n.ptb);
+    o.gps = pd_al256(o.pco + sizeof(int) * n.pco);
+    o.gio = pd_al256(o.gps + sizeof(int2) * n.gps);
+    o.lit = pd_al256(o.gio + sizeof(int) * n.gio);
+    o.lwv = pd_al256(o.lit + sizeof(int4) * n.lit);
+    o.lpt = pd_al256(o.lwv + sizeof(int2) * n.lwv);
+    o.lst = pd_al256(o.lpt + sizeof(int2) * n.lpt);
+    return pd_al256(o.lst + sizeof(float4) * n.lst);
+}
+// the pointer half of a descriptor whose arrays live in the blob at `base`
+inline void pd_desc_point_into(PdSeqDesc &d, char *base, const PdBlobArrays &o) {
+    d.pts = (const float4 *)(base + o.pts);
+    d.pair_ij = (const int2 *)(base + o.pij);
+    d.pair_item_off = (const int *)(base + o.pio);
+    d.items = (const int4 *)(base + o.itm);
+    d.ptab = (const int4 *)(base + o.ptb);
+    d.pchunk_off = (const int *)(base + o.pco);
+    d.gpos = (const int2 *)(base + o.gps);
+    d.ginc_off = (const int *)(base + o.gio);
+    d.litems = (const int4 *)(base + o.lit);
+    d.lwave = (const int2 *)(base + o.lwv);
+    d.lptab = (const int2 *)(base + o.lpt);
+    d.lstream = (const float4 *)(base + o.lst);
+}
 // Ordering of the frame pairs of a sequence by item length (host and device builders of the lane tables; n <= 576 keys, quadratic on purpose:
 // the same few lines on both sides).  val[q] = matches (by_steps false: compared through the item length ceil(val / nch)) or steps of
 // the pair's longest item (by_steps true); nch[q] = its cuts, 0 = no such pair.  Returns, for pair p, by_steps false: the NUMBER OF PAIRS
@@ -197,6 +239,16 @@ struct PdSeqHost {
     int max_item_len = 0;      // longest work item (matches); for device-built slots the per-pair hint (or the 512 maximum)
     int max_deg = 0;           // most frame pairs incident to one frame (host-built: exact; device-built: an upper bound from the capacities)
     bool device_built = false; // tables + descriptor were written by the ingestion kernels; the host never saw the counts
+};
+
+// the tables of one sequence as the host builder makes them (pd_build_seq_tables): the arrays of the PdSeqDesc and its match-derived scalars
+struct PdSeqTables {
+    std::vector<float4> pts, lstream;
+    std::vector<int2> pair_ij, gpos, lwave, lptab;
+    std::vector<int> pair_item_off, pchunk_off, ginc_off;
+    std::vector<int4> items, ptab, litems;
+    int n_pchunks = 0, single_item_pairs = 1, l_item_len = 0, l_max_steps = 0;
+    int max_item_len = 0, max_deg = 0;   // (PdSeqHost)
 };
 
 // ---- denoiser -----------------------------------------------------------------------------------
@@ -274,17 +326,22 @@ void pd_denoiser_generic_destroy(pd_engine *eng);
 int pd_denoiser_generic_launch(pd_engine *eng, const float *x, const float *z, int t, int B, int N, float *eps_out, float *mean_out,
                                float *x0_out, const float *noise, float *x_next_out, hipStream_t s);
 
-// pd_ggs.hip
+// pd_ggs.hip: the GGS kernels, their launch plan and launch
 int pd_ggs_init();
 int pd_ggs_plan(pd_engine *eng, int B, int N, const pd_ggs_cfg *cfg, PdGgsPlan *out);
 int pd_ggs_launch(pd_engine *eng, float *x, int B, int N, const PdGgsStage *stages, int n_stages,
                   const pd_ggs_cfg *cfg, int eval_only, float *stats, float *trace, int trace_iters,
                   float *loss_out, float *grad_out, hipStream_t s);
+// pd_ggs_tables.hip: the host builder of the match tables (pd_ggs_set_matches); no kernel
+int pd_build_seq_tables(const double *kp1, const double *kp2, const int64_t *i12, int64_t M, int n_frames, PdSeqTables &out);   // pure: no HIP call, no engine
 void pd_ggs_free_seq(PdSeqHost &h);
-int pd_ggs_ingest_init();   // pd_ggs_ingest.hip
+int pd_ggs_ingest_init();   // pd_ggs_ingest.hip: the device builder (pd_ggs_set_matches_csr_async)
+// pd_engine.hip: the engine's stream-event bookkeeping (pd_engine::uses / uploads / retired_blobs)
+bool pd_stream_capturing(hipStream_t s);
 int pd_wait_uploads(pd_engine *eng, hipStream_t s);   // device-side wait for pending asynchronous match uploads (no-op in a capture)
 int pd_mark_use(pd_engine *eng, hipStream_t s);
 int pd_record_stream_event(std::vector<pd_engine::StreamEvent> &list, hipStream_t s);   // (re)record this stream's event of the list
 int pd_wait_uses(pd_engine *eng, hipStream_t s, bool host);   // wait (device side on s, or on the host) for every recorded use
+void pd_free_retired_blobs(pd_engine *eng);   // outgrown slot blobs whose last readers have finished
 #define PD_GRAPH_CACHE_MAX 8
 #define PD_STAMP_SLOTS 128
