@@ -327,15 +327,20 @@ int pd_pose_embedding(const float *x, long long rows, int dim, float *out, void 
 /* camera_to_rel_deg (util/metric.py:14-47): R_*[B*N,9] row-major 3x3, T_*[B*N,3] in the PyTorch3D convention
  * (X_view = X_world R + T); for every sequence b and every pair i < j in torch.combinations order (:106-111) the angle
  * in degrees between the ground-truth and the predicted relative rotation (so3_relative_angle, :143-151) and between the
- * relative translation directions (:154-172; nan/inf -> 1e6).  Outputs [B * N(N-1)/2] each. */
+ * relative translation directions (:154-172).  A pair with a non-finite translation gets the reference's default of 1e6 rad
+ * (5.7e7 degrees) as its translation error, and a NaN rotation error when the non-finite translation is the second camera's (the
+ * reference's 4x4 product puts 0 * T into the rotation block).  Outputs [B * N(N-1)/2] each. */
 int pd_metrics_rel_pose_errors(const float *R_pred, const float *T_pred, const float *R_gt, const float *T_gt, int B, int N,
                                float *rel_r_deg, float *rel_t_deg, void *stream);
 
 /* out7 = {Auc_max_threshold (calculate_auc_np, util/metric.py:50-78), Racc_5, Racc_15, Racc_30, Tacc_5, Tacc_15,
- * Tacc_30 (test.py:113-119, percent)} over n error pairs. */
+ * Tacc_30 (test.py:113-119, percent)} over n error pairs; 1 <= max_threshold <= 64.  A pair whose r or t is NaN falls in no histogram
+ * bin (np.max propagates it, np.histogram drops it) and below no threshold, but counts in n. */
 int pd_metrics_summary(const float *rel_r_deg, const float *rel_t_deg, int n, int max_threshold, float *out7, void *stream);
 
-/* compute_ARE (util/metric.py:174-185): absolute rotation error in degrees of n rotation pairs [n,9]. */
+/* compute_ARE (util/metric.py:182-192): absolute rotation error in degrees of n rotation pairs [n,9], folded at 90 degrees as the
+ * reference does: e = acos(clip((trace(R_a^T R_b) - 1) / 2, -1, 1)), err = min(e, |180 - e|), so the result lies in [0, 90]; a NaN
+ * trace (a NaN entry, or 0 * inf) gives NaN as np.clip does, an infinite one is clipped and gives 0. */
 int pd_metrics_are(const float *R_a, const float *R_b, int n, float *err_deg, void *stream);
 
 /* pytorch3d.ops.corresponding_cameras_alignment(cameras_src, cameras_tgt, estimate_scale, mode="extrinsics", eps) as

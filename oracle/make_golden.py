@@ -194,6 +194,121 @@ def make_metrics():
     print("metrics.npz", os.path.getsize(os.path.join(OUT, "metrics.npz")))
 
 
+ARE_DEGREES = (0.0, 1e-3, 0.5, 60.0, 89.9, 90.0, 90.1, 120.0, 179.9, 180.0)
+TURN_DEGREES = (1e-3, 0.05, 0.5, 0.81, 1.0, 5.0, 90.0, 175.0, 179.5, 179.99, 180.0)
+AUC_THRESHOLDS = (1, 5, 30, 64)
+
+
+axis_rotation = O.axis_rotation
+
+
+def auc_edge_arrays():
+    """(r, t) fp32 error arrays of 80 pairs that sit on every edge of calculate_auc_np and of the accuracy thresholds: the value under
+    test is the larger one of its pair (the other one is half of it, or below it for values <= 0), first in r, then -- for the edges
+    proper -- in t; then NaN in r only, in t only and in both."""
+    f32 = np.float32
+    up = lambda v: np.nextafter(f32(v), f32(np.inf))          # noqa: E731
+    dn = lambda v: np.nextafter(f32(v), f32(-np.inf))         # noqa: E731
+    edges = [f32(0.0), f32(-0.0), dn(1), up(1), dn(5), up(5), dn(15), up(15), dn(30), up(30), f32(63.0), dn(64), f32(64.0), up(64)]
+    vals = edges + [f32(k) for k in range(1, 31)] + [f32(0.5), f32(-1.0), f32(1e6), f32(1e6 * 180.0 / np.pi), f32(np.inf)]
+    r, t = [], []
+
+    def other(v):
+        return f32(v / 2) if np.isfinite(v) and v > 0 else (f32(3.0) if v > 0 else f32(v - 1))
+
+    for v in vals:
+        r.append(v), t.append(other(v))
+    for v in edges + [f32(np.inf), f32(1e6)]:
+        r.append(other(v)), t.append(v)
+    nan = f32(np.nan)
+    for a, b in ((nan, f32(0.0)), (f32(0.0), nan), (nan, nan), (nan, f32(7.5)), (f32(7.5), nan)):
+        r.append(a), t.append(b)
+    fill = [f32(2.5), f32(7.25), f32(12.75), f32(21.5), f32(29.5), f32(45.25), f32(3.5), f32(17.5), f32(0.25), f32(9.75)]
+    k = 0
+    while len(r) < 80:
+        r.append(fill[k % len(fill)]), t.append(fill[(k + 3) % len(fill)])
+        k += 1
+    assert len(r) == 80
+    return np.array(r, dtype=f32), np.array(t, dtype=f32)
+
+
+def make_metrics_edges():
+    """tests/golden/metrics_edges.npz: the reference's util/metric.py (executed in place through ref_stubs.load_reference_metric) on the
+    edges of its three functions; fp32 inputs and recorded results only.
+      * compute_ARE on rotations by ARE_DEGREES about (1, 2, 3), once from the identity and once from a seeded rotation: the fold
+        min(e, |180 - e|) on both sides of 90 degrees and at 180; then three rows with a NaN or an infinite entry;
+      * camera_to_rel_deg on B = 2 x N = 6 seeded cameras with prediction == ground truth (`same`: identical cameras, 0.405 degrees from the
+        linearly extrapolated acos), with every second predicted camera turned by TURN_DEGREES about (1, 2, 3) (`turn<k>`; 0.81 degrees is
+        where the cosine reaches 1 - 1e-4, 179.19 its mirror), and on B = 12 two-camera sequences with identity rotations whose relative
+        translations are zero on either or both sides, parallel, anti-parallel, orthogonal, 1 / 30 / 89 degrees apart, and non-finite (the
+        1e6 rad default; a non-finite translation of a pair's SECOND camera also makes its rotation error NaN, through the 0 * T term of
+        the reference's 4x4 product) (`trans`);
+      * calculate_auc_np and np.mean(err < k) * 100 on `auc_edge_arrays` for max_threshold in AUC_THRESHOLDS.
+    ref_stubs restates pytorch3d's so3_relative_angle from the oracle (pytorch3d is absent), so the ROTATION-ANGLE entries (`*_r`) pin
+    the kernels to the oracle's restatement of that function, not to pytorch3d; everything else in the file is the reference's own
+    arithmetic."""
+    torch.set_num_threads(1)
+    rm = RS.load_reference_metric()
+    axis = (1.0, 2.0, 3.0)
+    out = {"are_degrees": np.array(ARE_DEGREES), "turn_degrees": np.array(TURN_DEGREES), "auc_thresholds": np.array(AUC_THRESHOLDS)}
+    g = torch.Generator().manual_seed(4711)
+    Q = O.quaternion_to_matrix(torch.randn(1, 4, generator=g, dtype=torch.float64))[0]
+    turns = torch.stack([axis_rotation(axis, d) for d in ARE_DEGREES])
+    Ra = torch.cat([torch.eye(3, dtype=torch.float64).expand(len(ARE_DEGREES), 3, 3), Q.expand(len(ARE_DEGREES), 3, 3)]).float()
+    Rb = torch.cat([turns, Q[None] @ turns]).float()
+    # three non-finite rows: a NaN entry (NaN), an inf entry that meets a non-zero one (trace +-inf, clipped: 0), one that meets a zero (0 * inf: NaN)
+    Ra, Rb = torch.cat([Ra, Q[None].float(), Q[None].float(), torch.eye(3)[None]]), torch.cat([Rb, Rb[13:14], Rb[13:14], Rb[3:4]])
+    Ra[20, 1, 2], Rb[21, 0, 0], Rb[22, 0, 1] = float("nan"), float("inf"), float("inf")
+    out["are_Ra"], out["are_Rb"] = Ra.numpy(), Rb.numpy()
+    out["are_deg"] = rm.compute_ARE(Ra, Rb)
+
+    B, N = 2, 6
+    Rg = O.quaternion_to_matrix(torch.randn(B * N, 4, generator=g, dtype=torch.float64))
+    Tg = torch.randn(B * N, 3, generator=g, dtype=torch.float64) + torch.tensor([0.0, 0.0, 4.0], dtype=torch.float64)
+    cases = {"same": (Rg, Tg, Rg, Tg, B)}
+    for k, d in enumerate(TURN_DEGREES):
+        Rp = Rg.clone()
+        Rp[1::2] = Rg[1::2] @ axis_rotation(axis, d)
+        cases[f"turn{k}"] = (Rp, Tg, Rg, Tg, B)
+    inf = float("inf")
+    rad = np.deg2rad
+    # relative translation (ground truth, prediction) per two-camera sequence; identity rotations: t_rel = T_2 - T_1
+    rel = [((0, 0, 0), (1, 0, 0)), ((0.5, -1, 2), (0, 0, 0)), ((0, 0, 0), (0, 0, 0)), ((0.5, -1, 2), (1, -2, 4)), ((0.5, -1, 2), (-1.5, 3, -6)),
+           ((1, 2, 0), (-2, 1, 3)), ((1, 0, 0), (np.cos(rad(1.0)), np.sin(rad(1.0)), 0)), ((0, 2, 0), (0, np.cos(rad(30.0)), np.sin(rad(30.0)))),
+           ((0, 0, 3), (np.sin(rad(89.0)), 0, np.cos(rad(89.0)))), ((1, 2, 3), (inf, 0, 0)), ((1, 2, 3), (1, 2, 3)), ((1, 2, 3), (1, 2, 3))]
+    Bt = len(rel)
+    base = torch.randn(Bt, 3, generator=g, dtype=torch.float64)
+    Tg2 = torch.stack([base, base + torch.tensor([a for a, _ in rel], dtype=torch.float64)], dim=1).reshape(2 * Bt, 3)
+    Tp2 = torch.stack([base, base + torch.tensor([b for _, b in rel], dtype=torch.float64)], dim=1).reshape(2 * Bt, 3)
+    Tg2[4], Tg2[5], Tp2[4], Tp2[5] = Tg2[4] * 0 + 1.25, Tg2[5] * 0 + 1.25, Tp2[4] * 0 - 0.5, Tp2[5] * 0 - 0.5      # exact zeros on both sides
+    Tg2[0:2] = torch.tensor([0.75, -2.0, 1.5], dtype=torch.float64)                                            # exact zero, ground truth
+    Tp2[2:4] = torch.tensor([-0.25, 1.0, 3.0], dtype=torch.float64)                                            # exact zero, prediction
+    Tp2[20, 1] = -inf                                  # non-finite in the FIRST camera of a predicted pair: rotation error finite, 1e6 default
+    Tg2[23, 2] = float("nan")                          # NaN in the second camera of a ground-truth pair: rotation error NaN, 1e6 default
+    I2 = torch.eye(3, dtype=torch.float64).expand(2 * Bt, 3, 3)
+    cases["trans"] = (I2, Tp2, I2, Tg2, Bt)
+    out["rel_cases"] = np.array(list(cases))
+    res = {}
+    for name, (Rp, Tp, Rg_, Tg_, b) in cases.items():
+        Rp, Tp, Rg_, Tg_ = (x.float().contiguous() for x in (Rp, Tp, Rg_, Tg_))
+        one = torch.ones(Rp.shape[0], 2)
+        r, t = rm.camera_to_rel_deg(rm.Cameras(R=Rp, T=Tp, focal_length=one), rm.Cameras(R=Rg_, T=Tg_, focal_length=one), torch.device("cpu"), b)
+        res[name] = (Rp.numpy(), Tp.numpy(), Rg_.numpy(), Tg_.numpy(), r.numpy(), t.numpy())
+    # `same` and `turn<k>` share the ground truth and the translations: stored once (`base_*`), the turned rotations and the results stacked
+    turn = [res[f"turn{k}"] for k in range(len(TURN_DEGREES))]
+    out.update(base_Rg=res["same"][2], base_Tg=res["same"][3], base_B=np.array(B), same_r=res["same"][4], same_t=res["same"][5],
+               turn_Rp=np.stack([c[0] for c in turn]), turn_r=np.stack([c[4] for c in turn]), turn_t=np.stack([c[5] for c in turn]))
+    out.update(trans_Rp=res["trans"][0], trans_Tp=res["trans"][1], trans_Rg=res["trans"][2], trans_Tg=res["trans"][3], trans_B=np.array(Bt),
+               trans_r=res["trans"][4], trans_t=res["trans"][5])
+
+    er, et = auc_edge_arrays()
+    out["auc_r"], out["auc_t"] = er, et
+    out["auc"] = np.array([rm.calculate_auc_np(er, et, max_threshold=m) for m in AUC_THRESHOLDS], dtype=np.float64)
+    out["racc"] = np.array([np.mean(er < k) * 100 for k in (5, 15, 30)], dtype=np.float64)
+    out["tacc"] = np.array([np.mean(et < k) * 100 for k in (5, 15, 30)], dtype=np.float64)
+    np.savez_compressed(os.path.join(OUT, "metrics_edges.npz"), **out)
+    print("metrics_edges.npz", os.path.getsize(os.path.join(OUT, "metrics_edges.npz")))
+
 
 def make_preprocess():
     """tests/golden/preprocess.npz (+ tests/golden/images/*.png, a few KB): the reference's util/load_img_folder.py
@@ -486,11 +601,14 @@ if __name__ == "__main__":
         make_guided_free(seeds=(1, 2), N=20, cond_start=10, per_pair=300, name="guided_free_full_s12", store_matches=False)
     elif len(sys.argv) > 1 and sys.argv[1] == "metrics":
         make_metrics()          # only the N3 fixture (the others stay byte-identical)
+    elif len(sys.argv) > 1 and sys.argv[1] == "metrics_edges":
+        make_metrics_edges()    # only the metric-edge fixture
     elif len(sys.argv) > 1 and sys.argv[1] == "preprocess":
         make_preprocess()       # only the N4 fixture
     else:
         main()
         make_metrics()
+        make_metrics_edges()
         make_preprocess()
         make_guided_free()
         make_guided_free(seeds=(0,), N=20, cond_start=10, per_pair=300, name="guided_free_full")

@@ -582,11 +582,21 @@ def calculate_auc_np(r_error: np.ndarray, t_error: np.ndarray, max_threshold: in
     return float(np.mean(np.cumsum(histogram.astype(float) / float(len(max_errors)))))
 
 
+def axis_rotation(axis, degrees) -> torch.Tensor:
+    """fp64 rotation matrix by `degrees` about `axis` (Rodrigues' formula); test inputs only"""
+    a = torch.tensor(axis, dtype=torch.float64)
+    a = a / a.norm()
+    K = hat(a[None])[0]
+    th = torch.tensor(np.deg2rad(degrees), dtype=torch.float64)
+    return torch.eye(3, dtype=torch.float64) + torch.sin(th) * K + (1.0 - torch.cos(th)) * (K @ K)
+
+
 def compute_ARE(R1: np.ndarray, R2: np.ndarray) -> np.ndarray:
-    """util/metric.py:174-185: absolute rotation error in degrees."""
+    """util/metric.py:182-192: absolute rotation error in degrees, folded at 90 degrees (min(e, |180 - e|)) as the reference has it."""
     R_rel = np.einsum("Bij,Bjk ->Bik", R1.transpose(0, 2, 1), R2)
     t = (np.trace(R_rel, axis1=1, axis2=2) - 1) / 2
-    return np.arccos(np.clip(t, -1, 1)) * 180 / np.pi
+    error = np.arccos(np.clip(t, -1, 1)) * 180 / np.pi
+    return np.minimum(error, np.abs(180 - error))
 
 
 def corresponding_cameras_alignment(R_src, T_src, R_tgt, T_tgt, estimate_scale: bool = True, eps: float = 1e-9):

@@ -4,7 +4,7 @@
 //   util/metric.py:14-47     camera_to_rel_deg: pairwise relative poses of all i < j per sequence, rotation angle and
 //                            translation-direction angle between prediction and ground truth (:106-172)
 //   util/metric.py:50-78     calculate_auc_np; test.py:113-121 the Racc / Tacc thresholds
-//   util/metric.py:174-185   compute_ARE
+//   util/metric.py:182-192   compute_ARE (the angle folded at 90 degrees: min(e, |180 - e|))
 //   demo.py:127-129          pytorch3d.ops.corresponding_cameras_alignment(estimate_scale=True, mode="extrinsics")
 // pytorch3d pieces (absent from the reference tree, restated from the published 0.7.x algorithms, see
 // oracle/pd_oracle.py): get_world_to_view_transform().get_matrix() = [[R, 0], [T, 1]] (row vectors),
@@ -35,8 +35,12 @@ __device__ __forceinline__ void pd_atb(const float *A, const float *B, float *C)
 
 // relative pose of cameras (R1, T1) -> (R2, T2) in the row-vector world-to-view convention:
 // inverse(se3_1) @ se3_2 = [[R1^T R2, 0], [T2 - T1 R1^T R2, 1]]   (metric.py:39-40, :114-140)
+// The reference forms the 4x4 product, whose rotation block also holds the term 0 * T2[c] (last column of the inverse times last row of
+// se3_2): zero for a finite T2, NaN for an infinite or NaN one, so that such a camera's pairs get a NaN rotation error.  Kept.
 __device__ __forceinline__ void pd_rel_pose(const float *R1, const float *T1, const float *R2, const float *T2, float *Rr, float *tr) {
     pd_atb(R1, R2, Rr);
+#pragma unroll
+    for (int q = 0; q < 9; ++q) Rr[q] += 0.0f * T2[q % 3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) tr[c] = T2[c] - (T1[0] * Rr[0 * 3 + c] + T1[1] * Rr[1 * 3 + c] + T1[2] * Rr[2 * 3 + c]);
 }
@@ -68,9 +72,10 @@ __global__ void pd_metrics_pairs_kernel(const float *__restrict__ Rp, const floa
     const float np_ = sqrtf(tpr[0] * tpr[0] + tpr[1] * tpr[1] + tpr[2] * tpr[2]) + eps;
     const float ng = sqrtf(tgr[0] * tgr[0] + tgr[1] * tgr[1] + tgr[2] * tgr[2]) + eps;
     const float d = (tpr[0] / np_) * (tgr[0] / ng) + (tpr[1] / np_) * (tgr[1] / ng) + (tpr[2] / np_) * (tgr[2] / ng);
-    const float loss = fmaxf(1.0f - d * d, eps);
+    const float l = 1.0f - d * d;
+    const float loss = l != l ? l : fmaxf(l, eps);               // torch.clamp_min keeps NaN (fmaxf alone would return eps: an error of 0)
     float e = acosf(sqrtf(1.0f - loss));
-    if (isnan(e) || isinf(e)) e = 1e6f;
+    if (isnan(e) || isinf(e)) e = 1e6f;                          // non-finite translations: the 1e6 rad default   :179
     t_deg[idx] = e * PD_RAD2DEG;
 }
 
@@ -85,7 +90,9 @@ __global__ __launch_bounds__(256) void pd_metrics_summary_kernel(const float *__
     __syncthreads();
     for (int i = tid; i < n; i += blockDim.x) {
         const float rv = r[i], tv = t[i];
-        const float m = fmaxf(rv, tv);                           // np.max over (r, t)   :64-67
+        // np.max over (r, t) propagates NaN (fmaxf alone would return the other operand) and np.histogram drops a NaN: such a pair is
+        // in no bin but still counts in n   :64-67
+        const float m = (rv != rv || tv != tv) ? NAN : fmaxf(rv, tv);
         // np.histogram(bins = arange(max_threshold + 1)): unit bins, the last one closed on the right   :70-73
         if (m >= 0.0f && m <= (float)max_threshold) {
             int bin = (int)floorf(m);
@@ -117,8 +124,10 @@ __global__ void pd_metrics_are_kernel(const float *__restrict__ Ra, const float 
     float tr = 0.0f;                                             // trace(Ra^T Rb) = sum of the elementwise product
 #pragma unroll
     for (int q = 0; q < 9; ++q) tr += Ra[i * 9 + q] * Rb[i * 9 + q];
-    const float c = fminf(fmaxf((tr - 1.0f) * 0.5f, -1.0f), 1.0f);
-    err[i] = acosf(c) * PD_RAD2DEG;
+    const float h = (tr - 1.0f) * 0.5f;
+    const float c = h != h ? h : fminf(fmaxf(h, -1.0f), 1.0f);   // np.clip keeps NaN (fmaxf / fminf alone would return -1: a folded error of 0)
+    const float e = acosf(c) * PD_RAD2DEG;
+    err[i] = fminf(e, fabsf(180.0f - e));                        // np.minimum(error, np.abs(180 - error))   :192
 }
 
 // one-sided Jacobi SVD of a 3x3 matrix in double: A = U diag(s) V^T (U, V orthogonal; adequate for the near-rotation

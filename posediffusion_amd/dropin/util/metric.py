@@ -48,7 +48,9 @@ def camera_to_rel_deg(pred_cameras, gt_cameras, device, batch_size):
 
 def rotation_angle(rot_gt, rot_pred, batch_size=None):
     """metric.py:143-151 for explicit relative rotations [n,3,3]: so3_relative_angle in degrees.  (Identity second
-    cameras turn the pair kernel into exactly this: R1 = I, T = 0 -> relative rotation = R2.)"""
+    cameras turn the pair kernel into exactly this: R1 = I, T = 0 -> relative rotation = R2.)
+    pytorch3d's so3_relative_angle raises on a trace outside [-1 - eps, 3 + eps]; an asynchronous kernel cannot, and such a
+    trace goes through the linearly extrapolated acos like any other."""
     rot_gt, rot_pred = _dev_f32(rot_gt), _dev_f32(rot_pred)
     n = rot_gt.shape[0]
     eye = torch.eye(3, device=rot_gt.device).expand(n, 3, 3)
@@ -89,7 +91,7 @@ def calculate_auc(r_error, t_error, max_threshold=30):
 
 
 def compute_ARE(rotation1, rotation2):
-    """metric.py:174-185 -> numpy array of degrees."""
+    """metric.py:182-192 -> numpy array of degrees, folded at 90 as the reference does: min(e, |180 - e|)."""
     dev = rotation1.device if isinstance(rotation1, torch.Tensor) and rotation1.is_cuda else torch.device("cuda", torch.cuda.current_device())
     Ra, Rb = _dev_f32(rotation1, dev), _dev_f32(rotation2, dev)
     err = torch.empty(Ra.shape[0], device=dev)

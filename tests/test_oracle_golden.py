@@ -270,6 +270,34 @@ def test_metrics_oracle_against_reference_fixture(golden):
     assert np.abs(O.compute_ARE(g["R_pred"], g["R_gt"]) - g["are_deg"]).max() < 1e-5
 
 
+def test_metrics_oracle_against_reference_edge_fixture(golden):
+    """O.compute_ARE / O.camera_to_rel_deg / O.calculate_auc_np on the edges recorded from the reference (oracle/make_golden.py
+    make_metrics_edges): the fold of the ARE at 90 degrees, both extrapolated ends of the rotation angle, zero / parallel / orthogonal
+    relative translations and the 1e6 default, every bin edge and threshold of the AUC, NaN and inf errors."""
+    g = golden["metrics_edges"]
+    are = O.compute_ARE(g["are_Ra"], g["are_Rb"])
+    assert np.isnan(g["are_deg"]).tolist() == [False] * 20 + [True, False, True] and g["are_deg"][21] == 0.0      # NaN entry, inf trace, 0 * inf
+    assert np.array_equal(np.isnan(are), np.isnan(g["are_deg"])) and np.nanmax(np.abs(are - g["are_deg"])) < 1e-5, (are, g["are_deg"])
+    assert np.nanmax(g["are_deg"]) <= 90.0 and abs(g["are_deg"][7] - 60.0) < 1e-3    # 120 degrees reads 60
+    default = np.float32(1e6) * np.float32(180.0 / np.pi)
+    from metrics_checks import fixture_rel_case
+    for name in g["rel_cases"]:
+        c = fixture_rel_case(g, name)
+        r, t = O.camera_to_rel_deg(*(torch.from_numpy(np.ascontiguousarray(c[k])) for k in ("Rp", "Tp", "Rg", "Tg")), c["B"])
+        r, t, rr, tr = r.numpy(), t.numpy(), c["r"], c["t"]
+        assert np.array_equal(np.isnan(r), np.isnan(rr)) and np.array_equal(np.isnan(t), np.isnan(tr)), name
+        big = tr > 1e5                                                                 # the 1e6 rad default: by equality
+        assert np.array_equal(t[big], tr[big]) and np.all(np.abs(tr[big] / default - 1) < 1e-6), name
+        ok = ~np.isnan(rr)
+        assert np.abs(r[ok] - rr[ok]).max() < 1e-5, name
+        ok = ~np.isnan(tr) & ~big
+        assert np.abs(t[ok] - tr[ok]).max() < 1e-5, name
+    assert (g["trans_t"] > 1e5).sum() == 3 and np.isnan(g["trans_r"]).tolist() == [False] * 9 + [True, False, True] and (g["trans_t"] == 90.0).sum() >= 4
+    for m, auc in zip(g["auc_thresholds"], g["auc"]):
+        assert abs(O.calculate_auc_np(g["auc_r"], g["auc_t"], int(m)) - float(auc)) < 1e-12, m
+        assert abs(O.calculate_auc_np(g["auc_r"].astype(np.float64), g["auc_t"].astype(np.float64), int(m)) - float(auc)) < 1e-12, m
+
+
 def test_camera_alignment_recovers_a_similarity_exactly():
     """The restated pytorch3d alignment (unpinned against pytorch3d's source) must at least undo any similarity of the
     world: X' = s X R_A + T_A maps cameras (R, T) to (R_A^T R, s T - T_A R_A^T R)."""
