@@ -1,5 +1,5 @@
 // pd_denoiser_dev.h -- shapes, device-side weight tables and small wave helpers shared by the
-// denoiser kernels (pd_denoiser.hip, pd_gemm_stream.h).
+// denoiser's host side (pd_denoiser.hip) and kernels (pd_gemm_small.h, pd_attn.h, pd_denoiser_kernels.h, pd_gemm_stream.h).
 #pragma once
 #include "pd_weight_prep.h"
 

@@ -39,6 +39,11 @@ struct PdQkvAttnArgs {
 };
 // sequences per workgroup: whole sequences in at most 95 token rows (96 rows + the zero row + the score tiles would exceed the 160 KiB of LDS by 528 B)
 static inline int pd_qkv_attn_group(int N) { return N >= 1 && N <= 32 ? (PD_QA_ROWS - 1) / N : 0; }
+// workgroups of a launch, one per (group of sequences, head); 0 for N > 32, which the kernel does not take
+static inline int pd_qkv_attn_wgs(int B, int N) {
+    const int G = pd_qkv_attn_group(N);
+    return G ? ((B + G - 1) / G) * NH : 0;
+}
 static inline size_t pd_qkv_attn_lds(int N) {
     const int G = pd_qkv_attn_group(N);
     const size_t image = (size_t)(G * N + 1) * PD_QA_LDR * sizeof(float);          // Q | K | V rows + one zero row
@@ -330,12 +335,11 @@ __global__ __launch_bounds__(PD_QA_THREADS) void pd_qkv_attn_kernel(PdQkvAttnArg
 // LayerNorm output (split words) -> ctx (split words) for B sequences of N <= 32 frames
 static inline void pd_qkv_attn(const unsigned *hn, const unsigned *Wh, const float *bias, unsigned *ctx, int B, int N, float c_scale, float out_scale,
                                hipStream_t s) {
-    const int G = pd_qkv_attn_group(N);
-    PdQkvAttnArgs g{hn, Wh, bias, ctx, B, N, G, c_scale, out_scale};
+    PdQkvAttnArgs g{hn, Wh, bias, ctx, B, N, pd_qkv_attn_group(N), c_scale, out_scale};
+    const dim3 grid(pd_qkv_attn_wgs(B, N)), blk(PD_QA_THREADS);
+    const size_t lds = pd_qkv_attn_lds(N);
 #ifdef PD_DEV_KNOBS
     static const int bare = pd_dev_knob("PD_QA_BARE", 0);
-    const dim3 grid(((B + G - 1) / G) * NH), blk(PD_QA_THREADS);
-    const size_t lds = pd_qkv_attn_lds(N);
     static const int deep = pd_dev_knob("PD_QA_DEEP", PD_QA_DEEP_DEFAULT);
     if (bare == 0 && !deep) { hipLaunchKernelGGL((pd_qkv_attn_kernel<0, false>), grid, blk, lds, s, g); return; }
     switch (bare) {
@@ -347,5 +351,5 @@ static inline void pd_qkv_attn(const unsigned *hn, const unsigned *Wh, const flo
     default: break;
     }
 #endif
-    hipLaunchKernelGGL((pd_qkv_attn_kernel<0, PD_QA_DEEP_DEFAULT != 0>), dim3(((B + G - 1) / G) * NH), dim3(PD_QA_THREADS), pd_qkv_attn_lds(N), s, g);
+    hipLaunchKernelGGL((pd_qkv_attn_kernel<0, PD_QA_DEEP_DEFAULT != 0>), grid, blk, lds, s, g);
 }
