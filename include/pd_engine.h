@@ -164,6 +164,31 @@ int pd_p_mean(pd_engine *eng, const float *x, const float *z, int t, int B, int 
 int pd_p_finish(pd_engine *eng, const float *mean, const float *noise, int t, int B, int N,
                 float *x_out, void *stream);
 
+/* ---- one timestep per sequence: the forward half of the training branch ------------------------
+ * GaussianDiffusion.forward / p_losses draw one t per sequence (gaussian_diffuser.py:331).  These entry points run that forward pass
+ * in ONE pass of the denoiser: `_first` and the tail look the timestep of every token row up on the device (t_seq[row / N]); a
+ * t_seq whose entries are all equal gives bitwise the results of the single-t entry points.  Forward only: nothing here computes
+ * a gradient, and the network is evaluated as under model.eval() -- dropout off (the reference under model.train() applies
+ * dropout 0.1, which the engine deliberately does not reproduce).
+ * An entry of t_seq outside [0, timesteps) cannot be seen by the host without a synchronisation: the device clamps it into the
+ * range (so no table is read out of bounds) and raises bit 3 of the asynchronous error word (pd_check_async_error).
+ * Argument checks and limits are those of pd_denoise_step: N <= 64, B <= max_B, N <= max_N; default-shape and generic engines,
+ * every PD_OPT_DENOISER_SPLIT mode.  Asynchronous on `stream`, no host synchronisation. */
+
+/* [timesteps] DEVICE fp32 each, copied (synchronously); needed by pd_p_losses only (gaussian_diffuser.py:164-165) */
+int pd_engine_set_q_tables(pd_engine *eng, const float *sqrt_alphas_cumprod, const float *sqrt_one_minus_alphas_cumprod);
+
+/* Denoiser.forward(x, t[B], z) with one timestep per sequence (models/denoiser.py:53-76); t_seq DEVICE int64 [B] */
+int pd_denoise_step_t(pd_engine *eng, const float *x, const float *z, const int64_t *t_seq, int B, int N, float *out, void *stream);
+
+/* GaussianDiffusion.p_losses (:308-327), eval-mode forward: x_t = q_sample(x_start, t, noise) (:211-216, one elementwise launch that
+ * also validates t_seq), model_out = Denoiser(x_t, t, z), loss = loss_fn(model_out, target, reduction "none").
+ * loss_type 1 = l1, 2 = l2 (elementwise).  Outputs [B,N,9] DEVICE, each may be NULL except loss_out: loss, x_0_pred, x_t, model_out.
+ * Target = noise (pred_noise; x_0_pred = predict_start_from_noise(x_t, t, model_out)) or x_start (PD_WEIGHTS_PRED_X0, then
+ * x_0_pred = model_out).  PD_ERR_STATE without q tables. */
+int pd_p_losses(pd_engine *eng, const float *x_start, const float *z, const int64_t *t_seq, const float *noise, int B, int N,
+                int loss_type, float *loss_out, float *x0_pred_out, float *xt_out, float *model_out, void *stream);
+
 /* ---- Geometry-Guided Sampling ------------------------------------------------------------ */
 
 /* Upload the matches of sequence slot `seq` (0 <= seq < max_B).  Replaces the per-call host
@@ -306,6 +331,16 @@ int pd_pose_to_camera_ex(pd_engine *eng, const float *enc, int n_cameras, float 
                          float *focal_out, float log_focal_length_bias, float min_focal_length, float max_focal_length,
                          void *stream);
 
+/* camera_to_pose_encoding (camera_transform.py:108-129), the inverse of the decode above; stateless like the metric kernels.
+ * R [n,9] row-major, T [n,3], focal [n,2] -> enc [n,9] = [T (copied unchanged) | quaternion (real part first) | logFL] with
+ * logFL = log(clamp(focal, min_focal_length, max_focal_length)) - log_focal_length_bias.  The quaternion is current pytorch3d's
+ * matrix_to_quaternion: the four candidates q_abs = sqrt(max(0, 1 +- m00 +- m11 +- m22)), the candidate row of the largest q_abs
+ * divided by 2 max(q_abs, 0.1), standardised to a non-negative real part.  pytorch3d is not a dependency of this project: this
+ * function is checked against an fp64 restatement of that rule (tests/pose_codec_checks.py), not against a fixture that the
+ * reference generated.  DEVICE pointers. */
+int pd_camera_to_pose(const float *R, const float *T, const float *focal, int n, float log_focal_length_bias,
+                      float min_focal_length, float max_focal_length, float *enc_out, void *stream);
+
 /* ---- rows D2 / D3 as stand-alone operators (stateless, all pointers DEVICE fp32) --------------------
  * The engine fuses both embeddings into the denoiser (a [T,128] table built at creation; the harmonic columns formed while
  * _first's rows are staged).  These two entry points run the same device code for a caller that uses the reference's
@@ -412,7 +447,8 @@ int pd_time_kernel(pd_engine *eng, int what, int B, int N, const pd_ggs_cfg *cfg
 
 /* Synchronises the device and reports (PD_ERR_STATE) what the kernels flagged asynchronously since the last check: a
  * bounded spin of the GGS cross-workgroup exchange that gave up (bit 0), an out-of-range frame index (bit 1) or violated
- * pd_match_hints (bit 2) met by pd_ggs_set_matches_csr_async.  Clears the word.  PD_OK otherwise. */
+ * pd_match_hints (bit 2) met by pd_ggs_set_matches_csr_async, a timestep outside [0, timesteps) met (and clamped) by
+ * pd_denoise_step_t / pd_p_losses (bit 3).  Clears the word.  PD_OK otherwise. */
 int pd_check_async_error(pd_engine *eng);
 
 /* Debug aid: switch the GGS kernel's in-kernel phase cycle counters on/off and (out6 != NULL)

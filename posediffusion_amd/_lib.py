@@ -86,6 +86,10 @@ SIGNATURES = {
     "pd_last_error": (C.c_char_p, []),
     "pd_version": (C.c_char_p, []),
     "pd_denoise_step": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    "pd_engine_set_q_tables": (_i, [_vp, _vp, _vp]),
+    "pd_denoise_step_t": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
+    "pd_p_losses": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "pd_camera_to_pose": (_i, [_vp, _vp, _vp, _i, C.c_float, C.c_float, C.c_float, _vp, _vp]),
     "pd_p_mean": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "pd_p_finish": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "pd_ggs_set_matches": (_i, [_vp, _i, _vp, _vp, _vp, _i64, _i, _i, _i]),

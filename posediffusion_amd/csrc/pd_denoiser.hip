@@ -13,6 +13,8 @@
 // This file is the host side: engine creation, the split-precision weights, and one step's launches.  The kernels are in the headers:
 //   pd_gemm_small.h (small batches), pd_gemm_stream.h / pd_gemm_split.h (large batches: exact / split precision), pd_attn.h and
 //   pd_qkv_attn.h (attention), pd_denoiser_kernels.h (embeddings, tail, probe); pd_denoiser_plan.h decides which of them a step launches.
+// One timestep per sequence (pd_denoise_step_t, pd_p_losses) changes _first and the tail only: den_first_small_t, den_first_streamed_t,
+// den_tail_t below; the streamed path's per-row-bias GEMM is instantiated in pd_denoiser_first_t.hip.
 #include "pd_denoiser_dev.h"
 #include "pd_gemm_stream.h"
 #include "pd_gemm_split.h"
@@ -134,6 +136,7 @@ static int den_set_gemm_lds() {     // the 32- / 16-wide pair of a small-batch G
 }
 static int den_set_lds_attributes() {
     PD_TRY((den_set_gemm_lds<KFIRST_PAD, 2, 0>()));
+    PD_TRY((den_set_gemm_lds<KFIRST_PAD, 3, 0>()));
     PD_TRY((den_set_gemm_lds<DM, 1, 0>()));
     PD_TRY((den_set_gemm_lds<DM, 1, 1>()));
     PD_TRY((den_set_gemm_lds<DM, 0, 2>()));
@@ -268,6 +271,18 @@ static void den_first_streamed(const PdDenoiserDev *d, const float *x, int t, in
     pd_gemm_dma<4>(d->emb, KFIRST_D, d->first_df, KFIRST_D, d->ttab + (size_t)t * DM, d->h, M, DM, s, nullptr, d->zproj);
 }
 
+// the same two with one timestep per token row: the A staging picks row t_row[m] of the time table; the bias becomes ttab[t_row[m]]
+static void den_first_small_t(const pd_engine *eng, const PdDenoiserDev *d, GemmArgs &g, const float *x, const float *z, const int *t_row, int N, int MT,
+                              hipStream_t s) {
+    g.bias = d->first_b; g.C = d->h; g.Nout = DM;
+    g.x = x; g.z = z; g.temb = d->t_table; g.t_row = t_row; g.n_frames = N;
+    launch_gemm<KFIRST_PAD, 3, 0>(g, d->first_wp, MT, eng->gemm_wide_min_tiles, s);
+}
+static void den_first_streamed_t(const PdDenoiserDev *d, const float *x, const int *t_row, int N, int M, hipStream_t s) {
+    hipLaunchKernelGGL(pd_embed_rows_kernel, dim3((M + 3) / 4), dim3(256), 0, s, x, N, M, d->emb);
+    pd_den_first_gemm_t(d, t_row, M, s);
+}
+
 static void den_layer_small(const pd_engine *eng, const PdDenoiserDev *d, const PdLayerDev &L, GemmArgs &g, int B, int N, int MT, hipStream_t s) {
     // x += MHA(LN1(x))
     g.A = d->h; g.bias = L.qkv_b; g.C = d->qkv; g.Nout = 3 * DM;
@@ -358,10 +373,39 @@ static void den_tail(const pd_engine *eng, const PdDenoiserDev *d, const float *
     hipLaunchKernelGGL(pd_tail_kernel, dim3((M + 3) / 4), dim3(256), 0, s, ha);
 }
 
+// the tail with every row's own schedule coefficients and the outputs of p_losses
+static void den_tail_t(const pd_engine *eng, const PdDenoiserDev *d, const float *x, int M, const PdTSeq &ts, float *eps_out, float *x0_out, hipStream_t s) {
+    HeadArgsT a;
+    memset(&a, 0, sizeof(a));
+    a.h.hid = d->hid; a.h.lnw = d->last_ln_w; a.h.lnb = d->last_ln_b;
+    a.h.w3 = d->last3_w; a.h.b3 = d->last3_b; a.h.x = x;
+    a.h.eps_out = eps_out; a.h.x0_out = x0_out;
+    a.h.M = M;
+    a.h.pred_x0 = eng->pred_x0;
+    a.t_row = ts.t_row; a.c_recip = eng->d_c_recip; a.c_recipm1 = eng->d_c_recipm1;
+    a.target = ts.target; a.loss_out = ts.loss_out; a.loss_type = ts.loss_type;
+    hipLaunchKernelGGL(pd_tail_t_kernel, dim3((M + 3) / 4), dim3(256), 0, s, a);
+}
+
+// t_seq [B] -> eng->d_t_row [B x N], clamped and checked on the device (bit 3 of the asynchronous error word); B, N checked by the caller
+int pd_denoiser_t_rows(pd_engine *eng, const int64_t *t_seq, int B, int N, hipStream_t s) {
+    const int M = B * N;
+    hipLaunchKernelGGL(pd_t_rows_kernel, dim3((M + 255) / 256), dim3(256), 0, s, t_seq, M, N, eng->timesteps, eng->d_t_row, eng->d_err);
+    PD_HIP_CHECK(hipGetLastError());
+    return PD_OK;
+}
+int pd_denoiser_q_sample(pd_engine *eng, const float *x_start, const float *noise, const int64_t *t_seq, int B, int N, float *xt, hipStream_t s) {
+    const int M = B * N;
+    hipLaunchKernelGGL(pd_q_sample_kernel, dim3((M * 9 + 255) / 256), dim3(256), 0, s, x_start, noise, t_seq, eng->d_q_a, eng->d_q_b, M, N, eng->timesteps,
+                       xt, eng->d_t_row, eng->d_err);
+    PD_HIP_CHECK(hipGetLastError());
+    return PD_OK;
+}
+
 // z_prepared: pd_denoiser_prepare ran for this z (the sampling loop calls it once); otherwise it is issued here (the step-level API)
 int pd_denoiser_launch(pd_engine *eng, const float *x, const float *z, int t, int B, int N, float *eps_out,
-                       float *mean_out, float *x0_out, const float *noise, float *x_next_out, hipStream_t s, bool z_prepared) {
-    if (eng->gden) return pd_denoiser_generic_launch(eng, x, z, t, B, N, eps_out, mean_out, x0_out, noise, x_next_out, s);
+                       float *mean_out, float *x0_out, const float *noise, float *x_next_out, hipStream_t s, bool z_prepared, const PdTSeq *ts) {
+    if (eng->gden) return pd_denoiser_generic_launch(eng, x, z, t, B, N, eps_out, mean_out, x0_out, noise, x_next_out, s, ts);
     PdDenoiserDev *d = eng->den;
     if (!x || !z || B <= 0 || N <= 0 || B > eng->max_B || N > eng->max_N || N > 64 || t < 0 || t >= d->timesteps) {
         pd_set_error("denoiser: invalid arguments (B=%d N=%d t=%d; max_B=%d max_N=%d, N <= 64, 0 <= t < %d)", B, N, t,
@@ -380,7 +424,9 @@ int pd_denoiser_launch(pd_engine *eng, const float *x, const float *z, int t, in
     GemmArgs g;                       // the small path's launches share it
     memset(&g, 0, sizeof(g));
     g.M = M;
-    if (small) den_first_small(eng, d, g, x, z, t, N, p.MT, s);
+    if (small && ts) den_first_small_t(eng, d, g, x, z, ts->t_row, N, p.MT, s);
+    else if (small) den_first_small(eng, d, g, x, z, t, N, p.MT, s);
+    else if (ts) den_first_streamed_t(d, x, ts->t_row, N, M, s);
     else den_first_streamed(d, x, t, N, M, s);
     for (int l = 0; l < d->num_layers; ++l) {
         const PdLayerDev &L = d->layers[l];
@@ -398,7 +444,8 @@ int pd_denoiser_launch(pd_engine *eng, const float *x, const float *z, int t, in
     } else {
         pd_gemm_dma<0>(d->h, DM, d->last0_wf, DM, d->last0_b, d->hid, M, HID, s);
     }
-    den_tail(eng, d, x, t, M, eps_out, mean_out, x0_out, noise, x_next_out, small, s);
+    if (ts) den_tail_t(eng, d, x, M, *ts, eps_out, x0_out, s);
+    else den_tail(eng, d, x, t, M, eps_out, mean_out, x0_out, noise, x_next_out, small, s);
     PD_HIP_CHECK(hipGetLastError());
     return PD_OK;
 }

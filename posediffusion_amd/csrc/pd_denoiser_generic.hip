@@ -71,9 +71,12 @@ __global__ void pd_gen_pad_kernel(const float *__restrict__ W, int src_rows, int
 // _first's input rows in the reference's column order (models/denoiser.py:56-68):
 //   [0,180) harmonic(x) | [180,189) x | [189,317) t_emb(t) | [317,317+z) z | pivot (frame 0 of a sequence; when enabled) | 0 padding
 // the harmonic expressions are those of pd_embed_rows_kernel (pytorch3d HarmonicEmbedding, n = 10, append_input)
+// TSEQ: one timestep per sequence -- temb is the whole table [T, 128] and row m takes its row t_row[m] (else temb is the row of the launch's t)
 // --------------------------------------------------------------------------------------------
+template <bool TSEQ>
 __global__ __launch_bounds__(256) void pd_gen_embed_kernel(const float *__restrict__ x, const float *__restrict__ z, const float *__restrict__ temb,
-                                                           int M, int n_frames, int zdim, int pivot, int Kfp, float *__restrict__ out) {
+                                                           int M, int n_frames, int zdim, int pivot, int Kfp, float *__restrict__ out,
+                                                           const int *__restrict__ t_row) {
     const size_t total = (size_t)M * Kfp;
     for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
         const int c = (int)(idx % Kfp);
@@ -86,7 +89,7 @@ __global__ __launch_bounds__(256) void pd_gen_embed_kernel(const float *__restri
         } else if (c < 189) {
             v = x[(size_t)row * 9 + (c - 180)];
         } else if (c < PD_GEN_FIRST_FIXED) {
-            v = temb[c - 189];
+            v = TSEQ ? temb[(size_t)t_row[row] * 128 + (c - 189)] : temb[c - 189];
         } else if (c < PD_GEN_FIRST_FIXED + zdim) {
             v = z[(size_t)row * zdim + (c - PD_GEN_FIRST_FIXED)];
         } else if (pivot && c == PD_GEN_FIRST_FIXED + zdim) {
@@ -192,7 +195,14 @@ struct PdGenTailArgs {
     float *eps_out, *mean_out, *x0_out, *xnext_out;
     float c_recip, c_recipm1, coef1, coef2, sigma;
     int M, H, Hp, pred_x0;
+    // TSEQ (pd_denoise_step_t, pd_p_losses): every row's own coefficients from device tables, and the loss (gaussian_diffuser.py:312-327)
+    const int *t_row;                     // [M]
+    const float *c_recip_tab, *c_recipm1_tab;
+    const float *target;                  // [M, 9], null without loss_out
+    float *loss_out;
+    int loss_type;                        // 1 = l1, 2 = l2
 };
+template <bool TSEQ>
 __global__ __launch_bounds__(256) void pd_gen_tail_kernel(PdGenTailArgs g) {
     const int lane = threadIdx.x & 63, m = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (m >= g.M) return;
@@ -233,6 +243,16 @@ __global__ __launch_bounds__(256) void pd_gen_tail_kernel(PdGenTailArgs g) {
         const size_t at = (size_t)m * 9 + lane;
         const float xv = g.x[at];
         e += g.b3[lane];
+        if constexpr (TSEQ) {
+            const int t = g.t_row[m];
+            if (g.eps_out) g.eps_out[at] = e;
+            if (g.x0_out) g.x0_out[at] = g.pred_x0 ? e : g.c_recip_tab[t] * xv - g.c_recipm1_tab[t] * e;   // :316, :319
+            if (g.loss_out) {
+                const float d = e - g.target[at];
+                g.loss_out[at] = g.loss_type == 2 ? d * d : fabsf(d);                                      // :323, reduction "none"
+            }
+            return;
+        }
         const float x0 = g.pred_x0 ? e : g.c_recip * xv - g.c_recipm1 * e;   // gaussian_diffuser.py:190-194, :221-227
         const float mu = g.coef1 * x0 + g.coef2 * xv;                     // :201-205
         if (g.eps_out) g.eps_out[at] = e;
@@ -355,7 +375,7 @@ void pd_denoiser_generic_destroy(pd_engine *eng) {
 }
 
 int pd_denoiser_generic_launch(pd_engine *eng, const float *x, const float *z, int t, int B, int N, float *eps_out, float *mean_out,
-                               float *x0_out, const float *noise, float *x_next_out, hipStream_t s) {
+                               float *x0_out, const float *noise, float *x_next_out, hipStream_t s, const PdTSeq *ts) {
     PdGenericDen *G = eng->gden;
     if (!x || !z || B <= 0 || N <= 0 || B > eng->max_B || N > eng->max_N || N > 64 || t < 0 || t >= G->timesteps) {
         pd_set_error("denoiser: invalid arguments (B=%d N=%d t=%d; max_B=%d max_N=%d, N <= 64, 0 <= t < %d)", B, N, t, eng->max_B, eng->max_N,
@@ -367,7 +387,8 @@ int pd_denoiser_generic_launch(pd_engine *eng, const float *x, const float *z, i
     {
         const size_t total = (size_t)M * G->Kfp;
         const int blocks = (int)std::min<size_t>((total + 255) / 256, 4096);
-        hipLaunchKernelGGL(pd_gen_embed_kernel, dim3(blocks), dim3(256), 0, s, x, z, G->t_table + (size_t)t * 128, M, N, G->z, G->pivot, G->Kfp, G->emb);
+        if (ts) hipLaunchKernelGGL(pd_gen_embed_kernel<true>, dim3(blocks), dim3(256), 0, s, x, z, G->t_table, M, N, G->z, G->pivot, G->Kfp, G->emb, ts->t_row);
+        else hipLaunchKernelGGL(pd_gen_embed_kernel<false>, dim3(blocks), dim3(256), 0, s, x, z, G->t_table + (size_t)t * 128, M, N, G->z, G->pivot, G->Kfp, G->emb, nullptr);
     }
     pd_gemm_dma<0>(G->emb, G->Kfp, G->first_w, G->Kfp, G->first_b, G->h, M, Dp, s);
     const float scale = 1.0f / sqrtf((float)G->hd);
@@ -405,7 +426,13 @@ int pd_denoiser_generic_launch(pd_engine *eng, const float *x, const float *z, i
     ta.c_recip = eng->c_recip[t]; ta.c_recipm1 = eng->c_recipm1[t]; ta.coef1 = eng->coef1[t]; ta.coef2 = eng->coef2[t];
     ta.sigma = expf(0.5f * eng->logvar[t]);
     ta.M = M; ta.H = G->hid; ta.Hp = G->Hp; ta.pred_x0 = eng->pred_x0;
-    hipLaunchKernelGGL(pd_gen_tail_kernel, dim3(rows_blocks), dim3(256), 0, s, ta);
+    if (ts) {
+        ta.t_row = ts->t_row; ta.c_recip_tab = eng->d_c_recip; ta.c_recipm1_tab = eng->d_c_recipm1;
+        ta.target = ts->target; ta.loss_out = ts->loss_out; ta.loss_type = ts->loss_type;
+        hipLaunchKernelGGL(pd_gen_tail_kernel<true>, dim3(rows_blocks), dim3(256), 0, s, ta);
+    } else {
+        hipLaunchKernelGGL(pd_gen_tail_kernel<false>, dim3(rows_blocks), dim3(256), 0, s, ta);
+    }
     PD_HIP_CHECK(hipGetLastError());
     return PD_OK;
 }

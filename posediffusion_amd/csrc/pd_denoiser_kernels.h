@@ -126,20 +126,10 @@ struct HeadArgs {
 #endif
 };
 
-__global__ __launch_bounds__(256) void pd_tail_kernel(HeadArgs g) {
-#ifdef PD_DEN_STAMPS
-    long long *const stamps = g.stamps;
-#endif
-    PD_STAMP(stamps, 0);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int m = blockIdx.x * 4 + wave;
-    if (m >= g.M) return;
+// LayerNorm(128) -> ReLU -> Linear(128 -> 9) of token row m, shared by the two tail kernels: lane o < 9 returns output o WITHOUT its bias
+__device__ __forceinline__ float pd_tail_project(const HeadArgs &g, int m, int lane) {
     const float *row = g.hid + (size_t)m * HID;
     const float v0 = row[lane], v1 = row[64 + lane];
-    // everything the last nine lanes add at the end is requested now (clamped lane: no predicated loads), not behind the reductions
-    const int l9 = lane < 9 ? lane : 8;
-    const size_t at = (size_t)m * 9 + l9;
-    const float b3v = g.b3[l9], xv = g.x[at], nz = g.noise ? g.noise[at] : 0.0f;
     const float mean = pd_wave_sum(v0 + v1) * (1.0f / HID);
     const float d0 = v0 - mean, d1 = v1 - mean;
     const float rstd = 1.0f / sqrtf(pd_wave_sum(d0 * d0 + d1 * d1) * (1.0f / HID) + 1e-5f);
@@ -151,6 +141,22 @@ __global__ __launch_bounds__(256) void pd_tail_kernel(HeadArgs g) {
         const float part = pd_wave_sum(fmaf(a0, g.w3[o * HID + lane], a1 * g.w3[o * HID + 64 + lane]));
         e = (lane == o) ? part : e;
     }
+    return e;
+}
+
+__global__ __launch_bounds__(256) void pd_tail_kernel(HeadArgs g) {
+#ifdef PD_DEN_STAMPS
+    long long *const stamps = g.stamps;
+#endif
+    PD_STAMP(stamps, 0);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int m = blockIdx.x * 4 + wave;
+    if (m >= g.M) return;
+    // everything the last nine lanes add at the end is requested now (clamped lane: no predicated loads), not behind the reductions
+    const int l9 = lane < 9 ? lane : 8;
+    const size_t at = (size_t)m * 9 + l9;
+    const float b3v = g.b3[l9], xv = g.x[at], nz = g.noise ? g.noise[at] : 0.0f;
+    float e = pd_tail_project(g, m, lane);
     if (lane < 9) {
         e += b3v;
         const float x0 = g.pred_x0 ? e : g.c_recip * xv - g.c_recipm1 * e;   // gaussian_diffuser.py:190-194, :221-227
@@ -163,6 +169,66 @@ __global__ __launch_bounds__(256) void pd_tail_kernel(HeadArgs g) {
     PD_STAMP(stamps, 5);
     PD_STAMP_DRAIN();
     PD_STAMP(stamps, 6);
+}
+
+// --------------------------------------------------------------------------------------------
+// one timestep per sequence (pd_denoise_step_t, pd_p_losses; gaussian_diffuser.py:308-332)
+// --------------------------------------------------------------------------------------------
+#define PD_ASYNC_ERR_T_RANGE 8u     // bit 3 of the asynchronous error word: an entry of t_seq outside [0, timesteps)
+// t_seq[b] clamped into [0, timesteps): nothing downstream indexes a table out of bounds; a clamped entry raises the error word
+__device__ __forceinline__ int pd_t_checked(const int64_t *__restrict__ t_seq, int b, int timesteps, unsigned int *err) {
+    const long long tv = t_seq[b];
+    if (tv >= 0 && tv < timesteps) return (int)tv;
+    atomicOr(err, PD_ASYNC_ERR_T_RANGE);
+    return tv < 0 ? 0 : timesteps - 1;
+}
+// t_row[m] = t_seq[m / n_frames]: the per-row index that _first and the tail read (pd_denoise_step_t's pre-pass)
+__global__ void pd_t_rows_kernel(const int64_t *__restrict__ t_seq, int M, int n_frames, int timesteps, int *__restrict__ t_row,
+                                 unsigned int *err) {
+    const int m = blockIdx.x * blockDim.x + threadIdx.x;
+    if (m < M) t_row[m] = pd_t_checked(t_seq, m / n_frames, timesteps, err);
+}
+// q_sample (gaussian_diffuser.py:211-216): x_t = sqrt_alphas_cumprod[t] x_start + sqrt_one_minus_alphas_cumprod[t] noise over the
+// M * 9 values, in torch's own roundings (two products, one sum: no fused multiply-add); the element of column 0 also writes t_row[m]
+__global__ void pd_q_sample_kernel(const float *__restrict__ x_start, const float *__restrict__ noise, const int64_t *__restrict__ t_seq,
+                                   const float *__restrict__ qa, const float *__restrict__ qb, int M, int n_frames, int timesteps,
+                                   float *__restrict__ xt, int *__restrict__ t_row, unsigned int *err) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= M * 9) return;
+    const int m = i / 9;
+    const int t = pd_t_checked(t_seq, m / n_frames, timesteps, err);
+    if (i - m * 9 == 0) t_row[m] = t;
+    xt[i] = __fadd_rn(__fmul_rn(qa[t], x_start[i]), __fmul_rn(qb[t], noise[i]));
+}
+// pd_tail_kernel with the schedule coefficients of every row's own timestep (device tables) and the outputs of p_losses (:312-327):
+// eps_out = the model output, x0_out = x_0_pred, loss_out = |model_out - target| (loss_type 1) or its square (2), each may be null
+struct HeadArgsT {
+    HeadArgs h;                           // hid .. b3, x (= x_t), eps_out, x0_out, M, pred_x0; the posterior fields are not read
+    const int *t_row;                     // [M]
+    const float *c_recip, *c_recipm1;     // [timesteps] sqrt_recip_alphas_cumprod, sqrt_recipm1_alphas_cumprod
+    const float *target;                  // [M, 9] noise (pred_noise) or x_start (pred_x0); null without loss_out
+    float *loss_out;
+    int loss_type;
+};
+__global__ __launch_bounds__(256) void pd_tail_t_kernel(HeadArgsT a) {
+    const HeadArgs &g = a.h;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int m = blockIdx.x * 4 + wave;
+    if (m >= g.M) return;
+    const int l9 = lane < 9 ? lane : 8;
+    const size_t at = (size_t)m * 9 + l9;
+    const int t = a.t_row[m];
+    const float b3v = g.b3[l9], xv = g.x[at], tg = a.loss_out ? a.target[at] : 0.0f, cr = a.c_recip[t], crm1 = a.c_recipm1[t];
+    float e = pd_tail_project(g, m, lane);
+    if (lane < 9) {
+        e += b3v;
+        if (g.eps_out) g.eps_out[at] = e;
+        if (g.x0_out) g.x0_out[at] = g.pred_x0 ? e : cr * xv - crm1 * e;     // gaussian_diffuser.py:316, :319
+        if (a.loss_out) {
+            const float d = e - tg;
+            a.loss_out[at] = a.loss_type == 2 ? d * d : fabsf(d);               // F.mse_loss / F.l1_loss, reduction "none" (:323)
+        }
+    }
 }
 
 // ---- probe: fp16-subnormal operands on the fp16 matrix pipe (pd_engine.h pd_debug_mfma_f16_subnormal) ----------------------------

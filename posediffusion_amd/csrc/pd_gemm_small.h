@@ -19,6 +19,7 @@
 //   AMODE 0: A' = A                      (plain rows of a [M, K] activation)
 //   AMODE 1: A' = LayerNorm(A) (K = 512) (norm_first encoder layer, eps 1e-5)
 //   AMODE 2: A' = [z | t_emb | harmonic(x) | x | pivot | 0 0]  (K = 704, denoiser.py:56-68; the engine's column order pd_first_col_all)
+//   AMODE 3: AMODE 2 with one timestep per token row: t_emb is row t_row[m] of the whole time table (pd_denoise_step_t, pd_p_losses)
 //   EPI   0: + bias     1: relu(+ bias)     2: + bias + residual (in place on C)
 // --------------------------------------------------------------------------------------------
 // -DPD_DEN_STAMPS (tools/den_small_legs.py; never in the product build): every launch of the small-batch chain records, from lane 0 of
@@ -42,10 +43,11 @@ struct GemmArgs {
     const float *bias;     // [Nout]
     float *C;              // [M, Nout]
     // AMODE 2
-    const float *x, *z, *temb;   // x [M,9], z [M,384], temb [128] (row of the table for this t)
+    const float *x, *z, *temb;   // x [M,9], z [M,384], temb [128] (row of the table for this t; AMODE 3: the whole table [T,128])
     int n_frames;
     int M, Nout;
     int MT;                // number of 32-row M tiles (XCD-aware block mapping)
+    const int *t_row;      // AMODE 3: [M] timestep of every token row, already inside [0, T)
 };
 
 template <int K, int AMODE, int EPI, int NT>
@@ -92,10 +94,11 @@ __global__ __launch_bounds__(256) void pd_gemm_kernel(GemmArgs g) {
         const bool live = m < g.M;
         const int mr = live ? m : g.M - 1;   // clamp: padded rows load a valid row and are zeroed
         float *dst = As + r * LDA;
-        if constexpr (AMODE == 2) {
+        if constexpr (AMODE == 2 || AMODE == 3) {
             // engine column order (pd_first_col_all): z | t_emb | harmonic | x | pivot | pad
             const float4 *zr = (const float4 *)(g.z + (size_t)mr * ZD);
             const float4 *te = (const float4 *)g.temb;
+            if constexpr (AMODE == 3) te += (size_t)g.t_row[mr] * 32;      // this row's own timestep: the same 128 values a single-t launch stages
             float4 zv[ZD / 32], tv[4];
 #pragma unroll
             for (int i = 0; i < ZD / 32; ++i) zv[i] = zr[sub + 8 * i];

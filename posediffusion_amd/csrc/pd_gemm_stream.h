@@ -107,12 +107,15 @@ __global__ __launch_bounds__(256) void pd_ln_stats_kernel(const float *__restric
 //   with a register stage.  Blocks walk groups of ~2048 rows x all column tiles, so that a group's A rows and the whole W
 //   stay in the L2s.  EPI 0: + bias   1: relu(+ bias)   2: + bias + C (residual, in place)   3: gelu(+ bias), exact erf form
 //   4 (pd_gemm_dma_kernel only): + bias + R (another [M, Nout] array).
+//   5 (pd_gemm_dma_kernel only): EPI 4 with a bias per ROW: + bias[t_row[m]][n] + R, bias a [T, Nout] table -- the time piece of the denoiser's
+//     _first when every sequence has a timestep of its own; the same two additions in the same order as EPI 4 with the table's row t.
 struct PdStreamArgs {
     const float *A, *W, *bias;
     float *C;
     int M, Nout, K, lda, ldw;
     const float2 *ln_stats;   // ALN only: (mean, rstd) of every A row (pd_ln_stats_kernel)
-    const float *R;           // EPI 4 only: [M, Nout] added to the result (the hoisted z piece of the denoiser's _first)
+    const float *R;           // EPI 4 / 5: [M, Nout] added to the result (the hoisted z piece of the denoiser's _first)
+    const int *t_row;         // EPI 5 only: [M] row of the bias table for every A row, already inside the table
 };
 #define PD_STREAM_KC 32
 #define PD_STREAM_LR (PD_STREAM_KC + 4)      // LDS row stride: fragment reads and staging writes both conflict free
@@ -395,11 +398,16 @@ __global__ __launch_bounds__(256) void pd_gemm_dma_kernel(PdStreamArgs g) {
 #pragma unroll
             for (int ni = 0; ni < WN; ++ni) {
                 const int colb = n0 + (wn * WN + ni) * 32 + pc, rb = m0 + (wm * WM + mi) * 32;
-                const float4 bias4 = *(const float4 *)(g.bias + colb);
+                float4 bias4, brow4[4];
+                if constexpr (EPI != 5) bias4 = *(const float4 *)(g.bias + colb);
+                if constexpr (EPI == 5) {     // a sequence boundary may fall anywhere in the tile: every row looks its own table row up
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) brow4[q] = *(const float4 *)(g.bias + (size_t)g.t_row[min(rb + 8 * q + pr, g.M - 1)] * g.Nout + colb);
+                }
 #pragma unroll
                 for (int i = 0; i < 16; ++i) patch[((i & 3) + 8 * (i >> 2) + 4 * hi) * 36 + l31] = acc[mi][ni][i];
                 float4 res4[4];
-                if constexpr (EPI == 2 || EPI == 4) {
+                if constexpr (EPI == 2 || EPI == 4 || EPI == 5) {
                     const float *rsrc = EPI == 2 ? g.C : g.R;
 #pragma unroll
                     for (int q = 0; q < 4; ++q) res4[q] = *(const float4 *)(rsrc + (size_t)min(rb + 8 * q + pr, g.M - 1) * g.Nout + colb);
@@ -408,13 +416,14 @@ __global__ __launch_bounds__(256) void pd_gemm_dma_kernel(PdStreamArgs g) {
                 for (int q = 0; q < 4; ++q) {
                     const int row = rb + 8 * q + pr;
                     const float4 a4 = *(const float4 *)(patch + (8 * q + pr) * 36 + pc);
+                    if constexpr (EPI == 5) bias4 = brow4[q];
                     float v[4] = {a4.x + bias4.x, a4.y + bias4.y, a4.z + bias4.z, a4.w + bias4.w};
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         if constexpr (EPI == 1) v[e] = pd_relu(v[e]);
                         if constexpr (EPI == 3) v[e] = 0.5f * v[e] * (1.0f + erff(v[e] * 0.70710678118654752f));
                     }
-                    if constexpr (EPI == 2 || EPI == 4) {
+                    if constexpr (EPI == 2 || EPI == 4 || EPI == 5) {
                         v[0] += res4[q].x; v[1] += res4[q].y; v[2] += res4[q].z; v[3] += res4[q].w;
                     }
                     if (row < g.M) *(float4 *)(g.C + (size_t)row * g.Nout + colb) = make_float4(v[0], v[1], v[2], v[3]);
@@ -428,9 +437,9 @@ __global__ __launch_bounds__(256) void pd_gemm_dma_kernel(PdStreamArgs g) {
 #pragma unroll
         for (int ni = 0; ni < WN; ++ni) {
             const int col = n0 + (wn * WN + ni) * 32 + l31, r0 = m0 + (wm * WM + mi) * 32 + 4 * hi;
-            const float bias = g.bias[col];
+            const float bias = EPI == 5 ? 0.0f : g.bias[col];
             float res[16];
-            if constexpr (EPI == 2 || EPI == 4) {
+            if constexpr (EPI == 2 || EPI == 4 || EPI == 5) {
                 const float *rsrc = EPI == 2 ? g.C : g.R;
 #pragma unroll
                 for (int i = 0; i < 16; ++i) res[i] = rsrc[(size_t)min(r0 + (i & 3) + 8 * (i >> 2), g.M - 1) * g.Nout + col];
@@ -438,10 +447,10 @@ __global__ __launch_bounds__(256) void pd_gemm_dma_kernel(PdStreamArgs g) {
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
                 const int row = r0 + (i & 3) + 8 * (i >> 2);
-                float v = acc[mi][ni][i] + bias;
+                float v = acc[mi][ni][i] + (EPI == 5 ? g.bias[(size_t)g.t_row[min(row, g.M - 1)] * g.Nout + col] : bias);
                 if constexpr (EPI == 1) v = pd_relu(v);
                 if constexpr (EPI == 3) v = 0.5f * v * (1.0f + erff(v * 0.70710678118654752f));
-                if constexpr (EPI == 2 || EPI == 4) v += res[i];
+                if constexpr (EPI == 2 || EPI == 4 || EPI == 5) v += res[i];
                 if (row < g.M) g.C[(size_t)row * g.Nout + col] = v;
             }
         }
@@ -449,8 +458,8 @@ __global__ __launch_bounds__(256) void pd_gemm_dma_kernel(PdStreamArgs g) {
 
 template <int EPI, bool ALN = false, int WM = 1, int WN = 1>
 static inline void pd_gemm_dma(const float *A, int lda, const float *W, int K, const float *bias, float *C, int M, int Nout, hipStream_t s,
-                               const float2 *ln_stats = nullptr, const float *R = nullptr) {
-    PdStreamArgs g{A, W, bias, C, M, Nout, K, lda, K, ln_stats, R};
+                               const float2 *ln_stats = nullptr, const float *R = nullptr, const int *t_row = nullptr) {
+    PdStreamArgs g{A, W, bias, C, M, Nout, K, lda, K, ln_stats, R, t_row};
     hipLaunchKernelGGL((pd_gemm_dma_kernel<EPI, ALN, WM, WN>), dim3(((M + 64 * WM - 1) / (64 * WM)) * (Nout / (64 * WN))), dim3(256),
                        (size_t)2 * (64 * WM + 64 * WN) * 32 * sizeof(float), s, g);
 }
@@ -463,7 +472,7 @@ static inline void pd_gemm_dma(const float *A, int lda, const float *W, int K, c
 template <int EPI, bool ALN = false, int WM = 1, int WN = 1>
 static inline void pd_gemm_stream(const float *A, int lda, const float *W, int K, const float *bias, float *C, int M, int Nout, hipStream_t s,
                                   const float2 *ln_stats = nullptr) {
-    PdStreamArgs g{A, W, bias, C, M, Nout, K, lda, K, ln_stats, nullptr};
+    PdStreamArgs g{A, W, bias, C, M, Nout, K, lda, K, ln_stats, nullptr, nullptr};
     const size_t lds = (size_t)2 * (64 * WM + 64 * WN) * PD_STREAM_LR * sizeof(float);
     hipLaunchKernelGGL((pd_gemm_stream_kernel<EPI, WM, WN, ALN>), dim3(((M + 64 * WM - 1) / (64 * WM)) * (Nout / (64 * WN))), dim3(256), lds, s, g);
 }

@@ -265,6 +265,11 @@ struct pd_engine {
     // schedule tables (host copies; kernels take the per-step scalars by value)
     std::vector<float> c_recip, c_recipm1, coef1, coef2, logvar;
     int pred_x0 = 0;                      // pd_weights.reserved & PD_WEIGHTS_PRED_X0
+    // one timestep per sequence (pd_denoise_step_t, pd_p_losses): the kernels index device copies of the tables by the row's own t
+    float *d_c_recip = nullptr, *d_c_recipm1 = nullptr;   // [timesteps] each
+    float *d_q_a = nullptr, *d_q_b = nullptr;             // [timesteps] sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod (pd_engine_set_q_tables)
+    int *d_t_row = nullptr;                               // [max_B x max_N] timestep of every token row, clamped into [0, timesteps)
+    float *d_xt = nullptr;                                // [max_B, max_N, 9] x_t of pd_p_losses when the caller does not ask for it
     // GGS
     std::vector<PdSeqHost> seqs;
     PdSeqDesc *d_seqs = nullptr;         // [max_B] device copy of the descriptors
@@ -311,9 +316,24 @@ void pd_denoiser_destroy(pd_engine *eng);
 bool pd_denoiser_has_streamed_path(const pd_engine *eng);   // created with max_B x max_N >= PD_STREAM_MIN_ROWS token rows
 bool pd_denoiser_weights_non_finite(const pd_engine *eng);  // the fp16-plane scales were refused because an encoder weight / bias is inf or NaN
 int pd_denoiser_build_split(pd_engine *eng, int mode);    // 1: bf16 planes (fast mode), 2: fp16 planes with static scales
-// eps_out / mean_out / x_next_out may each be null. noise null => 0.
+// One timestep per sequence (pd_denoise_step_t, pd_p_losses): _first and the tail read t_row[m] in place of the launch's `t`, and the tail
+// writes the outputs of p_losses in place of the posterior update (mean_out / noise / x_next_out must be null; eps_out = the model output,
+// x0_out = x_0_pred).
+struct PdTSeq {
+    const int *t_row;          // [B x N] DEVICE, every entry inside [0, timesteps) (pd_t_rows_kernel / pd_q_sample_kernel)
+    const float *target;       // [B, N, 9] the loss target, null without loss_out
+    float *loss_out;           // [B, N, 9] or null
+    int loss_type;             // 1 = l1, 2 = l2
+};
+// eps_out / mean_out / x_next_out may each be null. noise null => 0.  ts: null = the timestep t for every sequence.
 int pd_denoiser_launch(pd_engine *eng, const float *x, const float *z, int t, int B, int N, float *eps_out,
-                       float *mean_out, float *x0_out, const float *noise, float *x_next_out, hipStream_t s, bool z_prepared = false);
+                       float *mean_out, float *x0_out, const float *noise, float *x_next_out, hipStream_t s, bool z_prepared = false,
+                       const PdTSeq *ts = nullptr);
+// the pre-passes of the per-sequence entry points (pd_denoiser.hip): t_seq -> eng->d_t_row, checked; the second one with q_sample fused
+int pd_denoiser_t_rows(pd_engine *eng, const int64_t *t_seq, int B, int N, hipStream_t s);
+int pd_denoiser_q_sample(pd_engine *eng, const float *x_start, const float *noise, const int64_t *t_seq, int B, int N, float *xt, hipStream_t s);
+// pd_denoiser_first_t.hip: the streamed path's _first GEMM with the time piece as a per-row bias (ttab[t_row[m]])
+void pd_den_first_gemm_t(const PdDenoiserDev *d, const int *t_row, int M, hipStream_t s);
 // the step-invariant piece of _first for this z (once per sampling call; pd_denoiser_launch(..., z_prepared = true) then skips it)
 int pd_denoiser_prepare(pd_engine *eng, const float *z, int B, int N, hipStream_t s);
 
@@ -324,7 +344,7 @@ bool pd_denoiser_generic_shape_ok(const pd_weights *w, char *why, size_t why_len
 int pd_denoiser_generic_create(pd_engine *eng, const pd_weights *w);
 void pd_denoiser_generic_destroy(pd_engine *eng);
 int pd_denoiser_generic_launch(pd_engine *eng, const float *x, const float *z, int t, int B, int N, float *eps_out, float *mean_out,
-                               float *x0_out, const float *noise, float *x_next_out, hipStream_t s);
+                               float *x0_out, const float *noise, float *x_next_out, hipStream_t s, const PdTSeq *ts = nullptr);
 
 // pd_ggs.hip: the GGS kernels, their launch plan and launch
 int pd_ggs_init();

@@ -83,8 +83,8 @@ class Denoiser(nn.Module):
         steps = t.unique().tolist()
         if len(steps) == 1:
             return eng.denoise(x, z, int(steps[0]))
-        out = torch.empty_like(x, dtype=torch.float32)
-        for s in steps:                      # per-sequence timesteps: one launch group per distinct t
-            sel = (t == s).nonzero().flatten()
-            out[sel] = eng.denoise(x[sel], z[sel], int(s))
-        return out
+        if t.numel() != B:
+            raise ValueError(f"t must hold one timestep or one per sequence ({B}), got {t.numel()}")
+        if steps[0] < 0 or steps[-1] >= eng.timesteps:          # (the engine would clamp them and flag it asynchronously)
+            raise ValueError(f"timesteps must lie in [0, {eng.timesteps}), got {steps[0]} .. {steps[-1]}")
+        return eng.denoise_t(x, z, t)        # per-sequence timesteps (the training branch, gaussian_diffuser.py:331): one pass

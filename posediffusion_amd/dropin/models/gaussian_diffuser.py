@@ -1,10 +1,13 @@
-"""Drop-in `GaussianDiffusion` (pose_diffusion/models/gaussian_diffuser.py:75-306, sampling half).
+"""Drop-in `GaussianDiffusion` (pose_diffusion/models/gaussian_diffuser.py:75-341).
 
 Same constructor, same 13 persistent buffers (checkpoint keys `diffuser.betas` ...), same
 ``sample(shape, z, cond_fn=None, cond_start_step=0) -> (pose [B,N,9], process [T+1,B,N,9])``.
 The loop itself -- 100 denoiser evaluations, posterior updates and (when cond_fn is the shipped
 GGS partial) the 7000 guided iterations -- runs as one hipGraph replay of hand-written kernels.
-Training (`forward`/`p_losses`, :308-332) is out of scope and raises."""
+The training branch (`forward` / `p_losses`, :308-332) runs its FORWARD half on the engine, one pass of the denoiser for the whole
+batch of per-sequence timesteps: the diffusion loss of a checkpoint on a batch.  The returned tensors carry no grad (backward and the
+optimiser are out of scope), and the network is evaluated as under ``model.eval()``: the reference under ``model.train()`` applies
+dropout 0.1, which the engine does not reproduce."""
 import os
 from collections import namedtuple
 
@@ -143,9 +146,23 @@ class GaussianDiffusion(nn.Module):
     def sample(self, shape, z, cond_fn=None, cond_start_step=0):
         return self.p_sample_loop(shape, z=z, cond_fn=cond_fn, cond_start_step=cond_start_step)
 
-    # ---- training half: out of scope ---------------------------------------------------------
-    def p_losses(self, *a, **k):
-        raise NotImplementedError("training is out of scope of the MI355X sampling engine (SURVEY.md section 2.1)")
+    # ---- training branch, forward half (:308-332): q_sample, the denoiser and the loss as one pass on the engine ----------------------
+    @torch.no_grad()
+    def p_losses(self, x_start, t, z=None, noise=None):
+        """``{"loss", "noise", "x_0_pred", "x_t", "t"}`` as the reference returns them; loss elementwise (reduction "none").
+        Eval-mode forward, no grad (see the module docstring)."""
+        if z is None:
+            raise NotImplementedError("the denoiser cannot run unconditionally: p_losses needs the image features z")
+        if self.loss_type not in ("l1", "l2"):
+            raise ValueError(f"invalid loss type {self.loss_type}")
+        noise = torch.randn_like(x_start) if noise is None else noise              # :309
+        B, N, _ = x_start.shape
+        eng = host.get_engine(self.model, self, B, N)
+        out = eng.p_losses(x_start, z, t, noise, self.loss_type)
+        return {"loss": out["loss"], "noise": noise, "x_0_pred": out["x_0_pred"], "x_t": out["x_t"], "t": t}
 
-    def forward(self, *a, **k):
-        raise NotImplementedError("training is out of scope of the MI355X sampling engine (SURVEY.md section 2.1)")
+    def forward(self, pose, z=None, *args, **kwargs):
+        if z is None:
+            raise NotImplementedError("the denoiser cannot run unconditionally: forward needs the image features z")
+        t = torch.randint(0, self.num_timesteps, (len(pose),), device=pose.device).long()      # :330-331
+        return self.p_losses(pose, t, z=z, *args, **kwargs)

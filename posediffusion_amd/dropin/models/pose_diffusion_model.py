@@ -1,8 +1,10 @@
-"""Drop-in `PoseDiffusionModel` (pose_diffusion/models/pose_diffusion_model.py:35-142, inference branch).
+"""Drop-in `PoseDiffusionModel` (pose_diffusion/models/pose_diffusion_model.py:35-142).
 
 ``forward(image, gt_cameras=None, sequence_name=None, cond_fn=None, cond_start_step=0, training=True,
 batch_repeat=-1)`` keeps the reference signature; `training=False` returns
 ``{"pred_cameras": PerspectiveCameras(R, T, focal_length) in PyTorch3D NDC, "z": features}``.
+`training=True` (with ``gt_cameras``) follows :111-126: the diffusion results of ``GaussianDiffusion.forward`` on the encoded cameras plus
+``pred_cameras`` decoded from ``x_0_pred`` -- the forward half only: eval-mode network, no grad (dropin/models/gaussian_diffuser.py).
 Extension: ``z=`` accepts precomputed image features instead of ``image`` (skips the feature extractor)."""
 from typing import Dict, List, Optional
 
@@ -11,7 +13,7 @@ import torch.nn as nn
 
 from posediffusion_amd import host
 from posediffusion_amd.compat import instantiate
-from util.camera_transform import pose_encoding_to_camera
+from util.camera_transform import camera_to_pose_encoding, pose_encoding_to_camera
 
 
 class PoseDiffusionModel(nn.Module):
@@ -37,12 +39,25 @@ class PoseDiffusionModel(nn.Module):
 
     def forward(self, image: torch.Tensor = None, gt_cameras=None, sequence_name: Optional[List[str]] = None, cond_fn=None,
                 cond_start_step=0, training=True, batch_repeat=-1, z: Optional[torch.Tensor] = None):
-        if training:
-            raise NotImplementedError("training is out of scope of the MI355X sampling engine; call with training=False")
+        if training and gt_cameras is None:
+            raise NotImplementedError("the training branch needs ground-truth cameras (gt_cameras): it computes the diffusion loss of their "
+                                      "pose encoding; call with training=False to sample")
         if z is None:
             B, N = image.shape[0], image.shape[1]
             z = self.image_feature_extractor(image.reshape(B * N, *image.shape[2:])).reshape(B, N, -1)
         B, N, _ = z.shape
+        if training:                                                   # pose_diffusion_model.py:111-126
+            eng = host.get_engine(self.diffuser.model, self.diffuser, B * max(batch_repeat, 1), N)
+            pose_encoding = camera_to_pose_encoding(gt_cameras, pose_encoding_type=self.pose_encoding_type, engine=eng)
+            if batch_repeat > 0:
+                pose_encoding = pose_encoding.reshape(B * batch_repeat, -1, self.target_dim)
+                z = z.repeat(batch_repeat, 1, 1)
+            else:
+                pose_encoding = pose_encoding.reshape(B, -1, self.target_dim)
+            diffusion_results = self.diffuser(pose_encoding, z=z)
+            diffusion_results["pred_cameras"] = pose_encoding_to_camera(diffusion_results["x_0_pred"],
+                                                                        pose_encoding_type=self.pose_encoding_type, engine=eng)
+            return diffusion_results
         pose_encoding, _ = self.diffuser.sample(shape=[B, N, self.target_dim], z=z, cond_fn=cond_fn,
                                                 cond_start_step=cond_start_step)
         eng = host.get_engine(self.diffuser.model, self.diffuser, B, N)

@@ -1,4 +1,4 @@
-"""pose_encoding_to_camera (pose_diffusion/util/camera_transform.py:64-105) on the HIP engine."""
+"""pose_encoding_to_camera and camera_to_pose_encoding (pose_diffusion/util/camera_transform.py:64-129) on the HIP engine."""
 import torch
 
 from posediffusion_amd import _lib
@@ -17,3 +17,16 @@ def pose_encoding_to_camera(pose_encoding, pose_encoding_type="absT_quaR_logFL",
     if return_dict:
         return {"focal_length": f, "R": R, "T": T}
     return PerspectiveCameras(focal_length=f, R=R, T=T, device=R.device)
+
+
+@torch.no_grad()
+def camera_to_pose_encoding(camera, pose_encoding_type="absT_quaR_logFL", log_focal_length_bias=1.8, min_focal_length=0.1,
+                            max_focal_length=20, engine=None):
+    """[T | matrix_to_quaternion(R) | log(clamp(focal_length)) - bias] of ``camera`` (.R [.., 3, 3], .T [.., 3], .focal_length [.., 2]),
+    shape [n, 9] (camera_transform.py:108-129); the quaternion rule is current pytorch3d's (include/pd_engine.h pd_camera_to_pose)."""
+    if pose_encoding_type != "absT_quaR_logFL":
+        raise ValueError(f"Unknown pose encoding {pose_encoding_type}")           # camera_transform.py:126-127
+    if engine is None:
+        from posediffusion_amd.host import current_engine
+        engine = current_engine(camera.R.device)
+    return engine.camera_to_pose(camera.R, camera.T, camera.focal_length, log_focal_length_bias, min_focal_length, max_focal_length)

@@ -21,6 +21,10 @@ _TABLES = ("sqrt_recip_alphas_cumprod", "sqrt_recipm1_alphas_cumprod", "posterio
            "posterior_mean_coef2", "posterior_log_variance_clipped")
 
 
+_Q_TABLES = ("sqrt_alphas_cumprod", "sqrt_one_minus_alphas_cumprod")
+_LOSS_TYPES = {"l1": 1, "l2": 2}
+
+
 def make_ggs_cfg(cfg: Optional[Dict] = None, **over) -> _lib.pd_ggs_cfg:
     d = dict(GGS_DEFAULTS)
     for src in (cfg or {}), over:
@@ -97,6 +101,10 @@ class PoseEngine:
         with torch.cuda.device(self.device):
             torch.cuda.synchronize()
             _lib.check(self.lib.pd_engine_create(C.byref(w), self.max_B, self.max_N, C.byref(self._h)), "pd_engine_create")
+            # q_sample's two tables (gaussian_diffuser.py:164-165), needed by p_losses only; copied by the engine
+            self.has_q_tables = all(n in tables for n in _Q_TABLES)
+            if self.has_q_tables:
+                _lib.check(self.lib.pd_engine_set_q_tables(self._h, *(dev(tables[n]) for n in _Q_TABLES)), "pd_engine_set_q_tables")
         del keep
 
     # ---------------------------------------------------------------- lifecycle
@@ -135,6 +143,37 @@ class PoseEngine:
         out = torch.empty_like(x)
         _lib.check(self.lib.pd_denoise_step(self._h, x.data_ptr(), z.data_ptr(), int(t), B, N, out.data_ptr(),
                                             self._stream()), "pd_denoise_step")
+        return out
+
+    def _t_seq(self, t, B: int) -> torch.Tensor:
+        t = torch.as_tensor(t).reshape(-1).to(device=self.device, dtype=torch.int64).contiguous()
+        if t.numel() != B:
+            raise ValueError(f"expected one timestep per sequence ({B}), got {t.numel()}")
+        return t
+
+    def denoise_t(self, x: torch.Tensor, z: torch.Tensor, t: torch.Tensor) -> torch.Tensor:
+        """Denoiser.forward(x, t [B], z) with one timestep per sequence, in one pass (pd_denoise_step_t).  ``t`` stays on the device:
+        an entry outside [0, timesteps) is clamped there and reported by ``check_async()``.  Forward only, no grad."""
+        B, N, _ = x.shape
+        x, z, t = self._f32(x, (B, N, 9)), self._f32(z, (B, N, self.z_dim)), self._t_seq(t, B)
+        out = torch.empty_like(x)
+        _lib.check(self.lib.pd_denoise_step_t(self._h, x.data_ptr(), z.data_ptr(), t.data_ptr(), B, N, out.data_ptr(),
+                                              self._stream()), "pd_denoise_step_t")
+        return out
+
+    def p_losses(self, x_start: torch.Tensor, z: torch.Tensor, t: torch.Tensor, noise: torch.Tensor, loss_type: str = "l1"):
+        """The forward half of GaussianDiffusion.p_losses (gaussian_diffuser.py:308-327) in one pass of the denoiser: returns
+        ``{"loss", "x_0_pred", "x_t", "model_out"}``, each [B, N, 9].  The loss is elementwise (reduction "none") against the noise
+        (pred_noise) or x_start (pred_x0).  The network runs as under ``model.eval()`` (no dropout) and nothing carries a gradient."""
+        if loss_type not in _LOSS_TYPES:
+            raise ValueError(f"invalid loss type {loss_type}")                 # gaussian_diffuser.py:334-341
+        B, N, _ = x_start.shape
+        x_start, z = self._f32(x_start, (B, N, 9)), self._f32(z, (B, N, self.z_dim))
+        noise, t = self._f32(noise, (B, N, 9)), self._t_seq(t, B)
+        out = {k: torch.empty_like(x_start) for k in ("loss", "x_0_pred", "x_t", "model_out")}
+        _lib.check(self.lib.pd_p_losses(self._h, x_start.data_ptr(), z.data_ptr(), t.data_ptr(), noise.data_ptr(), B, N,
+                                        _LOSS_TYPES[loss_type], out["loss"].data_ptr(), out["x_0_pred"].data_ptr(), out["x_t"].data_ptr(),
+                                        out["model_out"].data_ptr(), self._stream()), "pd_p_losses")
         return out
 
     def p_mean(self, x: torch.Tensor, z: torch.Tensor, t: int) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -294,6 +333,21 @@ class PoseEngine:
                                                  float(log_focal_length_bias), float(min_focal_length), float(max_focal_length),
                                                  self._stream()), "pd_pose_to_camera_ex")
         return R, T, F
+
+    def camera_to_pose(self, R: torch.Tensor, T: torch.Tensor, focal_length: torch.Tensor, log_focal_length_bias: float = 1.8,
+                       min_focal_length: float = 0.1, max_focal_length: float = 20.0) -> torch.Tensor:
+        """camera_to_pose_encoding (camera_transform.py:108-129): R [n,3,3], T [n,3], focal_length [n,2] -> [n,9] =
+        [T | matrix_to_quaternion(R), real part first and non-negative | log(clamp(focal)) - bias] (pd_camera_to_pose)."""
+        R = self._f32(R).reshape(-1, 9)
+        n = R.shape[0]
+        T, F = self._f32(T).reshape(-1, 3), self._f32(focal_length).reshape(-1, 2)
+        if T.shape[0] != n or F.shape[0] != n:
+            raise ValueError(f"R, T and focal_length must describe the same cameras (got {n}, {T.shape[0]}, {F.shape[0]})")
+        enc = torch.empty(n, 9, device=self.device)
+        _lib.check(self.lib.pd_camera_to_pose(R.data_ptr(), T.data_ptr(), F.data_ptr(), n, float(log_focal_length_bias),
+                                              float(min_focal_length), float(max_focal_length), enc.data_ptr(), self._stream()),
+                   "pd_camera_to_pose")
+        return enc
 
     def lane_tables(self, seq: int = 0):
         """(lane items, waves, base item length, [steps per wave]) of match slot ``seq`` as the device holds them (pd_debug_lane_tables)."""
