@@ -1,1 +1,1 @@
-"""placeholder package (opencv_from_cameras_projection is fused into csrc/pd_ggs.hip)"""
+"""placeholder package (opencv_from_cameras_projection is fused into the GGS kernels' pose decode, csrc/pd_ggs_dev.h)"""

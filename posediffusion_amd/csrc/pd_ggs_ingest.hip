@@ -492,7 +492,7 @@ __global__ __launch_bounds__(256) void ingest_lane_stream_kernel(IngestArgs A) {
     }
 }
 
-// ---- kernel 4: pair-interleave the full 128-match groups of every item (the layout pd_ggs.hip's packed steps read) -----------
+// ---- kernel 4: pair-interleave the full 128-match groups of every item (the layout pd_ggs_sampson.h's packed steps read) -----------
 // one wave per work item; a lane rewrites exactly the two elements it read (group[lane], group[64 + lane]): in place, no hazards
 __global__ __launch_bounds__(64) void ingest_interleave_kernel(IngestArgs A) {
     const IngestSeq S = A.s[blockIdx.y];

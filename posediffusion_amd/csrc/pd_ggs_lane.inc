@@ -1,4 +1,5 @@
-// pd_ggs_lane.inc -- the lane-per-item GGS kernel (textually included by pd_ggs.hip after the helpers it shares with the other kernels).
+// pd_ggs_lane.inc -- the lane-per-item GGS kernel (textually included by pd_ggs.hip after the helpers it shares with the other kernels:
+// pd_ggs_dev.h, pd_ggs_sampson.h; its LDS image, carve_lane and lane_lds_bytes, is in pd_ggs_lds.h).
 //
 // Why another mapping (profiles/round3_valu_probe2.txt, round3_stream_probe.txt).  The wave-per-item kernel at one workgroup per
 // sequence sits on two walls at once: (1) a gfx950 SIMD retires one packed-fp32 VALU instruction every ~2.0 ns whatever the number
@@ -42,34 +43,6 @@
                             //   fabric behind the L2s (profiles/round6_zigzag_probe.txt: the ring pattern alone 6.6 -> 7.8 TB/s).  Every pass still sums every step
                             //   exactly once; the ORDER of a lane's sums alternates with the pass parity (deterministic: results stay bitwise reproducible and
                             //   independent of slot and launch shape, but differ in rounding from a forward-only build)
-#define PD_LANE_FIXED_FLOATS (48 * PD_FR_STRIDE + 48 * 4 + 8 + 48 * 3 + 48 * 9 + 48 * 4 + 8 + 64 * PD_XS_STRIDE + 64 * PD_XS_STRIDE + 16 + PD_GGS_FAST_FRAMES * 48)
-__device__ __forceinline__ Lds carve_lane(float *base, int pinc_rows) {
-    Lds L;
-    L.Rc = base;
-    L.fl = L.Rc + 48 * PD_FR_STRIDE;
-    L.cam = L.fl + 48 * 4;
-    L.gT = L.cam + 8;
-    L.gR = L.gT + 48 * 3;
-    L.gA = L.gR + 48 * 9;
-    L.ctl = L.gA + 48 * 4;
-    L.xst = L.ctl + 8;
-    L.mst = L.xst + 64 * PD_XS_STRIDE;
-    L.psum = L.mst + 64 * PD_XS_STRIDE;                // [16] valid counts of the waves
-    L.W = L.psum + 16;                                 // [PD_GGS_FAST_FRAMES * 48] quaternion Jacobians (jac_all)
-    L.gq = L.gR;
-    L.pinc = L.W + PD_GGS_FAST_FRAMES * 48;            // 16-byte aligned (PD_LANE_FIXED_FLOATS % 4 == 0)
-    L.incoff = (int *)(L.pinc + pinc_rows * 16);       // [68]
-    L.item = (float *)(L.incoff + 68);                 // [PD_LANE_MAX_ITEMS][PD_LANE_ITEM_VALS]
-    L.itab = nullptr;
-    L.F = nullptr;
-    L.stage = base + ((((L.item + PD_LANE_MAX_ITEMS * PD_LANE_ITEM_VALS) - base) + 255) & ~255);   // the waves' rings, 1 KiB aligned
-    return L;
-}
-static size_t lane_lds_bytes(int pinc_rows) {
-    size_t b = ((size_t)PD_LANE_FIXED_FLOATS + (size_t)pinc_rows * 16 + 68 + (size_t)PD_LANE_MAX_ITEMS * PD_LANE_ITEM_VALS) * 4;
-    b = (b + 1023) & ~(size_t)1023;
-    return b + (size_t)PD_LANE_SLOTS * PD_LANE_WAVES * 2048;
-}
 
 // the match stream is read through GLOBAL-address-space pointers (a pointer that came out of a descriptor in memory is generic to the
 // compiler: flat loads, which count on the LDS counter too) with a wave-uniform base per step and the lane as a 32-bit offset

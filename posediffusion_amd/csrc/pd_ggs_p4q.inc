@@ -1,4 +1,4 @@
-// P4 of one GGS iteration for pd_ggs_kernel (textually included; the two-hop and the lane-per-item kernel keep pd_ggs_p4.inc): wave 0,
+// P4 of one GGS iteration for pd_ggs_kernel and pd_ggs_lane_kernel (textually included; the two-hop kernel keeps pd_ggs_p4.inc): wave 0,
 // lane = frame.  The backward phase already turned the per-frame sums into dL/dq (through the Jacobian an idle wave prepared, jac_all)
 // and the dL/dA partials arrive as one float4 per row wave, so what is left here is the short tail of GGS_optimize
 // (geometry_guided_sampling.py:104-122): totals, early exit, the focal-length chain, masked-norm clip, momentum SGD, decode.

@@ -127,7 +127,7 @@ struct PdGgsParams {
 };
 
 // launch shape of one GGS launch (pd_ggs_plan): everything a captured graph node bakes in besides its arguments
-// Match table layout inside a work item: every FULL group of 128 matches is stored pair-interleaved (pd_ggs.hip MatchRegs) -- this is the
+// Match table layout inside a work item: every FULL group of 128 matches is stored pair-interleaved (pd_ggs_sampson.h MatchRegs) -- this is the
 // transform of one lane's two matches A = group[lane], B = group[64 + lane], applied by both table builders (host: pd_ggs_set_matches;
 // device: ingest_interleave_kernel)
 __host__ __device__ inline void pd_interleave_pair(const float4 a, const float4 b, float4 &q0, float4 &q1) {
@@ -346,7 +346,7 @@ void pd_denoiser_generic_destroy(pd_engine *eng);
 int pd_denoiser_generic_launch(pd_engine *eng, const float *x, const float *z, int t, int B, int N, float *eps_out, float *mean_out,
                                float *x0_out, const float *noise, float *x_next_out, hipStream_t s, const PdTSeq *ts = nullptr);
 
-// pd_ggs.hip: the GGS kernels, their launch plan and launch
+// pd_ggs.hip: the GGS kernels' translation unit (device code in pd_ggs_*.h / pd_ggs_lane.inc), their launch plan and launch
 int pd_ggs_init();
 int pd_ggs_plan(pd_engine *eng, int B, int N, const pd_ggs_cfg *cfg, PdGgsPlan *out);
 int pd_ggs_launch(pd_engine *eng, float *x, int B, int N, const PdGgsStage *stages, int n_stages,

@@ -151,7 +151,7 @@ def _all_sampson_fp32(x, pm):
 
 def test_sampson_threshold_rule_around_sampson_max(engine, golden):
     """geometry_guided_sampling.py:170 keeps `sampson < sampson_max` on torch's IEEE quotient.  The engine decides on the
-    IEEE quotient too (csrc/pd_ggs.hip sampson_step2: fast 1-ulp pass, exact re-run of an item that has a match within
+    IEEE quotient too (csrc/pd_ggs_sampson.h sampson_step2: fast 1-ulp pass, exact re-run of an item that has a match within
     16 ulp of the threshold), but ITS top / bottom differ from torch's by fp32 rounding order (F is built in another
     order), so the documented rule is: the valid set equals the reference's except for matches whose Sampson value lies
     within the contract tolerance (1e-4 relative) of sampson_max.  Checked with sampson_max placed EXACTLY on oracle

@@ -225,7 +225,7 @@ def test_engine_picks_the_lane_kernel_where_a_sequence_gets_one_workgroup(seeded
 def test_xcd_local_exchange_equals_the_spread_one(seeded_diffuser):
     """Round 4: at more than one workgroup per sequence the block -> (sequence, workgroup) map keeps a sequence's workgroups on one XCD
     and, once the launch-time handshake on XCC_ID has confirmed it, the exchange stores are plain stores through the shared L2
-    (pd_ggs.hip, `xl`).  PD_GGS_CFG_XCHG_SPREAD restores round 3's map + agent-scope stores.  The exchange only transports the items' sums:
+    (pd_ggs_kernels.h, `xl`).  PD_GGS_CFG_XCHG_SPREAD restores round 3's map + agent-scope stores.  The exchange only transports the items' sums:
     the poses, iteration counts and statistics must agree bit for bit, for one sequence, for a count that is not a multiple of 8 (padded map)
     and for k in {3, 24}, over enough iterations that a stale line would show."""
     B, N = 11, 20

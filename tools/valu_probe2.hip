@@ -48,7 +48,7 @@
 #define BLK16_CND                                                                                                             \
     ICND(32) ICND(33) ICND(34) ICND(35) ICND(36) ICND(37) ICND(38) ICND(39) ICND(40) ICND(41) ICND(42) ICND(43) ICND(44)       \
         ICND(45) ICND(46) ICND(47)
-// the instruction mix of ONE packed two-match Sampson step as sampson_step2 (csrc/pd_ggs.hip) compiles: 28 v_pk_fma, 11 v_pk_mul,
+// the instruction mix of ONE packed two-match Sampson step as sampson_step2 (csrc/pd_ggs_sampson.h) compiles: 28 v_pk_fma, 11 v_pk_mul,
 // 4 v_pk_add, 2 v_rcp, 2 v_cmp, 2 v_cndmask, 1 v_min3 = 50 VALU, dependencies as independent as the real step's are after scheduling
 #define BLK_STEPMIX                                                                                                           \
     BLK_PKFMA                                                                                                                 \
