@@ -135,7 +135,12 @@ typedef struct pd_ggs_cfg {
 
 /* Build an engine on the current HIP device.  Replaces the module construction +
  * load_state_dict of demo.py:46,56-57 for the sampling path.  Synchronous.
- * max_B sequences x max_N frames bound every later call (workspaces are sized once). */
+ * max_B sequences x max_N frames bound every later call (workspaces are sized once).
+ * Two frame limits: the denoiser, the training-branch forward and UNGUIDED sampling take up to 256 frames (max_N in [1, 256]; above 64
+ * frames attention runs the key-tiled kernel of csrc/pd_attn_long.h); GGS takes up to 64.  On an engine created for more than 64
+ * frames every GGS call with 64 < N <= max_N -- pd_ggs_set_matches / _csr_async, pd_ggs_guide / _optimize / _loss_grad, pd_sample* with
+ * ggs != NULL and cond_start_step > 0 -- returns PD_ERR_UNSUPPORTED with a message naming the 64-frame GGS limit, before anything is
+ * launched or allocated; the engine stays usable, and GGS at N <= 64 works on it as on any other. */
 int pd_engine_create(const pd_weights *w, int max_B, int max_N, pd_engine **out);
 void pd_engine_destroy(pd_engine *eng);
 const char *pd_last_error(void);
@@ -145,7 +150,7 @@ const char *pd_version(void);
 /* ---- denoiser + DDPM (GaussianDiffusion.p_sample pieces) --------------------------------- */
 
 /* eps_out[B,N,9] = Denoiser.forward(x[B,N,9], t (same for all B), z[B,N,z_dim])
- * (models/denoiser.py:53-76).  x, z, eps_out DEVICE.
+ * (models/denoiser.py:53-76).  x, z, eps_out DEVICE.  N <= min(max_N, 256).
  * Cost note for the step-level entry points (pd_denoise_step, pd_p_mean): at >= 1 024 token rows `_first` is computed as a
  * step-invariant z piece + a per-step piece (models/denoiser.py:56-70: z does not change over the T steps).  pd_sample /
  * pd_sample_phase compute the z piece ONCE per call; the step-level API cannot know that z is unchanged and recomputes it on
@@ -172,7 +177,7 @@ int pd_p_finish(pd_engine *eng, const float *mean, const float *noise, int t, in
  * dropout 0.1, which the engine deliberately does not reproduce).
  * An entry of t_seq outside [0, timesteps) cannot be seen by the host without a synchronisation: the device clamps it into the
  * range (so no table is read out of bounds) and raises bit 3 of the asynchronous error word (pd_check_async_error).
- * Argument checks and limits are those of pd_denoise_step: N <= 64, B <= max_B, N <= max_N; default-shape and generic engines,
+ * Argument checks and limits are those of pd_denoise_step: N <= 256, B <= max_B, N <= max_N; default-shape and generic engines,
  * every PD_OPT_DENOISER_SPLIT mode.  Asynchronous on `stream`, no host synchronisation. */
 
 /* [timesteps] DEVICE fp32 each, copied (synchronously); needed by pd_p_losses only (gaussian_diffuser.py:164-165) */
@@ -281,6 +286,12 @@ int pd_ggs_loss_grad(pd_engine *eng, const float *x, int B, int N, int update_R,
  *        frames = 256 workgroups; a batch of 103 keeps the two launches; 2: always; 0: never = the two launches it replaces (QKV GEMM -> fp32
  *        QKV in memory -> attention).  Same arithmetic in the same order: bitwise the same results whatever the choice. */
 #define PD_OPT_DENOISER_FUSED_ATTN 5
+/*   PD_OPT_DENOISER_LONG_ATTN  0 (default): sequences of more than 64 frames run the key-tiled attention kernel (csrc/pd_attn_long.h: K and V
+ *        through LDS in tiles of 64 keys, exact two-pass softmax), shorter ones the kernels that hold K and V whole; 1: the tiled kernel for
+ *        every N (comparison / testing).  It applies to the two-launch form, so the fused in_proj + attention kernel is not chosen while it
+ *        is 1.  At N <= 64 the default-shape tiled kernel performs the operations of pd_attn_kernel / pd_attn_seq_kernel in their order:
+ *        bitwise the same results (the MFMA attention of the fp16-plane mode at N <= 32 sums in another order: rounding-level). */
+#define PD_OPT_DENOISER_LONG_ATTN 6
 int pd_engine_set_option(pd_engine *eng, int option, int value);
 /* Reads an option back.  PD_OPT_DENOISER_SPLIT: the mode in force (an engine created from weights that hold inf / NaN stays on 0 although
  * it is large enough for 2 -- the only downgrade pd_engine_create performs by itself; PD_OPT_WEIGHTS_NON_FINITE (read-only) then reads 1). */
@@ -293,7 +304,8 @@ int pd_engine_get_option(pd_engine *eng, int option, int *value_out);
  *          noise[1+k] = the randn_like of step t = T-1-k (:278); slots the reference never
  *          draws (t == 0, guided steps) are ignored.
  *   cond_start_step / ggs: if ggs != NULL, steps with t < cond_start_step run pd_ggs_guide on
- *          the model mean with noise = 0 (:270-276); ggs == NULL = unguided.
+ *          the model mean with noise = 0 (:270-276); ggs == NULL = unguided.  Unguided: N <= 256; guided: N <= 64
+ *          (PD_ERR_UNSUPPORTED above, on an engine created for more than 64 frames).
  *   pose_out    [B,N,9]       DEVICE
  *   process_out [T+1,B,N,9]   DEVICE, may be NULL
  *   stats_out   [cond_start_step,B,5,4] DEVICE, may be NULL (see pd_ggs_guide), ordered by

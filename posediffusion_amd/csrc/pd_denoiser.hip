@@ -11,8 +11,8 @@
 // reference's fp32 path to rounding-order differences only (SURVEY.md headline fact 5).
 //
 // This file is the host side: engine creation, the split-precision weights, and one step's launches.  The kernels are in the headers:
-//   pd_gemm_small.h (small batches), pd_gemm_stream.h / pd_gemm_split.h (large batches: exact / split precision), pd_attn.h and
-//   pd_qkv_attn.h (attention), pd_denoiser_kernels.h (embeddings, tail, probe); pd_denoiser_plan.h decides which of them a step launches.
+//   pd_gemm_small.h (small batches), pd_gemm_stream.h / pd_gemm_split.h (large batches: exact / split precision), pd_attn.h,
+//   pd_attn_long.h (more than 64 frames) and pd_qkv_attn.h (attention), pd_denoiser_kernels.h (embeddings, tail, probe); pd_denoiser_plan.h decides which of them a step launches.
 // One timestep per sequence (pd_denoise_step_t, pd_p_losses) changes _first and the tail only: den_first_small_t, den_first_streamed_t,
 // den_tail_t below; the streamed path's per-row-bias GEMM is instantiated in pd_denoiser_first_t.hip.
 #include "pd_denoiser_dev.h"
@@ -21,6 +21,7 @@
 #include "pd_qkv_attn.h"
 #include "pd_gemm_small.h"
 #include "pd_attn.h"
+#include "pd_attn_long.h"
 #include "pd_denoiser_kernels.h"
 #include "pd_denoiser_plan.h"
 
@@ -148,6 +149,9 @@ static int den_set_lds_attributes() {
     PD_TRY(pd_set_lds(pd_attn_seq_kernel<1>, attn_seq_lds(64)));
     PD_TRY(pd_set_lds(pd_attn_seq_kernel<2>, attn_seq_lds(64)));
     PD_TRY(pd_set_lds(pd_attn_mma_kernel<2>, attn_mma_lds(32)));
+    PD_TRY(pd_set_lds(pd_attn_long_kernel<0>, pd_attn_long_lds(PD_MAX_DENOISER_FRAMES, DH)));
+    PD_TRY(pd_set_lds(pd_attn_long_kernel<1>, pd_attn_long_lds(PD_MAX_DENOISER_FRAMES, DH)));
+    PD_TRY(pd_set_lds(pd_attn_long_kernel<2>, pd_attn_long_lds(PD_MAX_DENOISER_FRAMES, DH)));
     PD_TRY(pd_set_lds((pd_qkv_attn_kernel<0, PD_QA_DEEP_DEFAULT != 0>), 160 * 1024));
 #ifdef PD_DEV_KNOBS
     PD_TRY(pd_set_lds((pd_qkv_attn_kernel<0, PD_QA_DEEP_DEFAULT == 0>), 160 * 1024));
@@ -283,15 +287,28 @@ static void den_first_streamed_t(const PdDenoiserDev *d, const float *x, const i
     pd_den_first_gemm_t(d, t_row, M, s);
 }
 
-static void den_layer_small(const pd_engine *eng, const PdDenoiserDev *d, const PdLayerDev &L, GemmArgs &g, int B, int N, int MT, hipStream_t s) {
+// the key-tiled attention kernel (pd_attn_long.h): more than 64 frames on every path, or PD_OPT_DENOISER_LONG_ATTN = 1
+template <int SPLIT_OUT>
+static void den_attn_long(const PdDenoiserDev *d, int B, int N, float out_scale, hipStream_t s) {
+    static_assert(PD_MAX_DENOISER_FRAMES == PD_ATTN_LONG_TILE * PD_ATTN_LONG_MAX_TILES, "a lane holds one score per 64-key tile");
+    hipLaunchKernelGGL(pd_attn_long_kernel<SPLIT_OUT>, dim3(B * NH, (N + PD_ATTN_LONG_ROWS - 1) / PD_ATTN_LONG_ROWS), dim3(256), pd_attn_long_lds(N, DH), s,
+                       d->qkv, d->ctx, N, out_scale);
+}
+
+static void den_layer_small(const pd_engine *eng, const PdDenoiserDev *d, const PdLayerDev &L, GemmArgs &g, bool long_attn, int B, int N, int MT,
+                            hipStream_t s) {
     // x += MHA(LN1(x))
     g.A = d->h; g.bias = L.qkv_b; g.C = d->qkv; g.Nout = 3 * DM;
     launch_gemm<DM, 1, 0>(g, L.qkv_wp, MT, eng->gemm_wide_min_tiles, s);
+    if (long_attn) {
+        den_attn_long<0>(d, B, N, 1.0f, s);
+    } else {
 #ifdef PD_DEN_STAMPS
-    hipLaunchKernelGGL(pd_attn_kernel<false>, dim3(B * NH, (N + 3) / 4), dim3(256), attn_lds(N), s, d->qkv, d->ctx, N, next_stamp_slot());
+        hipLaunchKernelGGL(pd_attn_kernel<false>, dim3(B * NH, (N + 3) / 4), dim3(256), attn_lds(N), s, d->qkv, d->ctx, N, next_stamp_slot());
 #else
-    hipLaunchKernelGGL(pd_attn_kernel<false>, dim3(B * NH, (N + 3) / 4), dim3(256), attn_lds(N), s, d->qkv, d->ctx, N);
+        hipLaunchKernelGGL(pd_attn_kernel<false>, dim3(B * NH, (N + 3) / 4), dim3(256), attn_lds(N), s, d->qkv, d->ctx, N);
 #endif
+    }
     g.A = d->ctx; g.bias = L.out_b; g.C = d->h; g.Nout = DM;
     launch_gemm<DM, 0, 2>(g, L.out_wp, MT, eng->gemm_wide_min_tiles, s);
     // x += W2 relu(W1 LN2(x))
@@ -301,11 +318,12 @@ static void den_layer_small(const pd_engine *eng, const PdDenoiserDev *d, const 
     launch_gemm<DFF, 0, 2>(g, L.ff2_wp, MT, eng->gemm_wide_min_tiles, s);
 }
 // exact fp32: LayerNorm is fused into the A staging of the streamed GEMMs (statistics pre-pass; affine folded into the weights, as on the small path)
-static void den_layer_streamed(const PdDenoiserDev *d, const PdLayerDev &L, int B, int N, int M, hipStream_t s) {
+static void den_layer_streamed(const PdDenoiserDev *d, const PdLayerDev &L, bool long_attn, int B, int N, int M, hipStream_t s) {
     float2 *stats = (float2 *)d->hn;           // (mean, rstd) per token row; applied in the A staging of the next GEMM
     hipLaunchKernelGGL(pd_ln_stats_kernel<DM>, dim3((M + 3) / 4), dim3(256), 0, s, d->h, stats, M, 1e-5f);
     pd_gemm_dma<0, true>(d->h, DM, L.qkv_wf, DM, L.qkv_b, d->qkv, M, 3 * DM, s, stats);                // LayerNorm-1 at the fragment reads
-    hipLaunchKernelGGL(pd_attn_seq_kernel<0>, dim3(B * NH), dim3(256), attn_seq_lds(N), s, d->qkv, d->ctx, N, 1.0f);
+    if (long_attn) den_attn_long<0>(d, B, N, 1.0f, s);
+    else hipLaunchKernelGGL(pd_attn_seq_kernel<0>, dim3(B * NH), dim3(256), attn_seq_lds(N), s, d->qkv, d->ctx, N, 1.0f);
     pd_gemm_dma<2>(d->ctx, DM, L.out_wf, DM, L.out_b, d->h, M, DM, s);
     hipLaunchKernelGGL(pd_ln_stats_kernel<DM>, dim3((M + 3) / 4), dim3(256), 0, s, d->h, stats, M, 1e-5f);
     pd_gemm_dma<1, true>(d->h, DM, L.ff1_wf, DM, L.ff1_b, d->ff, M, DFF, s, stats);                     // LayerNorm-2 likewise
@@ -313,10 +331,11 @@ static void den_layer_streamed(const PdDenoiserDev *d, const PdLayerDev &L, int 
 }
 // fast mode: the four encoder GEMMs on the bf16 matrix pipe in split precision (pd_gemm_split.h); activations
 // between them as split words -- LayerNorm, attention and the FF1 epilogue write them in place of fp32
-static void den_layer_bf16(const PdDenoiserDev *d, const PdLayerDev &L, int B, int N, int M, hipStream_t s) {
+static void den_layer_bf16(const PdDenoiserDev *d, const PdLayerDev &L, bool long_attn, int B, int N, int M, hipStream_t s) {
     hipLaunchKernelGGL((pd_ln_rows_kernel<DM, 1>), dim3((M + 3) / 4), dim3(256), 0, s, d->h, d->hn, M, 1e-5f, 1.0f);
     pd_gemm_split<0, 1, 2>((const unsigned *)d->hn, DM, L.qkv_ws, DM, L.qkv_b, d->qkv, M, 3 * DM, s);
-    hipLaunchKernelGGL(pd_attn_seq_kernel<1>, dim3(B * NH), dim3(256), attn_seq_lds(N), s, d->qkv, d->ctx, N, 1.0f);
+    if (long_attn) den_attn_long<1>(d, B, N, 1.0f, s);
+    else hipLaunchKernelGGL(pd_attn_seq_kernel<1>, dim3(B * NH), dim3(256), attn_seq_lds(N), s, d->qkv, d->ctx, N, 1.0f);
     pd_gemm_split<2, 1, 1>((const unsigned *)d->ctx, DM, L.out_ws, DM, L.out_b, d->h, M, DM, s);
     hipLaunchKernelGGL((pd_ln_rows_kernel<DM, 1>), dim3((M + 3) / 4), dim3(256), 0, s, d->h, d->hn, M, 1e-5f, 1.0f);
     pd_gemm_split<4, 1, 2>((const unsigned *)d->hn, DM, L.ff1_ws, DM, L.ff1_b, d->ff, M, DFF, s);
@@ -347,7 +366,8 @@ static void den_layer_f16(const PdDenoiserDev *d, const PdLayerDev &L, const PdD
         pd_qkv_attn((const unsigned *)d->hn, L.qkv_wh, L.qkv_b, (unsigned *)d->ctx, B, N, L.qkv_cs, L.ctx_scale, s);
     } else {
         den_gemm_f16<0>(p.strip & 1 ? 2 : 0, d->hn, DM, L.qkv_wh, L.qkv_b, d->qkv, M, 3 * DM, s, L.qkv_cs);
-        if (p.attn_mma) hipLaunchKernelGGL(pd_attn_mma_kernel<2>, dim3(B * NH), dim3(256), attn_mma_lds(N), s, d->qkv, d->ctx, N, L.ctx_scale);
+        if (p.long_attn) den_attn_long<2>(d, B, N, L.ctx_scale, s);
+        else if (p.attn_mma) hipLaunchKernelGGL(pd_attn_mma_kernel<2>, dim3(B * NH), dim3(256), attn_mma_lds(N), s, d->qkv, d->ctx, N, L.ctx_scale);
         else hipLaunchKernelGGL(pd_attn_seq_kernel<2>, dim3(B * NH), dim3(256), attn_seq_lds(N), s, d->qkv, d->ctx, N, L.ctx_scale);
     }
     den_gemm_f16<2>(p.strip & 2 ? p.rt_res : 0, d->ctx, DM, L.out_wh, L.out_b, d->h, M, DM, s, L.out_cs);
@@ -407,9 +427,9 @@ int pd_denoiser_launch(pd_engine *eng, const float *x, const float *z, int t, in
                        float *mean_out, float *x0_out, const float *noise, float *x_next_out, hipStream_t s, bool z_prepared, const PdTSeq *ts) {
     if (eng->gden) return pd_denoiser_generic_launch(eng, x, z, t, B, N, eps_out, mean_out, x0_out, noise, x_next_out, s, ts);
     PdDenoiserDev *d = eng->den;
-    if (!x || !z || B <= 0 || N <= 0 || B > eng->max_B || N > eng->max_N || N > 64 || t < 0 || t >= d->timesteps) {
-        pd_set_error("denoiser: invalid arguments (B=%d N=%d t=%d; max_B=%d max_N=%d, N <= 64, 0 <= t < %d)", B, N, t,
-                     eng->max_B, eng->max_N, d->timesteps);
+    if (!x || !z || B <= 0 || N <= 0 || B > eng->max_B || N > eng->max_N || N > PD_MAX_DENOISER_FRAMES || t < 0 || t >= d->timesteps) {
+        pd_set_error("denoiser: invalid arguments (B=%d N=%d t=%d; max_B=%d max_N=%d, N <= %d, 0 <= t < %d)", B, N, t,
+                     eng->max_B, eng->max_N, PD_MAX_DENOISER_FRAMES, d->timesteps);
         return PD_ERR_INVALID_ARG;
     }
     if (!z_prepared) {
@@ -418,7 +438,7 @@ int pd_denoiser_launch(pd_engine *eng, const float *x, const float *z, int t, in
     }
     static const int knob_strip = pd_dev_knob("PD_DEN_STRIP", 15), knob_attn_mma = pd_dev_knob("PD_DEN_ATTN_MMA", 1);     // development A / B
     const PdDenStepPlan p = pd_den_step_plan(B, N, eng->den_split, eng->den_fused_attn, eng->num_cus, d->hn != nullptr, d->split_ready,
-                                             d->split_h_ready, knob_strip, knob_attn_mma);
+                                             d->split_h_ready, knob_strip, knob_attn_mma, eng->den_long_attn);
     const bool small = p.path == PD_DEN_SMALL;
     const int M = p.M;
     GemmArgs g;                       // the small path's launches share it
@@ -431,9 +451,9 @@ int pd_denoiser_launch(pd_engine *eng, const float *x, const float *z, int t, in
     for (int l = 0; l < d->num_layers; ++l) {
         const PdLayerDev &L = d->layers[l];
         switch (p.path) {
-        case PD_DEN_SMALL: den_layer_small(eng, d, L, g, B, N, p.MT, s); break;
-        case PD_DEN_STREAMED: den_layer_streamed(d, L, B, N, M, s); break;
-        case PD_DEN_BF16_PLANES: den_layer_bf16(d, L, B, N, M, s); break;
+        case PD_DEN_SMALL: den_layer_small(eng, d, L, g, p.long_attn, B, N, p.MT, s); break;
+        case PD_DEN_STREAMED: den_layer_streamed(d, L, p.long_attn, B, N, M, s); break;
+        case PD_DEN_BF16_PLANES: den_layer_bf16(d, L, p.long_attn, B, N, M, s); break;
         case PD_DEN_F16_PLANES: den_layer_f16(d, L, p, B, N, s); break;
         }
     }

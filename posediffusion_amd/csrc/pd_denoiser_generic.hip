@@ -17,11 +17,13 @@
 //   encoder      pre-norm : h += out(attn(LN1(h)));  h += W2 relu(W1 LN2(h))
 //                post-norm: h = LN1(h + out(attn(h))); h = LN2(h + W2 relu(W1 h))      (nn.TransformerEncoderLayer, eps 1e-5, ReLU)
 //                LayerNorm over the runtime width with its affine (pd_gen_ln_kernel); attention one workgroup per (sequence, head)
-//                for a runtime head dim and N <= 64 (pd_gen_attn_kernel).
+//                for a runtime head dim and N <= 64 (pd_gen_attn_kernel); above 64 frames, or under PD_OPT_DENOISER_LONG_ATTN = 1, the
+//                key-tiled pd_gen_attn_long_kernel (pd_attn_long.h), up to PD_MAX_DENOISER_FRAMES = 256.
 //   _last        _last.0 as a GEMM, then LayerNorm(hidden) -> ReLU -> Linear(hidden, 9) fused with the DDPM update (pd_gen_tail_kernel,
 //                the outputs of pd_tail_kernel).
 #include "pd_denoiser_dev.h"
 #include "pd_gemm_stream.h"
+#include "pd_attn_long.h"
 
 #include <math.h>
 #include <string.h>
@@ -329,6 +331,7 @@ int pd_denoiser_generic_create(pd_engine *eng, const pd_weights *w) {
     // bound (N = 64 frames, head dim 256: 133 120 bytes), never from this engine's shape, so a later engine cannot lower it below what an
     // earlier one launches with
     PD_TRY(pd_set_lds(pd_gen_attn_kernel, pd_gen_attn_lds(PD_MAX_FRAMES, PD_GEN_MAX_HD)));
+    PD_TRY(pd_set_lds(pd_gen_attn_long_kernel<0>, pd_attn_long_lds(PD_MAX_DENOISER_FRAMES, PD_GEN_MAX_HD)));
 
     PD_TRY(G->mem.alloc(&G->t_table, (size_t)w->timesteps * 128, true));
     PD_TRY(pd_time_table(w, G->t_table));
@@ -377,9 +380,9 @@ void pd_denoiser_generic_destroy(pd_engine *eng) {
 int pd_denoiser_generic_launch(pd_engine *eng, const float *x, const float *z, int t, int B, int N, float *eps_out, float *mean_out,
                                float *x0_out, const float *noise, float *x_next_out, hipStream_t s, const PdTSeq *ts) {
     PdGenericDen *G = eng->gden;
-    if (!x || !z || B <= 0 || N <= 0 || B > eng->max_B || N > eng->max_N || N > 64 || t < 0 || t >= G->timesteps) {
-        pd_set_error("denoiser: invalid arguments (B=%d N=%d t=%d; max_B=%d max_N=%d, N <= 64, 0 <= t < %d)", B, N, t, eng->max_B, eng->max_N,
-                     G->timesteps);
+    if (!x || !z || B <= 0 || N <= 0 || B > eng->max_B || N > eng->max_N || N > PD_MAX_DENOISER_FRAMES || t < 0 || t >= G->timesteps) {
+        pd_set_error("denoiser: invalid arguments (B=%d N=%d t=%d; max_B=%d max_N=%d, N <= %d, 0 <= t < %d)", B, N, t, eng->max_B, eng->max_N,
+                     PD_MAX_DENOISER_FRAMES, G->timesteps);
         return PD_ERR_INVALID_ARG;
     }
     const int M = B * N, Dp = G->Dp, Fp = G->Fp;
@@ -393,13 +396,22 @@ int pd_denoiser_generic_launch(pd_engine *eng, const float *x, const float *z, i
     pd_gemm_dma<0>(G->emb, G->Kfp, G->first_w, G->Kfp, G->first_b, G->h, M, Dp, s);
     const float scale = 1.0f / sqrtf((float)G->hd);
     const size_t attn_lds = pd_gen_attn_lds(N, G->hd);
+    // more than 64 frames (or PD_OPT_DENOISER_LONG_ATTN = 1): K and V through LDS in tiles of 64 keys
+    const bool long_attn = N > PD_MAX_FRAMES || eng->den_long_attn;
+    const auto attention = [&]() {
+        if (long_attn)
+            hipLaunchKernelGGL(pd_gen_attn_long_kernel<0>, dim3(B * G->nhead, (N + PD_ATTN_LONG_ROWS - 1) / PD_ATTN_LONG_ROWS), dim3(256),
+                               pd_attn_long_lds(N, G->hd), s, G->qkv, G->ctx, N, G->nhead, G->hd, Dp, scale);
+        else
+            hipLaunchKernelGGL(pd_gen_attn_kernel, dim3(B * G->nhead), dim3(PD_GEN_ATTN_THREADS), attn_lds, s, G->qkv, G->ctx, N, G->nhead, G->hd, Dp, scale);
+    };
     for (int l = 0; l < G->layers; ++l) {
         const PdGenLayer &L = G->L[l];
         if (!G->post_norm) {
             // h += out_proj(attn(LN1(h)));  h += W2 relu(W1 LN2(h))
             hipLaunchKernelGGL(pd_gen_ln_kernel, dim3(rows_blocks), dim3(256), 0, s, G->h, G->hn, L.norm1_w, L.norm1_b, M, G->d, Dp);
             pd_gemm_dma<0>(G->hn, Dp, L.qkv_w, Dp, L.qkv_b, G->qkv, M, 3 * Dp, s);
-            hipLaunchKernelGGL(pd_gen_attn_kernel, dim3(B * G->nhead), dim3(PD_GEN_ATTN_THREADS), attn_lds, s, G->qkv, G->ctx, N, G->nhead, G->hd, Dp, scale);
+            attention();
             PD_HIP_CHECK(hipGetLastError());      // the one launch whose dynamic LDS depends on the call's shape: its status, not a later one's
             pd_gemm_dma<2>(G->ctx, Dp, L.out_w, Dp, L.out_b, G->h, M, Dp, s);
             hipLaunchKernelGGL(pd_gen_ln_kernel, dim3(rows_blocks), dim3(256), 0, s, G->h, G->hn, L.norm2_w, L.norm2_b, M, G->d, Dp);
@@ -408,7 +420,7 @@ int pd_denoiser_generic_launch(pd_engine *eng, const float *x, const float *z, i
         } else {
             // h = LN1(h + out_proj(attn(h)));  h = LN2(h + W2 relu(W1 h))
             pd_gemm_dma<0>(G->h, Dp, L.qkv_w, Dp, L.qkv_b, G->qkv, M, 3 * Dp, s);
-            hipLaunchKernelGGL(pd_gen_attn_kernel, dim3(B * G->nhead), dim3(PD_GEN_ATTN_THREADS), attn_lds, s, G->qkv, G->ctx, N, G->nhead, G->hd, Dp, scale);
+            attention();
             PD_HIP_CHECK(hipGetLastError());
             pd_gemm_dma<2>(G->ctx, Dp, L.out_w, Dp, L.out_b, G->h, M, Dp, s);
             hipLaunchKernelGGL(pd_gen_ln_kernel, dim3(rows_blocks), dim3(256), 0, s, G->h, G->h, L.norm1_w, L.norm1_b, M, G->d, Dp);

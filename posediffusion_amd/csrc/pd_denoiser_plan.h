@@ -29,20 +29,24 @@ enum PdDenPath {
 struct PdDenStepPlan {
     PdDenPath path;
     int M, MT;             // token rows; 32-row tiles of the small-batch GEMMs
+    bool long_attn;        // every path: the key-tiled pd_attn_long_kernel (pd_attn_long.h) in place of the path's attention kernel -- above 64
+                           //   frames always, below on request (PD_OPT_DENOISER_LONG_ATTN = 1: bitwise the kernel it replaces, except pd_attn_mma_kernel)
     // PD_DEN_F16_PLANES only (zero on the other paths)
     bool fused_attn;       // in_proj + attention as ONE kernel (pd_qkv_attn.h), else the QKV GEMM and an attention kernel
-    bool attn_mma;         // the attention kernel of the two-launch form: pd_attn_mma_kernel, else pd_attn_seq_kernel
+    bool attn_mma;         // the attention kernel of the two-launch form: pd_attn_mma_kernel, else pd_attn_seq_kernel (or the long kernel, above)
     int rt_res, rt_ff1;    // 32-row tiles per workgroup (1, 2 or 3) of the strip GEMMs: out-projection and FF2 (512 wide, residual epilogue); FF1
     int strip;             // PD_DEN_STRIP: bit mask {QKV, out, FF1, FF2} of the GEMMs on the strip kernel; the others run pd_gemm_split
 };
 
 // split / fused_attn: PD_OPT_DENOISER_SPLIT / PD_OPT_DENOISER_FUSED_ATTN; has_streamed: the engine was created for >= PD_STREAM_MIN_ROWS token
-// rows; split_ready / split_h_ready: the bf16 / fp16 planes are built; knob_*: the development knobs PD_DEN_STRIP and PD_DEN_ATTN_MMA
+// rows; split_ready / split_h_ready: the bf16 / fp16 planes are built; knob_*: the development knobs PD_DEN_STRIP and PD_DEN_ATTN_MMA;
+// long_attn: PD_OPT_DENOISER_LONG_ATTN
 static inline PdDenStepPlan pd_den_step_plan(int B, int N, int split, int fused_attn, int num_cus, bool has_streamed, bool split_ready,
-                                             bool split_h_ready, int knob_strip, int knob_attn_mma) {
+                                             bool split_h_ready, int knob_strip, int knob_attn_mma, int long_attn = 0) {
     PdDenStepPlan p = {};
     p.M = B * N;
     p.MT = (p.M + 31) / 32;
+    p.long_attn = N > 64 || long_attn != 0;
     // >= 1024 token rows (52 sequences of 20 frames): the encoder GEMMs are large enough for 64 x 64 tiles streamed through LDS
     // (pd_gemm_stream.h; same sums in another order than the 32-row split-K tiles of the small path, i.e. rounding-level differences
     // between small and large batches)
@@ -56,8 +60,8 @@ static inline PdDenStepPlan pd_den_step_plan(int B, int N, int split, int fused_
     // fill the chip's rounds (256 sequences = 256 workgroups: -76 us per step), not at 103 sequences (104 workgroups: +2 %)
     const int qa_wgs = pd_qkv_attn_wgs(B, N);
     const bool qa_fills = 4 * qa_wgs >= 3 * ((qa_wgs + cus - 1) / cus) * cus;
-    p.fused_attn = qa_wgs > 0 && (fused_attn == 1 ? qa_fills : fused_attn == 2);
-    p.attn_mma = N <= 32 && knob_attn_mma;
+    p.fused_attn = qa_wgs > 0 && !p.long_attn && (fused_attn == 1 ? qa_fills : fused_attn == 2);   // (qa_wgs is 0 above 32 frames)
+    p.attn_mma = N <= 32 && knob_attn_mma && !p.long_attn;
     // 512-wide outputs: 96-row tiles where 64-row tiles would give the busiest CUs two tiles and most CUs one (5 120 rows: 320 tiles on 256 CUs ->
     // 216 tiles of 1.5 x the work: the launch is as long as its busiest CU).  Same sums in the same order: bitwise the same C.
     const bool rt3 = PD_STRIP_RT3 && (((p.M + 63) / 64) * (DM / 128)) > cus && (((p.M + 95) / 96) * (DM / 128)) <= cus;

@@ -108,6 +108,7 @@ int pd_ggs_init() {
 
 // pd_ggs_plan, part 1: the arguments, and that every slot of the launch holds tables for N frames; returns the most work items of a slot
 static int plan_check_slots(pd_engine *eng, int B, int N, const pd_ggs_cfg *cfg, PdGgsPlan *out, int &max_items) {
+    PD_TRY(pd_ggs_frames_unsupported(eng, N, "pd_ggs"));       // an engine for more than 64 frames (the denoiser's limit is 256): a clean refusal
     if (!eng || !cfg || !out || B <= 0 || B > eng->max_B || N <= 0 || N > eng->max_N || N > PD_MAX_FRAMES) {
         pd_set_error("pd_ggs: invalid arguments (B=%d N=%d)", B, N);
         return PD_ERR_INVALID_ARG;

@@ -525,6 +525,7 @@ extern "C" int pd_ggs_set_matches_csr_async(pd_engine *eng, int seq_first, int n
         return PD_ERR_INVALID_ARG;
     }
     const int N = n_frames;
+    PD_TRY(pd_ggs_frames_unsupported(eng, N, "pd_ggs_set_matches_csr_async"));
     if (N <= 0 || N > PD_MAX_FRAMES || N > eng->max_N || height <= 0 || width <= 0) {
         pd_set_error("pd_ggs_set_matches_csr_async: invalid n_frames=%d (<= %d) or image size %dx%d", N, std::min(PD_MAX_FRAMES, eng->max_N),
                      height, width);

@@ -303,6 +303,7 @@ extern "C" int pd_ggs_set_matches(pd_engine *eng, int seq, const double *kp1, co
         pd_set_error("pd_ggs_set_matches: bad engine or sequence slot %d", seq);
         return PD_ERR_INVALID_ARG;
     }
+    if (M != 0) PD_TRY(pd_ggs_frames_unsupported(eng, n_frames, "pd_ggs_set_matches"));   // (M == 0 clears the slot whatever n_frames says)
     PD_HIP_CHECK(hipSetDevice(eng->device));
     // nothing of THIS engine in flight may still read the old tables; other engines (other batches of a pipeline) keep
     // running: no device-wide synchronisation here, and the blob is re-used when the new tables fit

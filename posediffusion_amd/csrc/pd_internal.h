@@ -11,7 +11,8 @@
 #include "../../include/pd_engine.h"
 
 #define PD_WAVE 64
-#define PD_MAX_FRAMES 64          // one wavefront lane per frame in the GGS update phase
+#define PD_MAX_FRAMES 64          // GGS: one wavefront lane per frame in the update phase
+#define PD_MAX_DENOISER_FRAMES 256   // the denoiser and unguided sampling: four 64-key tiles of pd_attn_long_kernel (pd_attn_long.h)
 #define PD_GGS_THREADS 512        // 8 waves per GGS workgroup
 #define PD_GGS_WAVES (PD_GGS_THREADS / PD_WAVE)
 #define PD_GGS_PINC_ROWS (2 * PD_GGS_THREADS)   // pair backward results in LDS: both sides of one chunk of PD_GGS_THREADS pairs
@@ -278,6 +279,7 @@ struct pd_engine {
     unsigned int *d_err = nullptr;       // [0] async error word; [2..] debug phase counters
     int ggs_prof_on = 0;
     int den_fused_attn = 1;          // PD_OPT_DENOISER_FUSED_ATTN: in the fp16-plane mode, in_proj + attention as one kernel with Q / K / V in LDS (N <= 32)
+    int den_long_attn = 0;           // PD_OPT_DENOISER_LONG_ATTN: 1 = the key-tiled attention kernel (pd_attn_long.h) for every N, not only above 64 frames
     int den_split = 0;               // PD_OPT_DENOISER_SPLIT: encoder GEMMs of the large-batch path: 0 exact fp32, 1 bf16 planes, 2 fp16 planes (default there)
     int gemm_wide_min_tiles = 200;   // launch_gemm: 32-wide tiles when there are at least this many of them
     float *d_stats_scratch = nullptr;
@@ -356,6 +358,8 @@ int pd_ggs_launch(pd_engine *eng, float *x, int B, int N, const PdGgsStage *stag
 int pd_build_seq_tables(const double *kp1, const double *kp2, const int64_t *i12, int64_t M, int n_frames, PdSeqTables &out);   // pure: no HIP call, no engine
 void pd_ggs_free_seq(PdSeqHost &h);
 int pd_ggs_ingest_init();   // pd_ggs_ingest.hip: the device builder (pd_ggs_set_matches_csr_async)
+// pd_engine.hip: PD_ERR_UNSUPPORTED (and the message) for a GGS call with PD_MAX_FRAMES < N <= max_N, else PD_OK
+int pd_ggs_frames_unsupported(const pd_engine *eng, int N, const char *who);
 // pd_engine.hip: the engine's stream-event bookkeeping (pd_engine::uses / uploads / retired_blobs)
 bool pd_stream_capturing(hipStream_t s);
 int pd_wait_uploads(pd_engine *eng, hipStream_t s);   // device-side wait for pending asynchronous match uploads (no-op in a capture)

@@ -115,6 +115,9 @@ class GaussianDiffusion(nn.Module):
                 raise ValueError(f"sequences {[b for b, h in enumerate(have) if not h]} of the batch have no matches: sample them in a call "
                                  "without cond_fn (demo.py:79-92) and the others with it")
             has_ggs = all(have)
+        if has_ggs and N > host.GGS_MAX_FRAMES:
+            # the denoiser takes up to 256 frames, GGS 64 (include/pd_engine.h): no silent fallback to unguided sampling
+            raise RuntimeError(f"guided sampling (GGS) is limited to {host.GGS_MAX_FRAMES} frames, got {N}: run unguided (GGS.enable=False)")
         eng = host.get_engine(self.model, self, B, N)
         if cond_fn is not None and parsed is None:
             # unknown guidance callable: reference control flow in Python, arithmetic on the HIP kernels

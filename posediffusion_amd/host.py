@@ -19,6 +19,7 @@ import torch
 from .engine import PoseEngine, make_ggs_cfg
 
 _DENOISER_PREFIXES = ("time_embed.", "_first.", "_trunk.", "_last.")
+GGS_MAX_FRAMES = 64          # PD_MAX_FRAMES: GGS stops here; the denoiser and unguided sampling take up to 256 frames (include/pd_engine.h)
 
 
 def _fingerprint(denoiser: torch.nn.Module, diffuser: Optional[torch.nn.Module]):
