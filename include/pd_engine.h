@@ -194,6 +194,33 @@ int pd_denoise_step_t(pd_engine *eng, const float *x, const float *z, const int6
 int pd_p_losses(pd_engine *eng, const float *x_start, const float *z, const int64_t *t_seq, const float *noise, int B, int N,
                 int loss_type, float *loss_out, float *x0_pred_out, float *xt_out, float *model_out, void *stream);
 
+/* ---- sequences of different frame counts in one padded batch ------------------------------------------------------
+ * n_frames HOST int32 [B], each in [1, N_of_the_later_calls]; NULL or B == 0 clears.
+ * While counts are set, sequence b of every call with that B has n_frames[b] frames: they sit in rows 0 .. n_frames[b]-1 of its N-row
+ * block of every [B, N, .] tensor (nothing is packed: the row stride stays N); rows at or beyond the count are padding.  Honoured by
+ * pd_denoise_step, pd_p_mean, pd_p_finish, pd_ggs_guide / _optimize / _loss_grad, pd_sample, pd_sample_phase and pd_debug_ggs_plan; the
+ * reference for each is the sequence run ALONE through the reference code with n_frames[b] frames.
+ *   denoiser  attention of sequence b sees keys < n_frames[b] only (the key-tiled kernel of csrc/pd_attn_long.h serves every N while counts
+ *             are set); the pivot column stays at row 0 of each block; valid rows do not depend on what the padding rows of x, z and noise
+ *             hold (NaN included: a padded key is never read); padding rows of EVERY output (eps_out, mean_out, x0_out, x_out, pose_out,
+ *             every slice of process_out) are written as +0.0f.
+ *   GGS       slot b's matches must have been uploaded with n_frames == n_frames[b] (else PD_ERR_INVALID_ARG); that one count drives the
+ *             focal mean, the min_matches test, both norms and every per-frame loop of the sequence.  Padding rows of model_mean are not
+ *             touched.  trace_out must be NULL (PD_ERR_INVALID_ARG).  The launch plan stays what it is -- ONE launch of ONE kernel family,
+ *             decided over the slots together: the lane-per-item kernel needs lane tables in every slot, the two-hop kernel several chunks
+ *             of pairs in every slot.  Where the plan refuses a mix the call returns the plan's PD_ERR_UNSUPPORTED and the engine stays
+ *             usable: GROUPING SEQUENCES INTO LAUNCHES THE PLAN ACCEPTS IS THE CALLER'S JOB.  The 64-frame GGS limit and the 256-frame
+ *             denoiser limit are unchanged.
+ *   graphs    "counts are set" is part of the key of a captured loop, the counts are not: a loop replayed after another
+ *             pd_engine_set_frame_counts with the same B uses the new counts.
+ *   errors    a count outside [1, N] and a call whose B differs from the B of the counts: PD_ERR_INVALID_ARG (the message names the rule);
+ *             pd_denoise_step_t and pd_p_losses: PD_ERR_UNSUPPORTED while counts are set (training batches are uniform); pd_time_kernel
+ *             ignores the counts.
+ * Ordered on `stream` (the counts reach the device as kernel arguments); no device synchronisation, no allocation; may be called while
+ * earlier work of the same stream is in flight.  The engine keeps a host copy for validation.  With no counts set every call launches
+ * exactly what it launched before this entry point existed. */
+int pd_engine_set_frame_counts(pd_engine *eng, int B, const int32_t *n_frames, void *stream);
+
 /* ---- Geometry-Guided Sampling ------------------------------------------------------------ */
 
 /* Upload the matches of sequence slot `seq` (0 <= seq < max_B).  Replaces the per-call host

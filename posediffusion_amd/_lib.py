@@ -88,6 +88,7 @@ SIGNATURES = {
     "pd_version": (C.c_char_p, []),
     "pd_denoise_step": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "pd_engine_set_q_tables": (_i, [_vp, _vp, _vp]),
+    "pd_engine_set_frame_counts": (_i, [_vp, _i, C.POINTER(C.c_int32), _vp]),
     "pd_denoise_step_t": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
     "pd_p_losses": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "pd_camera_to_pose": (_i, [_vp, _vp, _vp, _i, C.c_float, C.c_float, C.c_float, _vp, _vp]),

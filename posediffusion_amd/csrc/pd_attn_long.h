@@ -16,6 +16,11 @@
 // operation is that of pd_attn_kernel / pd_attn_seq_kernel on the same operands: the default-shape kernel gives their bits
 // (PD_OPT_DENOISER_LONG_ATTN = 1 forces it there; tests/test_gpu_long_sequences.py).
 //
+// Frame counts per sequence (pd_engine_set_frame_counts): `nf` != null gives sequence b its own number of frames Nk = nf[b] <= N in rows
+// 0 .. Nk - 1 of its N-row block.  Only keys < Nk are staged, scored and summed -- a padding row of qkv is never read, whatever it holds --, query
+// rows >= Nk are skipped (their ctx rows keep what they held; every later kernel is per-row work and the tail writes zeros there), and a
+// workgroup whose query rows all lie beyond Nk leaves at once.  With Nk == N every operation is that of the uniform call (same bits).
+//
 // One body serves the default shape (head dim a compile-time 128: pd_attn_long_kernel<SPLIT_OUT>) and the shape-generic path (runtime head
 // dim, a multiple of 4 in [8, 256], rows of stride Dp: pd_gen_attn_long_kernel).
 // LDS: pd_attn_long_lds(N, hd) -- 64 832 B at the default head and 256 frames (two workgroups per CU), 107 840 B at head dim 256.
@@ -41,16 +46,21 @@ static inline size_t pd_attn_long_lds(int N, int hd) {
 // SPLIT_OUT: 0 fp32, 1 bf16 split words, 2 fp16 split words of ctx * out_scale (pd_split_word_as)
 template <int HD, int SPLIT_OUT>
 __device__ __forceinline__ void pd_attn_long_body(const float *__restrict__ qkv, float *__restrict__ ctx, int N, int nhead, int hd_rt, int Dp,
-                                                  float scale, float out_scale) {
+                                                  float scale, float out_scale, const int *__restrict__ nf) {
     constexpr int R = PD_ATTN_LONG_RPW, TK = PD_ATTN_LONG_TILE, NT = PD_ATTN_LONG_MAX_TILES, NC = HD ? HD / 64 : 4;
     const int hd = HD ? HD : hd_rt, LD = hd + 4, hd4 = hd / 4;
-    const int nt = (N + TK - 1) / TK, PS = TK * nt;
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    float *T = lds, *Q = T + TK * LD, *P = Q + 4 * R * LD;      // tile [64][LD], Q [4 R][LD], P [4 waves][R][PS]
     const int b = blockIdx.x / nhead, h = blockIdx.x % nhead, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int i0 = blockIdx.y * (4 * R);                        // this workgroup's first query row
     const size_t ld3 = (size_t)3 * Dp;
     const float *base = qkv + (size_t)b * N * ld3 + (size_t)h * hd;
+    const int Ns = N;                                           // rows per sequence block (the stride of qkv and ctx)
+    if (nf) {                                                   // this sequence's own frame count (clamped: nothing is indexed past the block)
+        N = max(1, min(nf[b], Ns));
+        if (i0 >= N) return;                                    // (uniform over the workgroup, before any barrier)
+    }
+    const int nt = (N + TK - 1) / TK, PS = TK * nt;
+    float *T = lds, *Q = T + TK * LD, *P = Q + 4 * R * LD;      // tile [64][LD], Q [4 R][LD], P [4 waves][R][PS]
     for (int idx = tid; idx < 4 * R * hd4; idx += 256) {
         const int r = idx / hd4, d4 = idx - r * hd4;
         float4 q = *(const float4 *)(base + (size_t)min(i0 + r, N - 1) * ld3 + 4 * d4);
@@ -144,7 +154,7 @@ __device__ __forceinline__ void pd_attn_long_body(const float *__restrict__ qkv,
     for (int t = 0; t < R; ++t) {
         const int i = i0 + wave * R + t;
         if (i < N) {
-            float *out = ctx + (size_t)(b * N + i) * Dp + (size_t)h * hd;
+            float *out = ctx + (size_t)(b * Ns + i) * Dp + (size_t)h * hd;
 #pragma unroll
             for (int c = 0; c < NC; ++c) {
                 const int dd = lane + 64 * c;
@@ -159,14 +169,15 @@ __device__ __forceinline__ void pd_attn_long_body(const float *__restrict__ qkv,
 
 // the default shape: grid (B x NH, ceil(N / PD_ATTN_LONG_ROWS)), 256 threads, pd_attn_long_lds(N, DH) bytes
 template <int SPLIT_OUT>
-__global__ __launch_bounds__(256) void pd_attn_long_kernel(const float *__restrict__ qkv, float *__restrict__ ctx, int N, float out_scale) {
-    pd_attn_long_body<DH, SPLIT_OUT>(qkv, ctx, N, NH, DH, DM, 0.08838834764831845f /* 1/sqrt(128) */, out_scale);
+__global__ __launch_bounds__(256) void pd_attn_long_kernel(const float *__restrict__ qkv, float *__restrict__ ctx, int N, float out_scale,
+                                                           const int *__restrict__ nf) {
+    pd_attn_long_body<DH, SPLIT_OUT>(qkv, ctx, N, NH, DH, DM, 0.08838834764831845f /* 1/sqrt(128) */, out_scale, nf);
 }
 // the shape-generic path: grid (B x nhead, ceil(N / PD_ATTN_LONG_ROWS)), 256 threads, pd_attn_long_lds(N, hd) bytes (a template like its twin,
 // so that only the translation unit that launches it holds an instantiation; the generic path has fp32 activations only: SPLIT_OUT = 0)
 template <int SPLIT_OUT>
 __global__ __launch_bounds__(256) void pd_gen_attn_long_kernel(const float *__restrict__ qkv, float *__restrict__ ctx, int N, int nhead, int hd, int Dp,
-                                                               float scale) {
-    pd_attn_long_body<0, SPLIT_OUT>(qkv, ctx, N, nhead, hd, Dp, scale, 1.0f);
+                                                               float scale, const int *__restrict__ nf) {
+    pd_attn_long_body<0, SPLIT_OUT>(qkv, ctx, N, nhead, hd, Dp, scale, 1.0f, nf);
 }
 #endif

@@ -288,20 +288,21 @@ static void den_first_streamed_t(const PdDenoiserDev *d, const float *x, const i
 }
 
 // the key-tiled attention kernel (pd_attn_long.h): more than 64 frames on every path, or PD_OPT_DENOISER_LONG_ATTN = 1
+// nf: the frame counts per sequence (device, [B]) or null
 template <int SPLIT_OUT>
-static void den_attn_long(const PdDenoiserDev *d, int B, int N, float out_scale, hipStream_t s) {
+static void den_attn_long(const PdDenoiserDev *d, int B, int N, float out_scale, const int *nf, hipStream_t s) {
     static_assert(PD_MAX_DENOISER_FRAMES == PD_ATTN_LONG_TILE * PD_ATTN_LONG_MAX_TILES, "a lane holds one score per 64-key tile");
     hipLaunchKernelGGL(pd_attn_long_kernel<SPLIT_OUT>, dim3(B * NH, (N + PD_ATTN_LONG_ROWS - 1) / PD_ATTN_LONG_ROWS), dim3(256), pd_attn_long_lds(N, DH), s,
-                       d->qkv, d->ctx, N, out_scale);
+                       d->qkv, d->ctx, N, out_scale, nf);
 }
 
-static void den_layer_small(const pd_engine *eng, const PdDenoiserDev *d, const PdLayerDev &L, GemmArgs &g, bool long_attn, int B, int N, int MT,
+static void den_layer_small(const pd_engine *eng, const PdDenoiserDev *d, const PdLayerDev &L, GemmArgs &g, bool long_attn, const int *nf, int B, int N, int MT,
                             hipStream_t s) {
     // x += MHA(LN1(x))
     g.A = d->h; g.bias = L.qkv_b; g.C = d->qkv; g.Nout = 3 * DM;
     launch_gemm<DM, 1, 0>(g, L.qkv_wp, MT, eng->gemm_wide_min_tiles, s);
     if (long_attn) {
-        den_attn_long<0>(d, B, N, 1.0f, s);
+        den_attn_long<0>(d, B, N, 1.0f, nf, s);
     } else {
 #ifdef PD_DEN_STAMPS
         hipLaunchKernelGGL(pd_attn_kernel<false>, dim3(B * NH, (N + 3) / 4), dim3(256), attn_lds(N), s, d->qkv, d->ctx, N, next_stamp_slot());
@@ -318,11 +319,11 @@ static void den_layer_small(const pd_engine *eng, const PdDenoiserDev *d, const 
     launch_gemm<DFF, 0, 2>(g, L.ff2_wp, MT, eng->gemm_wide_min_tiles, s);
 }
 // exact fp32: LayerNorm is fused into the A staging of the streamed GEMMs (statistics pre-pass; affine folded into the weights, as on the small path)
-static void den_layer_streamed(const PdDenoiserDev *d, const PdLayerDev &L, bool long_attn, int B, int N, int M, hipStream_t s) {
+static void den_layer_streamed(const PdDenoiserDev *d, const PdLayerDev &L, bool long_attn, const int *nf, int B, int N, int M, hipStream_t s) {
     float2 *stats = (float2 *)d->hn;           // (mean, rstd) per token row; applied in the A staging of the next GEMM
     hipLaunchKernelGGL(pd_ln_stats_kernel<DM>, dim3((M + 3) / 4), dim3(256), 0, s, d->h, stats, M, 1e-5f);
     pd_gemm_dma<0, true>(d->h, DM, L.qkv_wf, DM, L.qkv_b, d->qkv, M, 3 * DM, s, stats);                // LayerNorm-1 at the fragment reads
-    if (long_attn) den_attn_long<0>(d, B, N, 1.0f, s);
+    if (long_attn) den_attn_long<0>(d, B, N, 1.0f, nf, s);
     else hipLaunchKernelGGL(pd_attn_seq_kernel<0>, dim3(B * NH), dim3(256), attn_seq_lds(N), s, d->qkv, d->ctx, N, 1.0f);
     pd_gemm_dma<2>(d->ctx, DM, L.out_wf, DM, L.out_b, d->h, M, DM, s);
     hipLaunchKernelGGL(pd_ln_stats_kernel<DM>, dim3((M + 3) / 4), dim3(256), 0, s, d->h, stats, M, 1e-5f);
@@ -331,10 +332,10 @@ static void den_layer_streamed(const PdDenoiserDev *d, const PdLayerDev &L, bool
 }
 // fast mode: the four encoder GEMMs on the bf16 matrix pipe in split precision (pd_gemm_split.h); activations
 // between them as split words -- LayerNorm, attention and the FF1 epilogue write them in place of fp32
-static void den_layer_bf16(const PdDenoiserDev *d, const PdLayerDev &L, bool long_attn, int B, int N, int M, hipStream_t s) {
+static void den_layer_bf16(const PdDenoiserDev *d, const PdLayerDev &L, bool long_attn, const int *nf, int B, int N, int M, hipStream_t s) {
     hipLaunchKernelGGL((pd_ln_rows_kernel<DM, 1>), dim3((M + 3) / 4), dim3(256), 0, s, d->h, d->hn, M, 1e-5f, 1.0f);
     pd_gemm_split<0, 1, 2>((const unsigned *)d->hn, DM, L.qkv_ws, DM, L.qkv_b, d->qkv, M, 3 * DM, s);
-    if (long_attn) den_attn_long<1>(d, B, N, 1.0f, s);
+    if (long_attn) den_attn_long<1>(d, B, N, 1.0f, nf, s);
     else hipLaunchKernelGGL(pd_attn_seq_kernel<1>, dim3(B * NH), dim3(256), attn_seq_lds(N), s, d->qkv, d->ctx, N, 1.0f);
     pd_gemm_split<2, 1, 1>((const unsigned *)d->ctx, DM, L.out_ws, DM, L.out_b, d->h, M, DM, s);
     hipLaunchKernelGGL((pd_ln_rows_kernel<DM, 1>), dim3((M + 3) / 4), dim3(256), 0, s, d->h, d->hn, M, 1e-5f, 1.0f);
@@ -357,7 +358,7 @@ static void den_gemm_f16(int rt, const float *A, int K, const unsigned *W, const
 }
 // fp16-plane mode: the fast mode's kernels with fp16 halves and the static power-of-two scales of pd_denoiser_build_split
 // (22 mantissa bits, fp32 accumulation: fp32-grade results at the three-product rate)
-static void den_layer_f16(const PdDenoiserDev *d, const PdLayerDev &L, const PdDenStepPlan &p, int B, int N, hipStream_t s) {
+static void den_layer_f16(const PdDenoiserDev *d, const PdLayerDev &L, const PdDenStepPlan &p, const int *nf, int B, int N, hipStream_t s) {
     const int M = p.M;
     hipLaunchKernelGGL((pd_ln_rows_kernel<DM, 2>), dim3((M + 3) / 4), dim3(256), 0, s, d->h, d->hn, M, 1e-5f, 512.0f);
     if (p.fused_attn) {
@@ -366,7 +367,7 @@ static void den_layer_f16(const PdDenoiserDev *d, const PdLayerDev &L, const PdD
         pd_qkv_attn((const unsigned *)d->hn, L.qkv_wh, L.qkv_b, (unsigned *)d->ctx, B, N, L.qkv_cs, L.ctx_scale, s);
     } else {
         den_gemm_f16<0>(p.strip & 1 ? 2 : 0, d->hn, DM, L.qkv_wh, L.qkv_b, d->qkv, M, 3 * DM, s, L.qkv_cs);
-        if (p.long_attn) den_attn_long<2>(d, B, N, L.ctx_scale, s);
+        if (p.long_attn) den_attn_long<2>(d, B, N, L.ctx_scale, nf, s);
         else if (p.attn_mma) hipLaunchKernelGGL(pd_attn_mma_kernel<2>, dim3(B * NH), dim3(256), attn_mma_lds(N), s, d->qkv, d->ctx, N, L.ctx_scale);
         else hipLaunchKernelGGL(pd_attn_seq_kernel<2>, dim3(B * NH), dim3(256), attn_seq_lds(N), s, d->qkv, d->ctx, N, L.ctx_scale);
     }
@@ -377,7 +378,7 @@ static void den_layer_f16(const PdDenoiserDev *d, const PdLayerDev &L, const PdD
 }
 // the fused LN / ReLU / Linear(128 -> 9) / DDPM tail on _last.0's output
 static void den_tail(const pd_engine *eng, const PdDenoiserDev *d, const float *x, int t, int M, float *eps_out, float *mean_out, float *x0_out,
-                     const float *noise, float *x_next_out, bool stamped, hipStream_t s) {
+                     const float *noise, float *x_next_out, bool stamped, const int *nf, int N, hipStream_t s) {
     HeadArgs ha;
     memset(&ha, 0, sizeof(ha));
     ha.hid = d->hid; ha.lnw = d->last_ln_w; ha.lnb = d->last_ln_b;
@@ -387,6 +388,7 @@ static void den_tail(const pd_engine *eng, const PdDenoiserDev *d, const float *
     ha.sigma = expf(0.5f * eng->logvar[t]);
     ha.M = M;
     ha.pred_x0 = eng->pred_x0;
+    ha.nf = nf; ha.n_frames = N;
 #ifdef PD_DEN_STAMPS
     ha.stamps = stamped ? next_stamp_slot() : nullptr;
 #endif
@@ -432,13 +434,17 @@ int pd_denoiser_launch(pd_engine *eng, const float *x, const float *z, int t, in
                      eng->max_B, eng->max_N, PD_MAX_DENOISER_FRAMES, d->timesteps);
         return PD_ERR_INVALID_ARG;
     }
+    // frame counts per sequence (pd_engine_set_frame_counts): attention takes the length of every sequence, the tail zeroes the padding rows;
+    // everything between is per-row work.  The training branch (ts) is refused by its entry points while counts are set.
+    const int *nf = nullptr;
+    if (!ts) PD_TRY(pd_frame_counts(eng, B, N, "denoiser", &nf));
     if (!z_prepared) {
         int rc = pd_denoiser_prepare(eng, z, B, N, s);
         if (rc) return rc;
     }
     static const int knob_strip = pd_dev_knob("PD_DEN_STRIP", 15), knob_attn_mma = pd_dev_knob("PD_DEN_ATTN_MMA", 1);     // development A / B
     const PdDenStepPlan p = pd_den_step_plan(B, N, eng->den_split, eng->den_fused_attn, eng->num_cus, d->hn != nullptr, d->split_ready,
-                                             d->split_h_ready, knob_strip, knob_attn_mma, eng->den_long_attn);
+                                             d->split_h_ready, knob_strip, knob_attn_mma, eng->den_long_attn, nf != nullptr);
     const bool small = p.path == PD_DEN_SMALL;
     const int M = p.M;
     GemmArgs g;                       // the small path's launches share it
@@ -451,10 +457,10 @@ int pd_denoiser_launch(pd_engine *eng, const float *x, const float *z, int t, in
     for (int l = 0; l < d->num_layers; ++l) {
         const PdLayerDev &L = d->layers[l];
         switch (p.path) {
-        case PD_DEN_SMALL: den_layer_small(eng, d, L, g, p.long_attn, B, N, p.MT, s); break;
-        case PD_DEN_STREAMED: den_layer_streamed(d, L, p.long_attn, B, N, M, s); break;
-        case PD_DEN_BF16_PLANES: den_layer_bf16(d, L, p.long_attn, B, N, M, s); break;
-        case PD_DEN_F16_PLANES: den_layer_f16(d, L, p, B, N, s); break;
+        case PD_DEN_SMALL: den_layer_small(eng, d, L, g, p.long_attn, nf, B, N, p.MT, s); break;
+        case PD_DEN_STREAMED: den_layer_streamed(d, L, p.long_attn, nf, B, N, M, s); break;
+        case PD_DEN_BF16_PLANES: den_layer_bf16(d, L, p.long_attn, nf, B, N, M, s); break;
+        case PD_DEN_F16_PLANES: den_layer_f16(d, L, p, nf, B, N, s); break;
         }
     }
     // _last.0 as a plain tile GEMM, then the tail
@@ -465,7 +471,7 @@ int pd_denoiser_launch(pd_engine *eng, const float *x, const float *z, int t, in
         pd_gemm_dma<0>(d->h, DM, d->last0_wf, DM, d->last0_b, d->hid, M, HID, s);
     }
     if (ts) den_tail_t(eng, d, x, M, *ts, eps_out, x0_out, s);
-    else den_tail(eng, d, x, t, M, eps_out, mean_out, x0_out, noise, x_next_out, small, s);
+    else den_tail(eng, d, x, t, M, eps_out, mean_out, x0_out, noise, x_next_out, small, nf, N, s);
     PD_HIP_CHECK(hipGetLastError());
     return PD_OK;
 }

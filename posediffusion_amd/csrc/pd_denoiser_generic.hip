@@ -197,6 +197,8 @@ struct PdGenTailArgs {
     float *eps_out, *mean_out, *x0_out, *xnext_out;
     float c_recip, c_recipm1, coef1, coef2, sigma;
     int M, H, Hp, pred_x0;
+    const int *nf;                  // frame counts per sequence (pd_engine_set_frame_counts) or null; n_frames rows per sequence block
+    int n_frames;
     // TSEQ (pd_denoise_step_t, pd_p_losses): every row's own coefficients from device tables, and the loss (gaussian_diffuser.py:312-327)
     const int *t_row;                     // [M]
     const float *c_recip_tab, *c_recipm1_tab;
@@ -208,6 +210,19 @@ template <bool TSEQ>
 __global__ __launch_bounds__(256) void pd_gen_tail_kernel(PdGenTailArgs g) {
     const int lane = threadIdx.x & 63, m = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (m >= g.M) return;
+    if (!TSEQ && g.nf) {            // a padding row (wave-uniform): every output gets +0, nothing of the row is read
+        const int sb = m / g.n_frames;
+        if (m - sb * g.n_frames >= g.nf[sb]) {
+            if (lane < 9) {
+                const size_t at = (size_t)m * 9 + lane;
+                if (g.eps_out) g.eps_out[at] = 0.0f;
+                if (g.x0_out) g.x0_out[at] = 0.0f;
+                if (g.mean_out) g.mean_out[at] = 0.0f;
+                if (g.xnext_out) g.xnext_out[at] = 0.0f;
+            }
+            return;
+        }
+    }
     const float *row = g.hid + (size_t)m * g.Hp;
     float v[PD_GEN_TAIL_PER];
     float s = 0.0f;
@@ -385,6 +400,8 @@ int pd_denoiser_generic_launch(pd_engine *eng, const float *x, const float *z, i
                      PD_MAX_DENOISER_FRAMES, G->timesteps);
         return PD_ERR_INVALID_ARG;
     }
+    const int *nf = nullptr;        // frame counts per sequence: the key-tiled attention kernel takes them, the tail zeroes the padding rows
+    if (!ts) PD_TRY(pd_frame_counts(eng, B, N, "denoiser", &nf));
     const int M = B * N, Dp = G->Dp, Fp = G->Fp;
     const int rows_blocks = (M + 3) / 4;
     {
@@ -397,11 +414,11 @@ int pd_denoiser_generic_launch(pd_engine *eng, const float *x, const float *z, i
     const float scale = 1.0f / sqrtf((float)G->hd);
     const size_t attn_lds = pd_gen_attn_lds(N, G->hd);
     // more than 64 frames (or PD_OPT_DENOISER_LONG_ATTN = 1): K and V through LDS in tiles of 64 keys
-    const bool long_attn = N > PD_MAX_FRAMES || eng->den_long_attn;
+    const bool long_attn = N > PD_MAX_FRAMES || eng->den_long_attn || nf;
     const auto attention = [&]() {
         if (long_attn)
             hipLaunchKernelGGL(pd_gen_attn_long_kernel<0>, dim3(B * G->nhead, (N + PD_ATTN_LONG_ROWS - 1) / PD_ATTN_LONG_ROWS), dim3(256),
-                               pd_attn_long_lds(N, G->hd), s, G->qkv, G->ctx, N, G->nhead, G->hd, Dp, scale);
+                               pd_attn_long_lds(N, G->hd), s, G->qkv, G->ctx, N, G->nhead, G->hd, Dp, scale, nf);
         else
             hipLaunchKernelGGL(pd_gen_attn_kernel, dim3(B * G->nhead), dim3(PD_GEN_ATTN_THREADS), attn_lds, s, G->qkv, G->ctx, N, G->nhead, G->hd, Dp, scale);
     };
@@ -438,6 +455,7 @@ int pd_denoiser_generic_launch(pd_engine *eng, const float *x, const float *z, i
     ta.c_recip = eng->c_recip[t]; ta.c_recipm1 = eng->c_recipm1[t]; ta.coef1 = eng->coef1[t]; ta.coef2 = eng->coef2[t];
     ta.sigma = expf(0.5f * eng->logvar[t]);
     ta.M = M; ta.H = G->hid; ta.Hp = G->Hp; ta.pred_x0 = eng->pred_x0;
+    ta.nf = nf; ta.n_frames = N;
     if (ts) {
         ta.t_row = ts->t_row; ta.c_recip_tab = eng->d_c_recip; ta.c_recipm1_tab = eng->d_c_recipm1;
         ta.target = ts->target; ta.loss_out = ts->loss_out; ta.loss_type = ts->loss_type;

@@ -121,6 +121,8 @@ struct HeadArgs {
     float c_recip, c_recipm1, coef1, coef2, sigma;
     int M;
     int pred_x0;           // objective "pred_x0": the model output is x_start (gaussian_diffuser.py:225-227)
+    const int *nf;         // frame counts per sequence (pd_engine_set_frame_counts) or null: row m is padding when m % n_frames >= nf[m / n_frames]
+    int n_frames;          //   rows per sequence block
 #ifdef PD_DEN_STAMPS
     long long *stamps;
 #endif
@@ -155,6 +157,18 @@ __global__ __launch_bounds__(256) void pd_tail_kernel(HeadArgs g) {
     // everything the last nine lanes add at the end is requested now (clamped lane: no predicated loads), not behind the reductions
     const int l9 = lane < 9 ? lane : 8;
     const size_t at = (size_t)m * 9 + l9;
+    if (g.nf) {            // a padding row (wave-uniform): every output gets +0, nothing of the row is read
+        const int sb = m / g.n_frames;
+        if (m - sb * g.n_frames >= g.nf[sb]) {
+            if (lane < 9) {
+                if (g.eps_out) g.eps_out[at] = 0.0f;
+                if (g.x0_out) g.x0_out[at] = 0.0f;
+                if (g.mean_out) g.mean_out[at] = 0.0f;
+                if (g.xnext_out) g.xnext_out[at] = 0.0f;
+            }
+            return;
+        }
+    }
     const float b3v = g.b3[l9], xv = g.x[at], nz = g.noise ? g.noise[at] : 0.0f;
     float e = pd_tail_project(g, m, lane);
     if (lane < 9) {

@@ -31,6 +31,7 @@ struct PdDenStepPlan {
     int M, MT;             // token rows; 32-row tiles of the small-batch GEMMs
     bool long_attn;        // every path: the key-tiled pd_attn_long_kernel (pd_attn_long.h) in place of the path's attention kernel -- above 64
                            //   frames always, below on request (PD_OPT_DENOISER_LONG_ATTN = 1: bitwise the kernel it replaces, except pd_attn_mma_kernel)
+                           //   and whenever frame counts per sequence are set
     // PD_DEN_F16_PLANES only (zero on the other paths)
     bool fused_attn;       // in_proj + attention as ONE kernel (pd_qkv_attn.h), else the QKV GEMM and an attention kernel
     bool attn_mma;         // the attention kernel of the two-launch form: pd_attn_mma_kernel, else pd_attn_seq_kernel (or the long kernel, above)
@@ -40,13 +41,14 @@ struct PdDenStepPlan {
 
 // split / fused_attn: PD_OPT_DENOISER_SPLIT / PD_OPT_DENOISER_FUSED_ATTN; has_streamed: the engine was created for >= PD_STREAM_MIN_ROWS token
 // rows; split_ready / split_h_ready: the bf16 / fp16 planes are built; knob_*: the development knobs PD_DEN_STRIP and PD_DEN_ATTN_MMA;
-// long_attn: PD_OPT_DENOISER_LONG_ATTN
+// long_attn: PD_OPT_DENOISER_LONG_ATTN; ragged: frame counts per sequence are set (pd_engine_set_frame_counts) -- the key-tiled kernel is the
+// one attention kernel that takes a length per sequence, so it serves every N then (and the fused in_proj + attention kernel is not chosen)
 static inline PdDenStepPlan pd_den_step_plan(int B, int N, int split, int fused_attn, int num_cus, bool has_streamed, bool split_ready,
-                                             bool split_h_ready, int knob_strip, int knob_attn_mma, int long_attn = 0) {
+                                             bool split_h_ready, int knob_strip, int knob_attn_mma, int long_attn = 0, bool ragged = false) {
     PdDenStepPlan p = {};
     p.M = B * N;
     p.MT = (p.M + 31) / 32;
-    p.long_attn = N > 64 || long_attn != 0;
+    p.long_attn = N > 64 || long_attn != 0 || ragged;
     // >= 1024 token rows (52 sequences of 20 frames): the encoder GEMMs are large enough for 64 x 64 tiles streamed through LDS
     // (pd_gemm_stream.h; same sums in another order than the 32-row split-K tiles of the small path, i.e. rounding-level differences
     // between small and large batches)

@@ -27,10 +27,94 @@ extern "C" const char *pd_last_error(void) { return g_err; }
 extern "C" const char *pd_version(void) { return "pd_engine 0.1 gfx950"; }
 
 // ---- small kernels ------------------------------------------------------------------------------
+// nf != null (frame counts per sequence): rows >= nf[b] of sequence b's n_frames-row block are padding and get +0
 __global__ void pd_finish_kernel(const float *__restrict__ mean, const float *__restrict__ noise, float sigma, int n,
-                                 float *__restrict__ out) {
+                                 float *__restrict__ out, const int *__restrict__ nf, int n_frames) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = noise ? mean[i] + sigma * noise[i] : mean[i];   // gaussian_diffuser.py:280
+    if (i >= n) return;
+    if (nf) {
+        const int m = i / 9, sb = m / n_frames;
+        if (m - sb * n_frames >= nf[sb]) {
+            out[i] = 0.0f;
+            return;
+        }
+    }
+    out[i] = noise ? mean[i] + sigma * noise[i] : mean[i];   // gaussian_diffuser.py:280
+}
+
+// ---- frame counts per sequence (pd_engine_set_frame_counts) -------------------------------------
+// The counts travel to the device as KERNEL ARGUMENTS (count - 1 in a byte, PD_NF_CHUNK per launch): ordered on the stream like any launch,
+// no staging buffer that a second call could overwrite while the first is still in flight, no allocation, no synchronisation.
+#define PD_NF_CHUNK 1024
+struct PdCountsChunk {
+    unsigned w[PD_NF_CHUNK / 4];
+};
+__global__ void pd_set_counts_kernel(PdCountsChunk v, int first, int n, int *__restrict__ dst) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) dst[first + i] = (int)((v.w[i >> 2] >> (8 * (i & 3))) & 255u) + 1;
+}
+// +0 into the padding rows of x [B, n_frames, 9] (slice 0 of the sampler's process buffer, which is a copy of the caller's noise)
+__global__ void pd_zero_padding_kernel(float *__restrict__ x, int n, const int *__restrict__ nf, int n_frames) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int m = i / 9, sb = m / n_frames;
+    if (m - sb * n_frames >= nf[sb]) x[i] = 0.0f;
+}
+
+extern "C" int pd_engine_set_frame_counts(pd_engine *eng, int B, const int32_t *n_frames, void *stream) {
+    if (!eng) {
+        pd_set_error("pd_engine_set_frame_counts: NULL engine");
+        return PD_ERR_INVALID_ARG;
+    }
+    if (!n_frames || B == 0) {
+        eng->nf_B = 0;               // cleared: every later call is a uniform one (the kernels get no count pointer)
+        return PD_OK;
+    }
+    if (B < 0 || B > eng->max_B) {
+        pd_set_error("pd_engine_set_frame_counts: B=%d must lie in [0, max_B=%d]", B, eng->max_B);
+        return PD_ERR_INVALID_ARG;
+    }
+    for (int b = 0; b < B; ++b)
+        if (n_frames[b] < 1 || n_frames[b] > eng->max_N) {
+            pd_set_error("pd_engine_set_frame_counts: n_frames[%d]=%d: every count must lie in [1, N] (N <= max_N=%d)", b, (int)n_frames[b], eng->max_N);
+            return PD_ERR_INVALID_ARG;
+        }
+    hipStream_t s = (hipStream_t)stream;
+    for (int first = 0; first < B; first += PD_NF_CHUNK) {
+        const int n = std::min(PD_NF_CHUNK, B - first);
+        PdCountsChunk c;
+        memset(&c, 0, sizeof(c));
+        for (int i = 0; i < n; ++i) c.w[i >> 2] |= (unsigned)(n_frames[first + i] - 1) << (8 * (i & 3));
+        hipLaunchKernelGGL(pd_set_counts_kernel, dim3((n + 255) / 256), dim3(256), 0, s, c, first, n, eng->d_nf);
+    }
+    PD_HIP_CHECK(hipGetLastError());
+    for (int b = 0; b < B; ++b) eng->nf_host[b] = n_frames[b];
+    eng->nf_B = B;
+    return PD_OK;
+}
+
+int pd_frame_counts(const pd_engine *eng, int B, int N, const char *who, const int **nf_dev) {
+    *nf_dev = nullptr;
+    if (!eng || eng->nf_B == 0) return PD_OK;
+    if (B != eng->nf_B) {
+        pd_set_error("%s: frame counts per sequence are set for B=%d (pd_engine_set_frame_counts), called with B=%d: a call must use the B of "
+                     "the counts, or clear them", who, eng->nf_B, B);
+        return PD_ERR_INVALID_ARG;
+    }
+    for (int b = 0; b < B; ++b)
+        if (eng->nf_host[b] > N) {
+            pd_set_error("%s: n_frames[%d]=%d (pd_engine_set_frame_counts) exceeds N=%d: every count must lie in [1, N]", who, b, eng->nf_host[b], N);
+            return PD_ERR_INVALID_ARG;
+        }
+    *nf_dev = eng->d_nf;
+    return PD_OK;
+}
+// the training branch draws one batch of uniform sequences: refused while counts are set
+static int counts_unsupported(const pd_engine *eng, const char *who) {
+    if (!eng || eng->nf_B == 0) return PD_OK;
+    pd_set_error("%s: not available while frame counts per sequence are set (pd_engine_set_frame_counts): training batches are uniform; clear "
+                 "the counts first", who);
+    return PD_ERR_UNSUPPORTED;
 }
 
 // torch.clamp: NaN stays NaN (fminf / fmaxf would return the bound)
@@ -184,7 +268,7 @@ extern "C" void pd_engine_destroy(pd_engine *eng) {
     }
     pd_denoiser_destroy(eng);
     void *ptrs[] = {eng->d_seqs, eng->d_xchg, eng->d_err, eng->d_z, eng->d_noise, eng->d_process, eng->d_mean, eng->d_stats, eng->d_stamps,
-                    eng->d_c_recip, eng->d_c_recipm1, eng->d_q_a, eng->d_q_b, eng->d_t_row, eng->d_xt};
+                    eng->d_c_recip, eng->d_c_recipm1, eng->d_q_a, eng->d_q_b, eng->d_t_row, eng->d_xt, eng->d_nf};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     delete eng;
@@ -271,6 +355,8 @@ extern "C" int pd_engine_create(const pd_weights *w, int max_B, int max_N, pd_en
         PD_ALLOC(eng->d_c_recipm1, sizeof(float) * T);
         PD_ALLOC(eng->d_t_row, sizeof(int) * (size_t)max_B * max_N);
         PD_ALLOC(eng->d_xt, sizeof(float) * bn9);
+        PD_ALLOC(eng->d_nf, sizeof(int) * max_B);
+        eng->nf_host.assign(max_B, 0);
 #undef PD_ALLOC
         if (hipMemcpy(eng->d_c_recip, w->sqrt_recip_alphas_cumprod, sizeof(float) * T, hipMemcpyDeviceToDevice) != hipSuccess ||
             hipMemcpy(eng->d_c_recipm1, w->sqrt_recipm1_alphas_cumprod, sizeof(float) * T, hipMemcpyDeviceToDevice) != hipSuccess) {
@@ -330,6 +416,7 @@ extern "C" int pd_engine_set_q_tables(pd_engine *eng, const float *sqrt_alphas_c
 
 extern "C" int pd_denoise_step_t(pd_engine *eng, const float *x, const float *z, const int64_t *t_seq, int B, int N, float *out, void *stream) {
     PD_TRY(check_seq_args(eng, x, z, t_seq, B, N, "pd_denoise_step_t"));
+    PD_TRY(counts_unsupported(eng, "pd_denoise_step_t"));
     if (!out) {
         pd_set_error("pd_denoise_step_t: NULL output");
         return PD_ERR_INVALID_ARG;
@@ -343,6 +430,7 @@ extern "C" int pd_denoise_step_t(pd_engine *eng, const float *x, const float *z,
 extern "C" int pd_p_losses(pd_engine *eng, const float *x_start, const float *z, const int64_t *t_seq, const float *noise, int B, int N,
                            int loss_type, float *loss_out, float *x0_pred_out, float *xt_out, float *model_out, void *stream) {
     PD_TRY(check_seq_args(eng, x_start, z, t_seq, B, N, "pd_p_losses"));
+    PD_TRY(counts_unsupported(eng, "pd_p_losses"));
     if (!noise || !loss_out || (loss_type != 1 && loss_type != 2)) {
         pd_set_error("pd_p_losses: noise and loss_out must not be NULL, loss_type must be 1 (l1) or 2 (l2) (got %d)", loss_type);
         return PD_ERR_INVALID_ARG;
@@ -386,9 +474,11 @@ extern "C" int pd_p_finish(pd_engine *eng, const float *mean, const float *noise
         pd_set_error("pd_p_finish: invalid arguments");
         return PD_ERR_INVALID_ARG;
     }
+    const int *nf = nullptr;
+    PD_TRY(pd_frame_counts(eng, B, N, "pd_p_finish", &nf));
     const int n = B * N * 9;
     hipLaunchKernelGGL(pd_finish_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, mean, noise,
-                       expf(0.5f * eng->logvar[t]), n, x_out);
+                       expf(0.5f * eng->logvar[t]), n, x_out, nf, N);
     PD_HIP_CHECK(hipGetLastError());
     return PD_OK;
 }
@@ -539,6 +629,8 @@ extern "C" int pd_sample_phase(pd_engine *eng, const float *z, const float *nois
                 }
         }
     }
+    const int *nf = nullptr;      // frame counts per sequence: checked here once more, so that a graph replay cannot skip the check
+    PD_TRY(pd_frame_counts(eng, B, N, "pd_sample", &nf));
     hipStream_t s = (hipStream_t)stream;
     const int T = eng->timesteps;
     const size_t bn9 = (size_t)B * N * 9;
@@ -552,6 +644,8 @@ extern "C" int pd_sample_phase(pd_engine *eng, const float *z, const float *nois
         PD_HIP_CHECK(hipMemcpyAsync(eng->d_z, z, sizeof(float) * B * N * eng->z_dim, hipMemcpyDeviceToDevice, s));
         PD_HIP_CHECK(hipMemcpyAsync(eng->d_noise, noise, sizeof(float) * (T + 1) * bn9, hipMemcpyDeviceToDevice, s));
         PD_HIP_CHECK(hipMemcpyAsync(eng->d_process, noise, sizeof(float) * bn9, hipMemcpyDeviceToDevice, s));   // :289
+        // padding rows of the start sample: +0 like those of every later slice (no valid row reads them)
+        if (nf) hipLaunchKernelGGL(pd_zero_padding_kernel, dim3(((int)bn9 + 255) / 256), dim3(256), 0, s, eng->d_process, (int)bn9, nf, N);
     }
     if (has_ggs && phase != PD_PHASE_UNGUIDED) {
         int rc = pd_wait_uploads(eng, s);     // asynchronous match uploads issued on another stream
@@ -570,7 +664,8 @@ extern "C" int pd_sample_phase(pd_engine *eng, const float *z, const float *nois
         key.cond_start = has_ggs ? cond_start_step : 0;
         key.has_ggs = has_ggs;
         key.phase = phase;
-        key.den_split = eng->den_split | (eng->den_fused_attn << 8) | (eng->den_long_attn << 16);      // the options change the captured launches
+        key.den_split = eng->den_split | (eng->den_fused_attn << 8) | (eng->den_long_attn << 16) | ((nf ? 1 : 0) << 24);      // the options change the captured launches;
+        // so does "frame counts are set" (another attention kernel) -- the counts themselves are read from the engine's device array by every replay
         if (has_ggs) {
             key.cfg = *ggs;
             // the GGS nodes bake the match-derived launch shape in: a re-upload with another item count must not
@@ -711,6 +806,13 @@ extern "C" int pd_time_kernel(pd_engine *eng, int what, int B, int N, const pd_g
         PD_TRY(pd_ggs_frames_unsupported(eng, N, "pd_time_kernel"));
     }
     hipStream_t s = (hipStream_t)stream;
+    // the timed launches are the uniform ones, whatever frame counts are set (restored on every return)
+    struct CountsOff {
+        pd_engine *e;
+        int B;
+        explicit CountsOff(pd_engine *e_) : e(e_), B(e_->nf_B) { e->nf_B = 0; }
+        ~CountsOff() { e->nf_B = B; }
+    } counts_off(eng);
     hipEvent_t e0, e1;
     PD_HIP_CHECK(hipEventCreate(&e0));
     PD_HIP_CHECK(hipEventCreate(&e1));

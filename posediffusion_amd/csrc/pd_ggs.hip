@@ -113,6 +113,10 @@ static int plan_check_slots(pd_engine *eng, int B, int N, const pd_ggs_cfg *cfg,
         pd_set_error("pd_ggs: invalid arguments (B=%d N=%d)", B, N);
         return PD_ERR_INVALID_ARG;
     }
+    // frame counts per sequence (pd_engine_set_frame_counts): slot b must hold tables for ITS count -- the kernels take the frame count of a
+    // sequence from its descriptor and only the row stride of x from N
+    const int *nf_dev = nullptr;
+    PD_TRY(pd_frame_counts(eng, B, N, "pd_ggs", &nf_dev));
     max_items = 0;
     for (int b = 0; b < B; ++b) {
         const PdSeqDesc &d = eng->seqs[b].desc;
@@ -120,8 +124,10 @@ static int plan_check_slots(pd_engine *eng, int B, int N, const pd_ggs_cfg *cfg,
             pd_set_error("pd_ggs: sequence slot %d has no matches (call pd_ggs_set_matches)", b);
             return PD_ERR_STATE;
         }
-        if (d.n_frames != N) {
-            pd_set_error("pd_ggs: slot %d matches were uploaded for %d frames, called with N=%d", b, d.n_frames, N);
+        const int n_b = nf_dev ? eng->nf_host[b] : N;
+        if (d.n_frames != n_b) {
+            if (nf_dev) pd_set_error("pd_ggs: slot %d matches were uploaded for %d frames, its frame count (pd_engine_set_frame_counts) is %d", b, d.n_frames, n_b);
+            else pd_set_error("pd_ggs: slot %d matches were uploaded for %d frames, called with N=%d", b, d.n_frames, N);
             return PD_ERR_INVALID_ARG;
         }
         max_items = std::max(max_items, d.n_items);
@@ -305,7 +311,7 @@ static PdGgsParams launch_params(const pd_engine *eng, float *x, int B, int N, c
     memset(&P, 0, sizeof(P));
     P.seqs = eng->d_seqs;
     P.x = x;
-    P.N = N;
+    P.N = N;                        // the row stride of x / grad_out; a sequence's own frame count is its descriptor's n_frames
     P.k = plan.k;
     for (int i = 0; i < n_stages; ++i) P.stages[i] = stages[i];
     P.n_stages = n_stages;
@@ -336,6 +342,10 @@ int pd_ggs_launch(pd_engine *eng, float *x, int B, int N, const PdGgsStage *stag
                   float *loss_out, float *grad_out, hipStream_t s) {
     if (!eng || !x || !cfg || n_stages <= 0 || n_stages > PD_GGS_MAX_STAGES) {
         pd_set_error("pd_ggs: invalid arguments (B=%d N=%d stages=%d)", B, N, n_stages);
+        return PD_ERR_INVALID_ARG;
+    }
+    if (trace && eng->nf_B) {       // a trace row is N x 9 + 3 floats of ONE frame count
+        pd_set_error("pd_ggs_optimize: trace_out must be NULL while frame counts per sequence are set (pd_engine_set_frame_counts)");
         return PD_ERR_INVALID_ARG;
     }
     PdGgsPlan plan;

@@ -30,12 +30,12 @@ __global__ __launch_bounds__(NW * 64, NW > PD_GGS_WAVES ? 3 : PD_GGS_MIN_WAVES_P
     const int b = blockIdx.x % B, wg = blockIdx.x / B;   // XCD-aware: see header comment (B: the launch's sequences, padded to 8 if P.xchg_local)
     if (b >= P.n_seqs) return;                           // (padding blocks of the XCD-local placement)
     const PdSeqDesc D = P.seqs[b];
-    const int N = P.N, k = P.k;
+    const int N = D.n_frames, k = P.k;   // this sequence's own frame count (pd_ggs_plan checked it: P.N, or its entry of pd_engine_set_frame_counts); rows of x stay P.N apart
     const int nW = k * PD_GGS_WAVES;
     const int n_items = D.n_items;
     const Lds L = carve(smem, n_slots, pinc_rows, items_cap);
     const bool p3t = tid < PD_GGS_THREADS;            // takes part in the 512-thread roles of P3
-    float *xg = P.x + (size_t)b * N * PD_POSE_DIM;
+    float *xg = P.x + (size_t)b * P.N * PD_POSE_DIM;
     u64 *xchg = P.xchg ? P.xchg + (size_t)b * 2 * P.xchg_stride : nullptr;
 
     // wave 0, lane n owns frame n: parameters + momentum live in LDS (L.xst / L.mst) and visit registers only inside P4
@@ -572,12 +572,12 @@ __global__ __launch_bounds__(PD_GGS_THREADS) void pd_ggs2_kernel(PdGgsParams P, 
     const int b = blockIdx.x % B, wg = blockIdx.x / B;
     if (b >= P.n_seqs) return;
     const PdSeqDesc D = P.seqs[b];
-    const int N = P.N, k = P.k;
+    const int N = D.n_frames, k = P.k;   // this sequence's own frame count (pd_ggs_plan checked it: P.N, or its entry of pd_engine_set_frame_counts); rows of x stay P.N apart
     const int nW = k * PD_GGS_WAVES;
     const int n_items = D.n_items;          // == D.n_pairs (one item per pair)
     const int n_inc = 2 * D.n_pairs;
     const Lds L = carve(smem, n_slots, PD_GGS_PINC_ROWS, n_slots);
-    float *xg = P.x + (size_t)b * N * PD_POSE_DIM;
+    float *xg = P.x + (size_t)b * P.N * PD_POSE_DIM;
     u64 *xbase = P.xchg + (size_t)b * 2 * P.xchg_stride;
     // LDS reuse: L.item holds this workgroup's item sums [n_slots][12]; L.pinc rows [0, 2 n_slots <= 512) the results of
     // its pairs, rows [512, 576) the gathered rows of an owned frame, rows [640, 704) the gathered totals [k <= 256][4],

@@ -233,7 +233,7 @@ __global__ __launch_bounds__(PD_LANE_THREADS, PD_LANE_WAVES / 4) void pd_ggs_lan
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform to the compiler too: everything derived from it stays scalar
     const int b = blockIdx.x;
     const PdSeqDesc D = P.seqs[b];
-    const int N = P.N;
+    const int N = D.n_frames;                           // this sequence's own frame count (see pd_ggs_kernel); rows of x stay P.N apart
     const Lds L = carve_lane(smem, pinc_rows);
     if (tid == 0) {
         // launch stamps (PdGgsParams::stamp): workgroup 0's start now; the pointer waits in two spare words of L.psum for the end of the kernel
@@ -242,7 +242,7 @@ __global__ __launch_bounds__(PD_LANE_THREADS, PD_LANE_WAVES / 4) void pd_ggs_lan
         ((unsigned *)L.psum)[14] = (unsigned)(size_t)P.stamp;                       // (two 32-bit words: no alignment asked of L.psum)
         ((unsigned *)L.psum)[15] = (unsigned)((size_t)P.stamp >> 32);
     }
-    float *xg = P.x + (size_t)b * N * PD_POSE_DIM;
+    float *xg = P.x + (size_t)b * P.N * PD_POSE_DIM;
     const float smax = P.sampson_max;
 
     const bool own = (wave == 0 && lane < N);

@@ -1,5 +1,5 @@
 // P4 of one GGS iteration (textually included by the GGS kernels of pd_ggs.hip): wave 0, lane = frame.
-// In scope: L, P, S, D, N, b, wg, lane, wave, inv_M, stepped, trace_row, last_print, last_cnt, last_loss.  The parameters xr[9]
+// In scope: L, P, S, D, N (the sequence's own frame count; P.N is the row stride of x and grad_out), b, wg, lane, wave, inv_M, stepped, trace_row, last_print, last_cnt, last_loss.  The parameters xr[9]
 // and the momentum mom[9] of frame `lane` are loaded from / stored back to L.xst / L.mst here.
 // Reads the per-frame gradients L.gR / L.gT / L.gA and the totals L.cam[6] (sum s), L.cam[7] (n valid), L.ctl[2].
             // ---- P4 (wave 0): totals, early exit, quaternion/focal chain, clip, momentum SGD ----
@@ -73,7 +73,7 @@
                             int lo_ = lane;
                             asm volatile("" : "+v"(lo_));     // address arithmetic of this rare branch stays here (not hoisted: registers)
 #pragma unroll
-                            for (int c = 0; c < 9; ++c) P.grad_out[((size_t)b * N + lo_) * 9 + c] = g[c];
+                            for (int c = 0; c < 9; ++c) P.grad_out[((size_t)b * P.N + lo_) * 9 + c] = g[c];
                         }
                         if (lane == 0 && wg == 0) {
                             P.loss_out[b * 4 + 0] = loss;

@@ -2,7 +2,7 @@
 // lane = frame.  The backward phase already turned the per-frame sums into dL/dq (through the Jacobian an idle wave prepared, jac_all)
 // and the dL/dA partials arrive as one float4 per row wave, so what is left here is the short tail of GGS_optimize
 // (geometry_guided_sampling.py:104-122): totals, early exit, the focal-length chain, masked-norm clip, momentum SGD, decode.
-// In scope: L, P, S, D, N, b, wg, lane, wave, inv_M, stepped, trace_row.  Leaves {printed statistic, valid count, loss} in L.ctl[5..7].
+// In scope: L, P, S, D, N (the sequence's own frame count; P.N is the row stride of x and grad_out), b, wg, lane, wave, inv_M, stepped, trace_row.  Leaves {printed statistic, valid count, loss} in L.ctl[5..7].
 // Reads L.gq [frame][8] = {dL/dq (4), dL/dT (3), -} (zeros where the stage leaves R / T alone), L.gA[0..3] (dL/dA totals, update_FL
 // only: ga_parts partials of 4), L.cam[6] (sum s), L.cam[7] (n valid), L.ctl[2] (sum min(s, max)).
             if (wave == 0 && (PD_GGS_ABLATE & 8)) {
@@ -62,7 +62,7 @@
                             int lo_ = lane;
                             asm volatile("" : "+v"(lo_));     // address arithmetic of this rare branch stays here (not hoisted: registers)
 #pragma unroll
-                            for (int c = 0; c < 9; ++c) P.grad_out[((size_t)b * N + lo_) * 9 + c] = g[c];
+                            for (int c = 0; c < 9; ++c) P.grad_out[((size_t)b * P.N + lo_) * 9 + c] = g[c];
                         }
                         if (lane == 0 && wg == 0) {
                             P.loss_out[b * 4 + 0] = loss;

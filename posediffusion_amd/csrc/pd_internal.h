@@ -102,7 +102,8 @@ struct PdGgsStage {
 struct PdGgsParams {
     const PdSeqDesc *seqs;     // [B]
     float *x;                  // [B, N, 9] in/out
-    int N, k;                  // frames, workgroups per sequence
+    int N, k;                  // rows per sequence block of x / grad_out (= frames, unless frame counts per sequence are set: then the
+                               //   kernels read a sequence's own count from its descriptor, seqs[b].n_frames), workgroups per sequence
     PdGgsStage stages[PD_GGS_MAX_STAGES];
     int n_stages;
     float alpha, lr, sampson_max, momentum;
@@ -271,6 +272,10 @@ struct pd_engine {
     float *d_q_a = nullptr, *d_q_b = nullptr;             // [timesteps] sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod (pd_engine_set_q_tables)
     int *d_t_row = nullptr;                               // [max_B x max_N] timestep of every token row, clamped into [0, timesteps)
     float *d_xt = nullptr;                                // [max_B, max_N, 9] x_t of pd_p_losses when the caller does not ask for it
+    // frame counts per sequence (pd_engine_set_frame_counts): tensors stay padded [B, N, .], sequence b has nf_host[b] frames in rows 0 .. of its block
+    int nf_B = 0;                                         // 0: no counts set; else the B they were set for
+    std::vector<int> nf_host;                             // [max_B] host copy (validation, the GGS launch plan)
+    int *d_nf = nullptr;                                  // [max_B] device copy, at a fixed address: captured graphs read the counts of the day
     // GGS
     std::vector<PdSeqHost> seqs;
     PdSeqDesc *d_seqs = nullptr;         // [max_B] device copy of the descriptors
@@ -289,7 +294,7 @@ struct pd_engine {
     float *d_z = nullptr, *d_noise = nullptr, *d_process = nullptr, *d_mean = nullptr, *d_stats = nullptr;
     // graph cache
     struct GraphKey {
-        int B, N, cond_start, has_ggs, phase, den_split;
+        int B, N, cond_start, has_ggs, phase, den_split;   // (den_split: the denoiser options and "frame counts are set", packed)
         pd_ggs_cfg cfg;
         PdGgsPlan plan;            // match-derived launch shape baked into the captured GGS nodes
     };
@@ -360,6 +365,9 @@ void pd_ggs_free_seq(PdSeqHost &h);
 int pd_ggs_ingest_init();   // pd_ggs_ingest.hip: the device builder (pd_ggs_set_matches_csr_async)
 // pd_engine.hip: PD_ERR_UNSUPPORTED (and the message) for a GGS call with PD_MAX_FRAMES < N <= max_N, else PD_OK
 int pd_ggs_frames_unsupported(const pd_engine *eng, int N, const char *who);
+// pd_engine.hip: the frame counts in force for a call of (B, N): *nf_dev = null when none are set, else the device array after checking that
+// B is the B they were set for and every count lies in [1, N] (PD_ERR_INVALID_ARG naming the rule otherwise)
+int pd_frame_counts(const pd_engine *eng, int B, int N, const char *who, const int **nf_dev);
 // pd_engine.hip: the engine's stream-event bookkeeping (pd_engine::uses / uploads / retired_blobs)
 bool pd_stream_capturing(hipStream_t s);
 int pd_wait_uploads(pd_engine *eng, hipStream_t s);   // device-side wait for pending asynchronous match uploads (no-op in a capture)

@@ -100,8 +100,15 @@ class GaussianDiffusion(nn.Module):
         return eng.p_finish(mean, noise, int(t)), x0
 
     @torch.no_grad()
-    def p_sample_loop(self, shape, z, cond_fn=None, cond_start_step=0):
+    def p_sample_loop(self, shape, z, cond_fn=None, cond_start_step=0, n_frames=None):
+        """``n_frames`` (this package's extension; the reference's signature when omitted): [B] frame counts of a padded batch --
+        sequence b has n_frames[b] frames in rows 0 .. of its N-row block, padding rows of the results are 0; with guidance the
+        ``matches_dict`` of sequence b must come from n_frames[b] frames (``img_shape[0]``)."""
         B, N, _ = shape
+        if n_frames is not None:
+            n_frames = [int(v) for v in (n_frames.tolist() if hasattr(n_frames, 'tolist') else n_frames)]
+            if len(n_frames) != B or min(n_frames) < 1 or max(n_frames) > N:
+                raise ValueError(f"n_frames must hold one count in [1, {N}] per sequence ({B}), got {n_frames}")
         device = self.betas.device
         parsed = host.parse_ggs_cond_fn(cond_fn) if cond_fn is not None else None
         # demo.py:79-92: hloc returning no matches (kp1 is None) means sampling without GGS
@@ -119,6 +126,9 @@ class GaussianDiffusion(nn.Module):
             # the denoiser takes up to 256 frames, GGS 64 (include/pd_engine.h): no silent fallback to unguided sampling
             raise RuntimeError(f"guided sampling (GGS) is limited to {host.GGS_MAX_FRAMES} frames, got {N}: run unguided (GGS.enable=False)")
         eng = host.get_engine(self.model, self, B, N)
+        if cond_fn is not None and parsed is None and n_frames is not None:
+            raise NotImplementedError("n_frames with a guidance callable other than the shipped geometry_guided_sampling partial: "
+                                      "a callable sees one padded [B, N, 9] tensor and cannot know the counts")
         if cond_fn is not None and parsed is None:
             # unknown guidance callable: reference control flow in Python, arithmetic on the HIP kernels
             pose = torch.randn(shape, device=device)
@@ -131,8 +141,8 @@ class GaussianDiffusion(nn.Module):
         cfg = None
         if has_ggs:
             matches, cfg = parsed
-            host.upload_matches(eng, matches, B)
-        pose, process, stats = eng.sample(z, noise, cond_start_step if has_ggs else 0, cfg, use_graph=self.use_graph)
+            host.upload_matches(eng, matches, B, n_frames)
+        pose, process, stats = eng.sample(z, noise, cond_start_step if has_ggs else 0, cfg, use_graph=self.use_graph, n_frames=n_frames)
         self.last_ggs_stats = stats
         if has_ggs:
             # the GGS workgroups of a sequence exchange sums through bounded spins; one that gave up (co-residency lost
@@ -146,8 +156,8 @@ class GaussianDiffusion(nn.Module):
         return pose, process
 
     @torch.no_grad()
-    def sample(self, shape, z, cond_fn=None, cond_start_step=0):
-        return self.p_sample_loop(shape, z=z, cond_fn=cond_fn, cond_start_step=cond_start_step)
+    def sample(self, shape, z, cond_fn=None, cond_start_step=0, n_frames=None):
+        return self.p_sample_loop(shape, z=z, cond_fn=cond_fn, cond_start_step=cond_start_step, n_frames=n_frames)
 
     # ---- training branch, forward half (:308-332): q_sample, the denoiser and the loss as one pass on the engine ----------------------
     @torch.no_grad()

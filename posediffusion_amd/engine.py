@@ -6,6 +6,7 @@ path -- constructing an engine without a GPU or without the built library raises
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 from typing import Dict, Optional, Sequence, Tuple
 
@@ -135,14 +136,43 @@ class PoseEngine:
     def check_async(self):
         _lib.check(self.lib.pd_check_async_error(self._h), "pd_check_async_error")
 
+    # ---------------------------------------------------------------- frame counts per sequence
+    def set_frame_counts(self, n_frames=None):
+        """pd_engine_set_frame_counts: ``n_frames`` [B] ints -- sequence b of every later call with that B has n_frames[b] frames, in rows
+        0 .. n_frames[b]-1 of its N-row block; the other rows are padding (outputs hold +0 there).  ``None`` clears.  Ordered on the
+        current stream, no synchronisation."""
+        if n_frames is None:
+            _lib.check(self.lib.pd_engine_set_frame_counts(self._h, 0, None, self._stream()), "pd_engine_set_frame_counts")
+            return
+        if isinstance(n_frames, torch.Tensor):
+            n_frames = n_frames.detach().cpu().tolist()
+        counts = [int(v) for v in n_frames]
+        arr = (C.c_int32 * max(len(counts), 1))(*counts)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.pd_engine_set_frame_counts(self._h, len(counts), arr, self._stream()), "pd_engine_set_frame_counts")
+
+    @contextlib.contextmanager
+    def _counts(self, n_frames):
+        """The ``n_frames=`` keyword of the calls below: set for the call, cleared afterwards (also when the call raises)."""
+        if n_frames is None:
+            yield
+            return
+        self.set_frame_counts(n_frames)
+        try:
+            yield
+        finally:
+            self.set_frame_counts(None)
+
     # ---------------------------------------------------------------- denoiser / DDPM
-    def denoise(self, x: torch.Tensor, z: torch.Tensor, t: int) -> torch.Tensor:
-        """Denoiser.forward (models/denoiser.py:53-76) for one shared timestep t."""
+    def denoise(self, x: torch.Tensor, z: torch.Tensor, t: int, n_frames=None) -> torch.Tensor:
+        """Denoiser.forward (models/denoiser.py:53-76) for one shared timestep t.  ``n_frames`` [B]: frame counts per sequence
+        (see ``set_frame_counts``), here and on every call below that takes it."""
         B, N, _ = x.shape
         x, z = self._f32(x, (B, N, 9)), self._f32(z, (B, N, self.z_dim))
         out = torch.empty_like(x)
-        _lib.check(self.lib.pd_denoise_step(self._h, x.data_ptr(), z.data_ptr(), int(t), B, N, out.data_ptr(),
-                                            self._stream()), "pd_denoise_step")
+        with self._counts(n_frames):
+            _lib.check(self.lib.pd_denoise_step(self._h, x.data_ptr(), z.data_ptr(), int(t), B, N, out.data_ptr(),
+                                                self._stream()), "pd_denoise_step")
         return out
 
     def _t_seq(self, t, B: int) -> torch.Tensor:
@@ -176,22 +206,24 @@ class PoseEngine:
                                         out["model_out"].data_ptr(), self._stream()), "pd_p_losses")
         return out
 
-    def p_mean(self, x: torch.Tensor, z: torch.Tensor, t: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    def p_mean(self, x: torch.Tensor, z: torch.Tensor, t: int, n_frames=None) -> Tuple[torch.Tensor, torch.Tensor]:
         """(model_mean, x_start) of p_mean_variance (models/gaussian_diffuser.py:231-246)."""
         B, N, _ = x.shape
         x, z = self._f32(x, (B, N, 9)), self._f32(z, (B, N, self.z_dim))
         mean, x0 = torch.empty_like(x), torch.empty_like(x)
-        _lib.check(self.lib.pd_p_mean(self._h, x.data_ptr(), z.data_ptr(), int(t), B, N, mean.data_ptr(), x0.data_ptr(),
-                                      self._stream()), "pd_p_mean")
+        with self._counts(n_frames):
+            _lib.check(self.lib.pd_p_mean(self._h, x.data_ptr(), z.data_ptr(), int(t), B, N, mean.data_ptr(), x0.data_ptr(),
+                                          self._stream()), "pd_p_mean")
         return mean, x0
 
-    def p_finish(self, mean: torch.Tensor, noise: Optional[torch.Tensor], t: int) -> torch.Tensor:
+    def p_finish(self, mean: torch.Tensor, noise: Optional[torch.Tensor], t: int, n_frames=None) -> torch.Tensor:
         B, N, _ = mean.shape
         mean = self._f32(mean)
         noise = None if noise is None else self._f32(noise, mean.shape)
         out = torch.empty_like(mean)
-        _lib.check(self.lib.pd_p_finish(self._h, mean.data_ptr(), _ptr(noise), int(t), B, N, out.data_ptr(),
-                                        self._stream()), "pd_p_finish")
+        with self._counts(n_frames):
+            _lib.check(self.lib.pd_p_finish(self._h, mean.data_ptr(), _ptr(noise), int(t), B, N, out.data_ptr(),
+                                            self._stream()), "pd_p_finish")
         return out
 
     # ---------------------------------------------------------------- GGS
@@ -243,47 +275,62 @@ class PoseEngine:
         keep[:] = [(e, ts) for e, ts in keep if not e.query()]
         keep.append((ev, (kp1, kp2, i12)))
 
-    def ggs_guide(self, model_mean: torch.Tensor, t: int, cfg=None) -> Tuple[torch.Tensor, torch.Tensor]:
-        """geometry_guided_sampling(model_mean, t, ...) for every sequence b (match slot b)."""
+    def ggs_guide(self, model_mean: torch.Tensor, t: int, cfg=None, n_frames=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """geometry_guided_sampling(model_mean, t, ...) for every sequence b (match slot b).  With ``n_frames`` slot b must hold the
+        matches of a sequence of n_frames[b] frames; padding rows of ``model_mean`` come back untouched."""
         B, N, _ = model_mean.shape
         x = self._f32(model_mean).clone()
         stats = torch.zeros(B, 5, 4, device=self.device)
         c = cfg if isinstance(cfg, _lib.pd_ggs_cfg) else make_ggs_cfg(cfg)
-        _lib.check(self.lib.pd_ggs_guide(self._h, x.data_ptr(), B, N, int(t), C.byref(c), stats.data_ptr(), self._stream()),
-                   "pd_ggs_guide")
+        with self._counts(n_frames):
+            _lib.check(self.lib.pd_ggs_guide(self._h, x.data_ptr(), B, N, int(t), C.byref(c), stats.data_ptr(), self._stream()),
+                       "pd_ggs_guide")
         return x, stats
 
+    def ggs_plan(self, B: int, N: int, cfg=None, n_frames=None):
+        """pd_debug_ggs_plan: {workgroups per sequence, item slots, LDS bytes, two-hop, waves, staging pieces, lane kernel, its LDS steps}."""
+        c = cfg if isinstance(cfg, _lib.pd_ggs_cfg) else make_ggs_cfg(cfg)
+        out = (C.c_int * 8)()
+        with self._counts(n_frames):
+            _lib.check(self.lib.pd_debug_ggs_plan(self._h, int(B), int(N), C.byref(c), out), "pd_debug_ggs_plan")
+        return [int(v) for v in out]
+
     def ggs_optimize(self, model_mean: torch.Tensor, update_R=True, update_T=True, update_FL=True, cfg=None,
-                     trace: bool = False):
+                     trace: bool = False, n_frames=None):
         B, N, _ = model_mean.shape
         x = self._f32(model_mean).clone()
         c = cfg if isinstance(cfg, _lib.pd_ggs_cfg) else make_ggs_cfg(cfg)
         iters = c.iter_num * (2 if (update_R and update_T and update_FL) else 1)
         stats = torch.zeros(B, 1, 4, device=self.device)
         tr = torch.zeros(B, max(iters, 1), N * 9 + 3, device=self.device) if trace else None
-        _lib.check(self.lib.pd_ggs_optimize(self._h, x.data_ptr(), B, N, int(update_R), int(update_T), int(update_FL),
-                                            C.byref(c), stats.data_ptr(), _ptr(tr), self._stream()), "pd_ggs_optimize")
+        with self._counts(n_frames):
+            _lib.check(self.lib.pd_ggs_optimize(self._h, x.data_ptr(), B, N, int(update_R), int(update_T), int(update_FL),
+                                                C.byref(c), stats.data_ptr(), _ptr(tr), self._stream()), "pd_ggs_optimize")
         return x, stats[:, 0], tr
 
-    def ggs_loss_grad(self, x: torch.Tensor, update_R=True, update_T=True, update_FL=True, cfg=None):
+    def ggs_loss_grad(self, x: torch.Tensor, update_R=True, update_T=True, update_FL=True, cfg=None, n_frames=None):
         B, N, _ = x.shape
         x = self._f32(x)
         c = cfg if isinstance(cfg, _lib.pd_ggs_cfg) else make_ggs_cfg(cfg)
         loss = torch.zeros(B, 4, device=self.device)
         grad = torch.zeros_like(x)
-        _lib.check(self.lib.pd_ggs_loss_grad(self._h, x.data_ptr(), B, N, int(update_R), int(update_T), int(update_FL),
-                                             C.byref(c), loss.data_ptr(), grad.data_ptr(), self._stream()), "pd_ggs_loss_grad")
+        with self._counts(n_frames):
+            _lib.check(self.lib.pd_ggs_loss_grad(self._h, x.data_ptr(), B, N, int(update_R), int(update_T), int(update_FL),
+                                                 C.byref(c), loss.data_ptr(), grad.data_ptr(), self._stream()), "pd_ggs_loss_grad")
         return loss, grad
 
     # ---------------------------------------------------------------- sampler
     def sample(self, z: torch.Tensor, noise: torch.Tensor, cond_start_step: int = 0, ggs_cfg=None,
-               use_graph: bool = True, want_process: bool = True, phase: int = 0, out=None):
+               use_graph: bool = True, want_process: bool = True, phase: int = 0, out=None, n_frames=None):
         """GaussianDiffusion.sample (models/gaussian_diffuser.py:284-306).  ``noise`` is
         [T+1,B,N,9]: noise[0] the initial randn, noise[1+k] the randn_like of step t = T-1-k.
 
         ``phase`` (pd_engine.h PD_PHASE_*): 0 = the whole loop; 1 = inputs + unguided steps only,
         2 = guided steps + results.  A phase-2 call takes the ``(pose, process, stats)`` tuple the
-        phase-1 call returned as ``out`` (the buffers are written by phase 2 only)."""
+        phase-1 call returned as ``out`` (the buffers are written by phase 2 only).
+
+        ``n_frames`` [B]: frame counts per sequence (``set_frame_counts``): set for this call and cleared after it; both halves of a
+        split call take the same counts."""
         B, N, _ = z.shape
         T = self.timesteps
         z = self._f32(z, (B, N, self.z_dim))
@@ -298,10 +345,11 @@ class PoseEngine:
             stats = torch.zeros(max(cond_start_step, 1), B, 5, 4, device=self.device) if has_ggs else None
         else:
             pose, process, stats = out
-        _lib.check(self.lib.pd_sample_phase(self._h, z.data_ptr(), noise.data_ptr(), B, N, int(cond_start_step),
-                                            C.byref(c) if c is not None else None, int(phase), pose.data_ptr(),
-                                            _ptr(process), _ptr(stats), int(bool(use_graph)), self._stream()),
-                   "pd_sample_phase")
+        with self._counts(n_frames):
+            _lib.check(self.lib.pd_sample_phase(self._h, z.data_ptr(), noise.data_ptr(), B, N, int(cond_start_step),
+                                                C.byref(c) if c is not None else None, int(phase), pose.data_ptr(),
+                                                _ptr(process), _ptr(stats), int(bool(use_graph)), self._stream()),
+                       "pd_sample_phase")
         return pose, process, stats
 
     def set_split_precision(self, mode):

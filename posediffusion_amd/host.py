@@ -159,10 +159,11 @@ def has_matches(md) -> bool:
     return md is not None and md.get("kp1") is not None and len(md["kp1"]) > 0
 
 
-def upload_matches(engine: PoseEngine, matches, B: int):
+def upload_matches(engine: PoseEngine, matches, B: int, n_frames=None):
     """matches: one reference-style matches_dict (B == 1) or a list of B of them.  Uploads are cached per slot so
     the five calls per guided step upload once: a slot is skipped only when it still holds the SAME arrays (the cache
-    keeps references, so their ids cannot be recycled) with the same content fingerprint."""
+    keeps references, so their ids cannot be recycled) with the same content fingerprint.  Every sequence is uploaded with ITS
+    frame count, ``img_shape[0]``; ``n_frames`` [B] (the counts of a padded batch) must agree with it."""
     lst = list(matches) if isinstance(matches, (list, tuple)) else [matches]
     if len(lst) != B:
         raise ValueError(f"GGS needs one matches_dict per sequence: got {len(lst)} for B={B} "
@@ -172,6 +173,9 @@ def upload_matches(engine: PoseEngine, matches, B: int):
         if not has_matches(md):
             raise ValueError(f"matches_dict of sequence {b} holds no matches (kp1 is None or empty); "
                              "call the sampler without cond_fn for such a sequence (demo.py:79-92)")
+        if n_frames is not None and int(md["img_shape"][0]) != int(n_frames[b]):
+            raise ValueError(f"matches_dict of sequence {b} was extracted from {int(md['img_shape'][0])} frames (img_shape[0]), "
+                             f"its frame count is {int(n_frames[b])}")
         fp = _match_fingerprint(md)
         ent = cache.get(b)
         if ent is not None and ent[0] is md["kp1"] and ent[1] is md["kp2"] and ent[2] is md["i12"] and ent[3] == fp:

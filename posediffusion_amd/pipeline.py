@@ -182,13 +182,16 @@ class SamplingPipeline:
 
     def submit(self, z: torch.Tensor, noise: torch.Tensor, cond_start_step: int = 0, ggs_cfg=None,
                use_graph: bool = True, want_process: bool = False,
-               inputs_ready: Optional[torch.cuda.Event] = None) -> PendingSample:
+               inputs_ready: Optional[torch.cuda.Event] = None, n_frames=None) -> PendingSample:
         """Enqueue GaussianDiffusion.sample for one batch; returns immediately.
 
         ``z`` / ``noise`` must be complete when the unguided stream reaches them: pass the event that
         follows their producer as ``inputs_ready`` (or synchronise before submitting).  The pipeline
         deliberately does not touch the caller's current stream: a marker on the default stream can
-        sit behind a guided half when the two share a hardware queue, which stalls the whole pipe."""
+        sit behind a guided half when the two share a hardware queue, which stalls the whole pipe.
+
+        ``n_frames`` [B]: frame counts per sequence of this padded batch (PoseEngine.set_frame_counts); each half sets them on its own
+        stream just before its launches, so batches with other counts may follow on the same context."""
         i = self._submitted
         j = i % self.contexts
         eng = self.engines[j]
@@ -206,9 +209,9 @@ class SamplingPipeline:
             if tr:
                 tr[0].record(us)
             if not guided:
-                out = eng.sample(z, noise, cond_start_step, ggs_cfg, use_graph=use_graph, want_process=want_process)
+                out = eng.sample(z, noise, cond_start_step, ggs_cfg, use_graph=use_graph, want_process=want_process, n_frames=n_frames)
             else:
-                out = eng.sample(z, noise, cond_start_step, ggs_cfg, use_graph=use_graph, want_process=want_process, phase=1)
+                out = eng.sample(z, noise, cond_start_step, ggs_cfg, use_graph=use_graph, want_process=want_process, phase=1, n_frames=n_frames)
         if tr:
             tr[1].record(us)
         if gs is not us:
@@ -221,7 +224,7 @@ class SamplingPipeline:
                 tr[2].record(gs)
             if guided:
                 out = eng.sample(z, noise, cond_start_step, ggs_cfg, use_graph=use_graph, want_process=want_process,
-                                 phase=2, out=out)
+                                 phase=2, out=out, n_frames=n_frames)
             if tr:
                 tr[3].record(gs)
                 self._trace.append(tr)
