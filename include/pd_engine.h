@@ -130,6 +130,10 @@ typedef struct pd_ggs_cfg {
 #define PD_GGS_CFG_XCHG_SPREAD 32     /* pd_ggs_cfg.reserved: with several workgroups per sequence, do NOT place a sequence's workgroups on one XCD
                                        * (where the engine would: at most 32 of them per XCD) -- the exchange then goes through write-through
                                        * agent-scope stores as in rounds 1-3; bitwise the same results -- comparison / testing */
+#define PD_GGS_CFG_LONG_FRAMES 64     /* pd_ggs_cfg.reserved: run the kernel for sequences of more than 64 frames (pd_ggs_long_kernel: the two-hop
+                                       * scheme with frame tables for 256 frames, one thread per frame in the update phase) at any N; at
+                                       * N <= 64 bitwise the two-hop kernel's results -- comparison / testing.  Its requirements are those
+                                       * listed under PD_OPT_GGS_MAX_FRAMES */
 
 /* ---- lifecycle -------------------------------------------------------------------------- */
 
@@ -137,10 +141,11 @@ typedef struct pd_ggs_cfg {
  * load_state_dict of demo.py:46,56-57 for the sampling path.  Synchronous.
  * max_B sequences x max_N frames bound every later call (workspaces are sized once).
  * Two frame limits: the denoiser, the training-branch forward and UNGUIDED sampling take up to 256 frames (max_N in [1, 256]; above 64
- * frames attention runs the key-tiled kernel of csrc/pd_attn_long.h); GGS takes up to 64.  On an engine created for more than 64
- * frames every GGS call with 64 < N <= max_N -- pd_ggs_set_matches / _csr_async, pd_ggs_guide / _optimize / _loss_grad, pd_sample* with
- * ggs != NULL and cond_start_step > 0 -- returns PD_ERR_UNSUPPORTED with a message naming the 64-frame GGS limit, before anything is
- * launched or allocated; the engine stays usable, and GGS at N <= 64 works on it as on any other. */
+ * frames attention runs the key-tiled kernel of csrc/pd_attn_long.h); GGS takes up to 64 by default and up to max_N once the engine
+ * option PD_OPT_GGS_MAX_FRAMES is raised (opt-in: the exchange region of a 256-frame sequence is 33.7 MB per slot).  With the limit at v,
+ * every GGS call with v < N <= max_N -- pd_ggs_set_matches / _csr_async, pd_ggs_guide / _optimize / _loss_grad, pd_sample* with
+ * ggs != NULL and cond_start_step > 0 -- returns PD_ERR_UNSUPPORTED with a message naming the v-frame GGS limit, before anything is
+ * launched or allocated; the engine stays usable, and GGS at N <= v works on it as on any other. */
 int pd_engine_create(const pd_weights *w, int max_B, int max_N, pd_engine **out);
 void pd_engine_destroy(pd_engine *eng);
 const char *pd_last_error(void);
@@ -209,8 +214,10 @@ int pd_p_losses(pd_engine *eng, const float *x_start, const float *z, const int6
  *             touched.  trace_out must be NULL (PD_ERR_INVALID_ARG).  The launch plan stays what it is -- ONE launch of ONE kernel family,
  *             decided over the slots together: the lane-per-item kernel needs lane tables in every slot, the two-hop kernel several chunks
  *             of pairs in every slot.  Where the plan refuses a mix the call returns the plan's PD_ERR_UNSUPPORTED and the engine stays
- *             usable: GROUPING SEQUENCES INTO LAUNCHES THE PLAN ACCEPTS IS THE CALLER'S JOB.  The 64-frame GGS limit and the 256-frame
- *             denoiser limit are unchanged.
+ *             usable: GROUPING SEQUENCES INTO LAUNCHES THE PLAN ACCEPTS IS THE CALLER'S JOB.  The GGS frame limit (64, or PD_OPT_GGS_MAX_FRAMES)
+ *             applies to N and the 256-frame denoiser limit is unchanged.  With the option raised, a launch in which any slot's count
+ *             exceeds 64 runs pd_ggs_long_kernel for ALL its slots; that kernel does not need several chunks of pairs in a slot, so short
+ *             sequences with few pairs share such a launch.
  *   graphs    "counts are set" is part of the key of a captured loop, the counts are not: a loop replayed after another
  *             pd_engine_set_frame_counts with the same B uses the new counts.
  *   errors    a count outside [1, N] and a call whose B differs from the B of the counts: PD_ERR_INVALID_ARG (the message names the rule);
@@ -319,6 +326,17 @@ int pd_ggs_loss_grad(pd_engine *eng, const float *x, int B, int N, int update_R,
  *        is 1.  At N <= 64 the default-shape tiled kernel performs the operations of pd_attn_kernel / pd_attn_seq_kernel in their order:
  *        bitwise the same results (the MFMA attention of the fp16-plane mode at N <= 32 sums in another order: rounding-level). */
 #define PD_OPT_DENOISER_LONG_ATTN 6
+/*   PD_OPT_GGS_MAX_FRAMES  the most frames GGS admits on this engine: 64 (default) or any value in (64, max_N].  Above 64 frames GGS runs
+ *        pd_ggs_long_kernel (the two-hop scheme of the 33 .. 64-frame kernel: per-frame sums in a fixed order that does not depend on the
+ *        workgroup count).  Setting the option is SYNCHRONOUS: it waits for the device, reallocates the exchange region to
+ *        (2 v^2 + 512) lines of 128 bytes per sequence slot and epoch (v = 256: 33.7 MB per slot; 64: 2.2 MB) and drops the cached
+ *        hipGraphs.  If that allocation fails it returns PD_ERR_HIP and the previous limit and region stay in force; any other value
+ *        returns PD_ERR_INVALID_ARG.  A launch above 64 frames needs, and is refused with PD_ERR_UNSUPPORTED naming the number otherwise:
+ *        every frame pair <= 512 matches; 2 <= workgroups per sequence <= 256 (so B <= CUs / 2; wgs_per_seq = 1 is refused); the item
+ *        slots of a workgroup, ceil(pairs / (8 wgs)) x 8, within its LDS image (<= 208); 2 pairs + wgs + N exchange lines within the
+ *        region.  Matches of such sequences are uploaded with pd_ggs_set_matches; pd_ggs_set_matches_csr_async stays limited to 64
+ *        frames (PD_ERR_UNSUPPORTED above).  Every launch at N <= 64 is what it is without the option. */
+#define PD_OPT_GGS_MAX_FRAMES 7
 int pd_engine_set_option(pd_engine *eng, int option, int value);
 /* Reads an option back.  PD_OPT_DENOISER_SPLIT: the mode in force (an engine created from weights that hold inf / NaN stays on 0 although
  * it is large enough for 2 -- the only downgrade pd_engine_create performs by itself; PD_OPT_WEIGHTS_NON_FINITE (read-only) then reads 1). */
@@ -331,8 +349,8 @@ int pd_engine_get_option(pd_engine *eng, int option, int *value_out);
  *          noise[1+k] = the randn_like of step t = T-1-k (:278); slots the reference never
  *          draws (t == 0, guided steps) are ignored.
  *   cond_start_step / ggs: if ggs != NULL, steps with t < cond_start_step run pd_ggs_guide on
- *          the model mean with noise = 0 (:270-276); ggs == NULL = unguided.  Unguided: N <= 256; guided: N <= 64
- *          (PD_ERR_UNSUPPORTED above, on an engine created for more than 64 frames).
+ *          the model mean with noise = 0 (:270-276); ggs == NULL = unguided.  Unguided: N <= 256; guided: N <= 64, or
+ *          <= the engine's PD_OPT_GGS_MAX_FRAMES (PD_ERR_UNSUPPORTED above that limit).
  *   pose_out    [B,N,9]       DEVICE
  *   process_out [T+1,B,N,9]   DEVICE, may be NULL
  *   stats_out   [cond_start_step,B,5,4] DEVICE, may be NULL (see pd_ggs_guide), ordered by

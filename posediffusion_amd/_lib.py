@@ -61,10 +61,12 @@ PD_WEIGHTS_GENERIC = 8       # the shape-generic denoiser path even at the defau
 PD_GGS_CFG_LANE_ITEMS = 8       # lane-per-item kernel (the throughput shape) whatever the batch size
 PD_GGS_CFG_NO_LANE_ITEMS = 16   # never the lane-per-item kernel
 PD_GGS_CFG_XCHG_SPREAD = 32     # k > 1: no XCD-local placement of a sequence's workgroups (comparison)
+PD_GGS_CFG_LONG_FRAMES = 64     # the kernel of sequences above 64 frames at any N (comparison / testing)
 PD_OPT_DENOISER_SPLIT = 2
 PD_OPT_WEIGHTS_NON_FINITE = 4   # pd_engine_get_option only
 PD_OPT_DENOISER_FUSED_ATTN = 5  # in_proj + attention as one kernel, Q / K / V in LDS (default 1)
 PD_OPT_DENOISER_LONG_ATTN = 6   # 1: the key-tiled attention kernel of sequences above 64 frames for every N (default 0; comparison / testing)
+PD_OPT_GGS_MAX_FRAMES = 7       # frames GGS admits: 64 (default) or a value in (64, max_N]; reallocates the exchange region, synchronous
 PD_MATCH_HINT_ONE_ORDER = 1 << 30   # pd_match_hints.max_pairs flag: every frame pair in one order only (hloc's i < j pairs)
 
 

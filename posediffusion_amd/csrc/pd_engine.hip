@@ -274,6 +274,9 @@ extern "C" void pd_engine_destroy(pd_engine *eng) {
     delete eng;
 }
 
+// granules per (sequence slot, epoch) of the GGS exchange region for sequences of up to ggs_N frames: (2 N^2 + 512) lines of 16
+static size_t xchg_granules_for(int ggs_N) { return (size_t)(2 * ggs_N * ggs_N + 512) * 16; }
+
 extern "C" int pd_engine_create(const pd_weights *w, int max_B, int max_N, pd_engine **out) {
     if (!w || !out || max_B <= 0 || max_N <= 0 || max_N > PD_MAX_DENOISER_FRAMES || w->timesteps <= 0 || w->timesteps > 4096) {
         pd_set_error("pd_engine_create: invalid arguments (max_B=%d, max_N=%d must be in [1,%d])", max_B, max_N, PD_MAX_DENOISER_FRAMES);
@@ -334,8 +337,7 @@ extern "C" int pd_engine_create(const pd_weights *w, int max_B, int max_N, pd_en
         // one 128-byte line (16 granules) per item; the two-hop kernel lays out (pair, side) lines (both orders of every
         // pair: < 2 N^2) + one line per workgroup + one per frame in the same buffer
         // (GGS only, so sized by its own frame limit: an engine for 256 frames would otherwise hold 34 MB per slot for nothing)
-        const int ggs_N = std::min(max_N, PD_MAX_FRAMES);
-        eng->xchg_granules = (size_t)(2 * ggs_N * ggs_N + 512) * 16;
+        eng->xchg_granules = xchg_granules_for(std::min(max_N, PD_MAX_FRAMES));
 #define PD_ALLOC(ptr, bytes)                                             \
     if (hipMalloc((void **)&(ptr), (bytes)) != hipSuccess) {             \
         pd_set_error("pd_engine_create: hipMalloc of %zu B failed", (size_t)(bytes)); \
@@ -501,13 +503,14 @@ extern "C" int pd_pose_to_camera(pd_engine *eng, const float *enc, int n_cameras
 }
 
 // ---- GGS API ------------------------------------------------------------------------------------
-// GGS stops at PD_MAX_FRAMES = 64 frames (one lane per frame in its update phase, pair tables in chunks), the denoiser at
-// PD_MAX_DENOISER_FRAMES = 256: on an engine created for more than 64 frames a GGS call with 64 < N <= max_N is refused before
-// anything is launched or allocated.  (N > max_N stays PD_ERR_INVALID_ARG, reported by the call's own argument check.)
+// GGS stops at the engine's PD_OPT_GGS_MAX_FRAMES -- PD_MAX_FRAMES = 64 frames unless the option was raised (the kernels for up to 64
+// frames hold one lane per frame in their update phase and pair tables in chunks; pd_ggs_long_kernel takes up to 256) --, the denoiser at
+// PD_MAX_DENOISER_FRAMES = 256: a GGS call with that limit < N <= max_N is refused before anything is launched or allocated.
+// (N > max_N stays PD_ERR_INVALID_ARG, reported by the call's own argument check.)
 int pd_ggs_frames_unsupported(const pd_engine *eng, int N, const char *who) {
-    if (!eng || N <= PD_MAX_FRAMES || N > eng->max_N) return PD_OK;
+    if (!eng || N <= eng->ggs_max_frames || N > eng->max_N) return PD_OK;
     pd_set_error("%s: geometry-guided sampling (GGS) is limited to %d frames (N=%d); the denoiser and unguided sampling take up to %d "
-                 "frames: sample without GGS", who, PD_MAX_FRAMES, N, PD_MAX_DENOISER_FRAMES);
+                 "frames: sample without GGS", who, eng->ggs_max_frames, N, PD_MAX_DENOISER_FRAMES);
     return PD_ERR_UNSUPPORTED;
 }
 static void guide_stages(const pd_ggs_cfg *cfg, PdGgsStage *st) {
@@ -765,6 +768,33 @@ extern "C" int pd_engine_set_option(pd_engine *eng, int option, int value) {
         }
         eng->den_long_attn = value;
         break;
+    case PD_OPT_GGS_MAX_FRAMES: {
+        if (value != PD_MAX_FRAMES && !(value > PD_MAX_FRAMES && value <= eng->max_N && value <= PD_GGS_LONG_MAX_FRAMES)) {
+            pd_set_error("pd_engine_set_option: PD_OPT_GGS_MAX_FRAMES takes %d (the default) or a value in (%d, max_N=%d] with max_N <= %d (got %d)",
+                         PD_MAX_FRAMES, PD_MAX_FRAMES, eng->max_N, PD_GGS_LONG_MAX_FRAMES, value);
+            return PD_ERR_INVALID_ARG;
+        }
+        // synchronous: nothing of this engine may still use the exchange region, and the captured GGS nodes hold its address
+        PD_HIP_CHECK(hipSetDevice(eng->device));
+        PD_HIP_CHECK(hipDeviceSynchronize());
+        const size_t granules = xchg_granules_for(std::min(value, eng->max_N));
+        if (granules != eng->xchg_granules) {
+            unsigned long long *fresh = nullptr;
+            if (hipMalloc((void **)&fresh, sizeof(unsigned long long) * 2 * granules * eng->max_B) != hipSuccess) {
+                (void)hipGetLastError();
+                pd_set_error("pd_engine_set_option: PD_OPT_GGS_MAX_FRAMES = %d: hipMalloc of %zu B for the exchange region failed; the limit stays %d",
+                             value, sizeof(unsigned long long) * 2 * granules * eng->max_B, eng->ggs_max_frames);
+                return PD_ERR_HIP;
+            }
+            (void)hipFree(eng->d_xchg);
+            eng->d_xchg = fresh;
+            eng->xchg_granules = granules;
+        }
+        for (auto &g : eng->graphs) (void)hipGraphExecDestroy(g.second);
+        eng->graphs.clear();
+        eng->ggs_max_frames = value;
+        break;
+    }
     case 3:      // (PD_OPT_DENOISER_PERSISTENT of round 3: the persistent small-batch kernel was measured 2.4 x slower and parked, tools/parked/)
         if (value == 0) break;
         pd_set_error("pd_engine_set_option: option 3 (the persistent small-batch denoiser launch of round 3) is no longer built: it measured "
@@ -774,7 +804,7 @@ extern "C" int pd_engine_set_option(pd_engine *eng, int option, int value) {
         pd_set_error("pd_engine_set_option: unknown option %d", option);
         return PD_ERR_INVALID_ARG;
     }
-    return PD_OK;      // (captured graphs are keyed on the option: nothing to drop)
+    return PD_OK;      // (captured graphs are keyed on the denoiser options: nothing to drop; PD_OPT_GGS_MAX_FRAMES moves the exchange region and drops them)
 }
 
 extern "C" int pd_engine_get_option(pd_engine *eng, int option, int *value_out) {
@@ -786,6 +816,7 @@ extern "C" int pd_engine_get_option(pd_engine *eng, int option, int *value_out) 
     case PD_OPT_DENOISER_SPLIT: *value_out = eng->den_split; break;
     case PD_OPT_DENOISER_FUSED_ATTN: *value_out = eng->den_fused_attn; break;
     case PD_OPT_DENOISER_LONG_ATTN: *value_out = eng->den_long_attn; break;
+    case PD_OPT_GGS_MAX_FRAMES: *value_out = eng->ggs_max_frames; break;
     case PD_OPT_WEIGHTS_NON_FINITE: *value_out = pd_denoiser_weights_non_finite(eng) ? 1 : 0; break;
     default:
         pd_set_error("pd_engine_get_option: unknown option %d", option);
@@ -926,7 +957,7 @@ extern "C" int pd_debug_ggs_plan(pd_engine *eng, int B, int N, const pd_ggs_cfg 
     PdGgsPlan plan;
     int rc = pd_ggs_plan(eng, B, N, cfg, &plan);
     if (rc) return rc;
-    const int v[8] = {plan.k, plan.n_slots, plan.lds, plan.two_hop, plan.waves, plan.stage_p, plan.lane, plan.lane_rl};
+    const int v[8] = {plan.k, plan.n_slots, plan.lds, plan.long_frames ? 2 : plan.two_hop, plan.waves, plan.stage_p, plan.lane, plan.lane_rl};
     for (int i = 0; i < 8; ++i) out8[i] = v[i];
     return PD_OK;
 }

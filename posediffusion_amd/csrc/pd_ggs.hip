@@ -31,7 +31,7 @@
 // switches below govern all of their code -- and the host code bound to them: pd_ggs_init, pd_ggs_plan, pd_ggs_launch.  The device code
 // itself is in the headers included below: pd_ggs_lds.h (the LDS images and their sizes), pd_ggs_dev.h (cross-lane sums, pair geometry, pose
 // decode), pd_ggs_sampson.h (the match pass), pd_ggs_kernels.h (pd_ggs_kernel, pd_ggs2_kernel), pd_ggs_lane.inc (pd_ggs_lane_kernel), and the
-// statement fragments those include (pd_ggs_pairbwd.inc, pd_ggs_p3b.inc, pd_ggs_p4.inc, pd_ggs_p4q.inc).  The match tables the kernels read are
+// statement fragments those include (pd_ggs_pairbwd.inc, pd_ggs_p3b.inc, pd_ggs_p4.inc, pd_ggs_p4_long.inc, pd_ggs_p4q.inc).  The match tables the kernels read are
 // built elsewhere: on the host by pd_ggs_tables.hip (pd_ggs_set_matches), on the device by pd_ggs_ingest.hip; the stream events that order
 // uploads against launches belong to pd_engine.hip.
 #include "pd_internal.h"
@@ -63,7 +63,7 @@
 #include "pd_ggs_lds.h"        // the two LDS images: struct Lds, carve / carve_lane and the byte counts derived from them
 #include "pd_ggs_dev.h"        // cross-lane sums, pair geometry, pose decode, quaternion Jacobian
 #include "pd_ggs_sampson.h"    // the match pass: Sampson steps, item passes, LDS-DMA staging
-#include "pd_ggs_kernels.h"    // pd_ggs_kernel, pd_ggs2_kernel, pd_ggs_zero_kernel
+#include "pd_ggs_kernels.h"    // pd_ggs_kernel, pd_ggs2_kernel, pd_ggs_long_kernel, pd_ggs_zero_kernel
 #include "pd_ggs_lane.inc"     // pd_ggs_lane_kernel
 
 // --------------------------------------------------------------------------------------------
@@ -98,6 +98,7 @@ int pd_ggs_init() {
                 if (PdGgsKernel f = ggs_variant(stage_p, resident, waves))
                     PD_HIP_CHECK(hipFuncSetAttribute((const void *)f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     PD_HIP_CHECK(hipFuncSetAttribute((const void *)pd_ggs2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    PD_HIP_CHECK(hipFuncSetAttribute((const void *)pd_ggs_long_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     PD_HIP_CHECK(hipFuncSetAttribute((const void *)pd_ggs_lane_kernel<PD_LANE_RV>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     if (!lane_pinc_aligned()) {
         pd_set_error("pd_ggs: the lane kernel's LDS image puts its float4 rows off a 16-byte boundary");
@@ -108,8 +109,8 @@ int pd_ggs_init() {
 
 // pd_ggs_plan, part 1: the arguments, and that every slot of the launch holds tables for N frames; returns the most work items of a slot
 static int plan_check_slots(pd_engine *eng, int B, int N, const pd_ggs_cfg *cfg, PdGgsPlan *out, int &max_items) {
-    PD_TRY(pd_ggs_frames_unsupported(eng, N, "pd_ggs"));       // an engine for more than 64 frames (the denoiser's limit is 256): a clean refusal
-    if (!eng || !cfg || !out || B <= 0 || B > eng->max_B || N <= 0 || N > eng->max_N || N > PD_MAX_FRAMES) {
+    PD_TRY(pd_ggs_frames_unsupported(eng, N, "pd_ggs"));       // more frames than the engine's GGS limit (64, or PD_OPT_GGS_MAX_FRAMES; the denoiser's is 256): a clean refusal
+    if (!eng || !cfg || !out || B <= 0 || B > eng->max_B || N <= 0 || N > eng->max_N || N > eng->ggs_max_frames) {
         pd_set_error("pd_ggs: invalid arguments (B=%d N=%d)", B, N);
         return PD_ERR_INVALID_ARG;
     }
@@ -288,6 +289,55 @@ static int plan_wave_items(const pd_engine *eng, int B, int N, const pd_ggs_cfg 
     return PD_OK;
 }
 
+// pd_ggs_plan, part 4: pd_ggs_long_kernel -- more than PD_MAX_FRAMES frames in the launch (or in one of its slots, with frame counts per
+// sequence), or PD_GGS_CFG_LONG_FRAMES.  One shape, no fall-back: what it needs and does not find is refused, naming the number.
+static int plan_long(const pd_engine *eng, int B, int N, const pd_ggs_cfg *cfg, int device_cus, int max_items, PdGgsPlan *out) {
+    for (int b = 0; b < B; ++b)
+        if (!eng->seqs[b].desc.single_item_pairs) {
+            pd_set_error("pd_ggs: slot %d holds a frame pair of more than %d matches (its longest work item has %d after the cut): the kernel for "
+                         "more than %d frames takes at most %d matches per frame pair", b, PD_ITEM_MAX_MATCHES, eng->seqs[b].max_item_len,
+                         PD_MAX_FRAMES, PD_ITEM_MAX_MATCHES);
+            return PD_ERR_UNSUPPORTED;
+        }
+    if (cfg->wgs_per_seq == 1 || cfg->wgs_per_seq > PD_GGS_LONG_TOT_ROWS || device_cus / B < 2) {
+        if (cfg->wgs_per_seq == 1 || cfg->wgs_per_seq > PD_GGS_LONG_TOT_ROWS)
+            pd_set_error("pd_ggs: wgs_per_seq=%d: the kernel for more than %d frames runs 2 .. %d workgroups per sequence", cfg->wgs_per_seq,
+                         PD_MAX_FRAMES, PD_GGS_LONG_TOT_ROWS);
+        else
+            pd_set_error("pd_ggs: B=%d leaves %d workgroup per sequence on %d CUs: the kernel for more than %d frames needs at least 2 (B <= %d)", B,
+                         device_cus / B, device_cus, PD_MAX_FRAMES, device_cus / 2);
+        return PD_ERR_UNSUPPORTED;
+    }
+    int k = cfg->wgs_per_seq > 0 ? cfg->wgs_per_seq : (max_items + PD_GGS_WAVES - 1) / PD_GGS_WAVES;
+    k = std::max(2, std::min(k, std::min(device_cus / B, PD_GGS_LONG_TOT_ROWS)));
+    const int n_slots = (max_items + k * PD_GGS_WAVES - 1) / (k * PD_GGS_WAVES) * PD_GGS_WAVES;
+    const int n_batch = ggs_long_batch(n_slots);
+    if (n_batch <= 0) {
+        pd_set_error("pd_ggs: %d frame pairs on %d workgroups per sequence (B=%d) are %d item slots per workgroup: their tables alone need %zu B of "
+                     "LDS (> 160 KiB) in the kernel for more than %d frames", max_items, k, B, n_slots, ggs_long_lds_bytes(n_slots, 64), PD_MAX_FRAMES);
+        return PD_ERR_UNSUPPORTED;
+    }
+    const size_t lds = ggs_long_lds_bytes(n_slots, n_batch);
+    for (int b = 0; b < B; ++b) {
+        const PdSeqDesc &d = eng->seqs[b].desc;
+        const size_t lines = (size_t)2 * d.n_pairs + k + d.n_frames;
+        if (lines * PD_XCHG_LINE > eng->xchg_granules) {
+            pd_set_error("pd_ggs: slot %d needs %zu exchange lines (2 x %d frame pairs + %d workgroups + %d frames), the region holds %zu", b, lines,
+                         d.n_pairs, k, d.n_frames, eng->xchg_granules / PD_XCHG_LINE);
+            return PD_ERR_UNSUPPORTED;
+        }
+    }
+    (void)N;
+    out->long_frames = 1;
+    out->k = k;
+    out->waves = PD_GGS_WAVES;
+    out->n_slots = n_slots;
+    out->pinc_rows = 2 * n_batch;      // (reported; the kernel's argument is n_batch)
+    out->lds = (int)lds;
+    out->max_items = max_items;
+    return PD_OK;
+}
+
 // The launch shape of one GGS launch, derived from the uploaded match tables: workgroups per sequence, local item
 // slots, dynamic LDS and which kernel.  Captured hipGraphs bake these in, so pd_sample_phase keys its graph cache on
 // the plan (a re-upload with another item count must never replay the old shape: the kernel would index its LDS
@@ -300,6 +350,14 @@ int pd_ggs_plan(pd_engine *eng, int B, int N, const pd_ggs_cfg *cfg, PdGgsPlan *
     int k = cfg->wgs_per_seq > 0 ? cfg->wgs_per_seq : (max_items + PD_GGS_WAVES - 1) / PD_GGS_WAVES;
     k = std::max(1, std::min(k, device_cus / B));
     memset(out, 0, sizeof(*out));
+    // more than PD_MAX_FRAMES frames (with frame counts set: in any slot), or on request: the kernel with frame tables for 256 frames
+    bool long_frames = (cfg->reserved & PD_GGS_CFG_LONG_FRAMES) != 0;
+    if (eng->nf_B) {
+        for (int b = 0; b < B; ++b) long_frames = long_frames || eng->nf_host[b] > PD_MAX_FRAMES;
+    } else {
+        long_frames = long_frames || N > PD_MAX_FRAMES;
+    }
+    if (long_frames) return plan_long(eng, B, N, cfg, device_cus, max_items, out);
     if (plan_lane(eng, B, N, cfg, device_cus, out)) return PD_OK;
     return plan_wave_items(eng, B, N, cfg, device_cus, k, max_items, out);
 }
@@ -359,7 +417,9 @@ int pd_ggs_launch(pd_engine *eng, float *x, int B, int N, const PdGgsStage *stag
     }
     const size_t lds = (size_t)plan.lds;
     const int B_map = plan.xchg_local ? ((B + 7) & ~7) : B;     // the kernels' block -> (sequence, workgroup) mapping
-    if (plan.lane)
+    if (plan.long_frames)
+        hipLaunchKernelGGL(pd_ggs_long_kernel, dim3(B * plan.k), dim3(PD_GGS_THREADS), lds, s, P, B, plan.n_slots, plan.pinc_rows / 2);
+    else if (plan.lane)
         hipLaunchKernelGGL(pd_ggs_lane_kernel<PD_LANE_RV>, dim3(B), dim3(PD_LANE_THREADS), lds, s, P, plan.pinc_rows);
     else if (plan.two_hop)
         hipLaunchKernelGGL(pd_ggs2_kernel, dim3(B * plan.k), dim3(PD_GGS_THREADS), lds, s, P, B, plan.n_slots);

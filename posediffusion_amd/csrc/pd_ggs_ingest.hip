@@ -526,6 +526,11 @@ extern "C" int pd_ggs_set_matches_csr_async(pd_engine *eng, int seq_first, int n
     }
     const int N = n_frames;
     PD_TRY(pd_ggs_frames_unsupported(eng, N, "pd_ggs_set_matches_csr_async"));
+    if (N > PD_MAX_FRAMES && N <= eng->max_N) {      // (PD_OPT_GGS_MAX_FRAMES above 64: the ingestion kernels keep N^2 counters in LDS)
+        pd_set_error("pd_ggs_set_matches_csr_async: device-side ingestion is limited to %d frames (n_frames=%d); upload the matches of longer "
+                     "sequences with pd_ggs_set_matches", PD_MAX_FRAMES, N);
+        return PD_ERR_UNSUPPORTED;
+    }
     if (N <= 0 || N > PD_MAX_FRAMES || N > eng->max_N || height <= 0 || width <= 0) {
         pd_set_error("pd_ggs_set_matches_csr_async: invalid n_frames=%d (<= %d) or image size %dx%d", N, std::min(PD_MAX_FRAMES, eng->max_N),
                      height, width);

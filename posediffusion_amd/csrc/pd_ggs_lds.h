@@ -1,6 +1,6 @@
-// pd_ggs_lds.h -- the two LDS images of the GGS kernels, each written down ONCE: carve() (pd_ggs_kernel, pd_ggs2_kernel) and carve_lane()
-// (pd_ggs_lane_kernel) hand out the pointers the kernels use, and the host reads the dynamic LDS size of a launch off those same pointers
-// (ggs_lds_bytes, lane_lds_bytes) -- a field added to a carve is in the byte count by construction.  The images fill the 160 KiB of a CU at
+// pd_ggs_lds.h -- the three LDS images of the GGS kernels, each written down ONCE: carve() (pd_ggs_kernel, pd_ggs2_kernel), carve_lane()
+// (pd_ggs_lane_kernel) and carve_long() (pd_ggs_long_kernel) hand out the pointers the kernels use, and the host reads the dynamic LDS size of a launch off those same pointers
+// (ggs_lds_bytes, lane_lds_bytes, ggs_long_lds_bytes) -- a field added to a carve is in the byte count by construction.  The images fill the 160 KiB of a CU at
 // the large shapes: a byte count that lagged behind its carve would let the kernel index past the LDS it was launched with.
 #pragma once
 #include "pd_internal.h"
@@ -102,3 +102,62 @@ static size_t lane_lds_bytes(int pinc_rows, int wave_slots) {
 }
 // the float4 rows of L.pinc rest on the fields before it adding up to a multiple of 16 bytes (checked once, by pd_ggs_init)
 static bool lane_pinc_aligned() { return pd_ggs_lds_offset(carve_lane(pd_ggs_lds_origin(), 0).pinc) % 16 == 0; }
+
+// The image of the kernel for up to PD_GGS_LONG_FRAMES frames (pd_ggs_long_kernel): the same struct with frame tables for 256 frames, the hop
+// windows of the two-hop scheme under names of their own, and only this workgroup's slots of the item tables.  L.pinc = the own rows (what
+// pd_ggs_pairbwd.inc writes); L.prof / L.W / L.stage are not part of this image.
+#define PD_GGS_LONG_FRAMES 256        // frames of the tables (thread = frame on waves 0 .. 3 in the serial phases)
+#define PD_GGS_LONG_INCOFF 260        // CSR offsets of the incidence rows by frame: N + 1 entries, padded to 16 bytes
+#define PD_GGS_LONG_FRAME_ROWS 512    // gathered rows of an owned frame: up to 2 (N - 1) = 510 when both orders of every pair occur
+#define PD_GGS_LONG_TOT_ROWS 256      // gathered totals lines, one per workgroup of the sequence (k <= 256), 4 floats each
+#define PD_GGS_LONG_RED 32            // cross-wave partial sums of the serial phases: 8 sums x the 4 frame waves
+struct LdsLong : Lds {
+    float *red;         // [PD_GGS_LONG_RED]
+    float *tot_rows;    // [PD_GGS_LONG_TOT_ROWS][4]
+    float *frame_rows;  // [PD_GGS_LONG_FRAME_ROWS][16]
+    float *own_rows;    // [2 n_batch][16] results of a batch of this workgroup's pairs: row 2 s = side 0 of the batch's slot s, 2 s + 1 = side 1
+    int *grow;          // [2 n_slots] exchange row of each local (pair, side)
+    float *end;         // one past the image
+};
+// n_slots: item slots of a workgroup (L.itab, L.grow); n_batch <= n_slots: those whose F, item sums and rows are in LDS at a time
+__host__ __device__ __forceinline__ LdsLong carve_long(float *base, int n_slots, int n_batch) {
+    constexpr int NF = PD_GGS_LONG_FRAMES;
+    LdsLong L;
+    L.Rc = base;
+    L.fl = L.Rc + NF * PD_FR_STRIDE;
+    L.cam = L.fl + NF * 4;
+    L.gT = L.cam + 8;
+    L.gR = L.gT + NF * 3;
+    L.gA = L.gR + NF * 9;
+    L.ctl = L.gA + NF * 4;
+    L.red = L.ctl + 8;
+    L.xst = L.red + PD_GGS_LONG_RED;
+    L.mst = L.xst + NF * PD_XS_STRIDE;
+    L.psum = L.mst + NF * PD_XS_STRIDE;                 // [NF][16] the gathered frame sums
+    L.incoff = (int *)(L.psum + NF * 16);
+    L.tot_rows = (float *)(L.incoff + PD_GGS_LONG_INCOFF);
+    L.frame_rows = L.tot_rows + PD_GGS_LONG_TOT_ROWS * 4;
+    L.own_rows = L.frame_rows + PD_GGS_LONG_FRAME_ROWS * 16;
+    L.pinc = L.own_rows;
+    L.F = L.own_rows + 2 * n_batch * 16;
+    L.item = L.F + n_batch * PD_F_STRIDE;
+    L.itab = (int4 *)(L.item + n_batch * PD_ITEM_VALS);
+    L.grow = (int *)(L.itab + n_slots);
+    L.end = (float *)(L.grow + 2 * n_slots);
+    L.prof = nullptr;
+    L.W = nullptr;
+    L.gq = L.gR;
+    L.stage = nullptr;
+    return L;
+}
+// dynamic LDS of a pd_ggs_long_kernel launch
+static size_t ggs_long_lds_bytes(int n_slots, int n_batch) { return pd_ggs_lds_offset(carve_long(pd_ggs_lds_origin(), n_slots, n_batch).end); }
+// Slots per batch for a workgroup of n_slots: all of them when that image fits the 160 KiB of a CU (and P3a's one thread per slot of a
+// batch, <= PD_GGS_THREADS); else the largest multiple of 64 that fits (the lanes of the totals wave then keep their slots across
+// batches); 0: not even 64.
+static int ggs_long_batch(int n_slots) {
+    if (n_slots <= PD_GGS_THREADS && ggs_long_lds_bytes(n_slots, n_slots) <= 160 * 1024) return n_slots;
+    int nb = (n_slots < PD_GGS_THREADS ? n_slots : PD_GGS_THREADS) & ~63;
+    while (nb > 0 && ggs_long_lds_bytes(n_slots, nb) > 160 * 1024) nb -= 64;
+    return nb;
+}

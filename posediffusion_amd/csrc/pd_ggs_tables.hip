@@ -65,6 +65,16 @@ static int cut_work_items(const std::vector<int> &key_off, int N, PdSeqTables &t
 static int chunk_incidences(int N, PdSeqTables &t) {
     const int n_pairs = (int)t.pair_ij.size();
     t.n_pchunks = (n_pairs + PD_GGS_THREADS - 1) / PD_GGS_THREADS;
+    // most pairs incident to one frame: the row stride of the fast per-frame sums (pd_ggs_kernel)
+    std::vector<int> deg(N, 0);
+    for (int p = 0; p < n_pairs; ++p) {
+        deg[t.pair_ij[p].x]++;
+        deg[t.pair_ij[p].y]++;
+    }
+    for (int n = 0; n < N; ++n) t.max_deg = std::max(t.max_deg, deg[n]);
+    // more than PD_MAX_FRAMES frames (PD_OPT_GGS_MAX_FRAMES): only pd_ggs_long_kernel runs, which reads the global tables (gpos, ginc_off) --
+    // the chunk tables of the one-hop and lane kernels are not built (n_pchunks is still reported)
+    if (N > PD_MAX_FRAMES) return PD_OK;
     if (t.n_pchunks > PD_GGS_MAX_PCHUNKS) {
         pd_set_error("pd_ggs_set_matches: %d frame pairs with matches (max %d)", n_pairs, PD_GGS_MAX_PCHUNKS * PD_GGS_THREADS);
         return PD_ERR_UNSUPPORTED;
@@ -87,13 +97,6 @@ static int chunk_incidences(int N, PdSeqTables &t) {
     for (int p = 0; p < n_pairs; ++p)
         t.ptab[p] = make_int4(t.pair_ij[p].x | (t.pair_ij[p].y << 8), t.pair_item_off[p], t.pair_item_off[p + 1] - t.pair_item_off[p],
                               pos0[p] | (pos1[p] << 16));
-    // most pairs incident to one frame: the row stride of the fast per-frame sums (pd_ggs_kernel)
-    std::vector<int> deg(N, 0);
-    for (int p = 0; p < n_pairs; ++p) {
-        deg[t.pair_ij[p].x]++;
-        deg[t.pair_ij[p].y]++;
-    }
-    for (int n = 0; n < N; ++n) t.max_deg = std::max(t.max_deg, deg[n]);
     return PD_OK;
 }
 
@@ -266,7 +269,7 @@ static std::vector<char> pack_tables(const PdSeqTables &t, PdBlobArrays &o) {
     n.lpt = t.lptab.size();
     n.lst = t.lstream.size();
     std::vector<char> host(pd_blob_layout(n, o), 0);
-    auto put = [&](size_t off, const auto &v) { memcpy(host.data() + off, v.data(), sizeof(v[0]) * v.size()); };
+    auto put = [&](size_t off, const auto &v) { if (!v.empty()) memcpy(host.data() + off, v.data(), sizeof(v[0]) * v.size()); };
     put(o.pts, t.pts);
     put(o.pij, t.pair_ij);
     put(o.pio, t.pair_item_off);
@@ -315,10 +318,10 @@ extern "C" int pd_ggs_set_matches(pd_engine *eng, int seq, const double *kp1, co
         pd_ggs_free_seq(h);
         return upload_seq_desc(eng, seq);
     }
-    if (!kp1 || !kp2 || !i12 || M < 0 || n_frames <= 0 || n_frames > PD_MAX_FRAMES || n_frames > eng->max_N ||
+    if (!kp1 || !kp2 || !i12 || M < 0 || n_frames <= 0 || n_frames > eng->ggs_max_frames || n_frames > eng->max_N ||
         height <= 0 || width <= 0) {
         pd_set_error("pd_ggs_set_matches: invalid arguments (M=%lld n_frames=%d h=%d w=%d; n_frames <= %d)",
-                     (long long)M, n_frames, height, width, std::min(PD_MAX_FRAMES, eng->max_N));
+                     (long long)M, n_frames, height, width, std::min(eng->ggs_max_frames, eng->max_N));
         return PD_ERR_INVALID_ARG;
     }
     PdSeqTables t;

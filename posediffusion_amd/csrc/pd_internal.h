@@ -11,7 +11,8 @@
 #include "../../include/pd_engine.h"
 
 #define PD_WAVE 64
-#define PD_MAX_FRAMES 64          // GGS: one wavefront lane per frame in the update phase
+#define PD_MAX_FRAMES 64          // GGS by default (one wavefront lane per frame in the update phase); PD_OPT_GGS_MAX_FRAMES raises an engine's limit
+#define PD_GGS_LONG_MAX_FRAMES 256   // ... up to this: pd_ggs_long_kernel (one thread per frame on four waves, frame indices packed in 8 bits)
 #define PD_MAX_DENOISER_FRAMES 256   // the denoiser and unguided sampling: four 64-key tiles of pd_attn_long_kernel (pd_attn_long.h)
 #define PD_GGS_THREADS 512        // 8 waves per GGS workgroup
 #define PD_GGS_WAVES (PD_GGS_THREADS / PD_WAVE)
@@ -144,6 +145,7 @@ struct PdGgsPlan {
     int lane, lane_rl;         // lane-per-item kernel chosen; steps RV .. RV + lane_rl - 1 of its longest wave's stream live in LDS for the whole
                                //   launch (<= PD_LANE_RL; the PD_LANE_RING slots of the ring come on top)
     int xchg_local;            // one-hop kernel: XCD-local placement of a sequence's workgroups (see PdGgsParams)
+    int long_frames;           // pd_ggs_long_kernel (more than PD_MAX_FRAMES frames, or PD_GGS_CFG_LONG_FRAMES): k, n_slots, lds and max_items are its shape
 };
 
 // lane items of one frame pair with m matches at lane-item length len: ceil(m / len) items of balanced size (host and device builders)
@@ -281,6 +283,7 @@ struct pd_engine {
     PdSeqDesc *d_seqs = nullptr;         // [max_B] device copy of the descriptors
     unsigned long long *d_xchg = nullptr;
     size_t xchg_granules = 0;            // per (sequence, slot)
+    int ggs_max_frames = PD_MAX_FRAMES;  // PD_OPT_GGS_MAX_FRAMES: frames GGS admits on this engine; d_xchg is sized for it
     unsigned int *d_err = nullptr;       // [0] async error word; [2..] debug phase counters
     int ggs_prof_on = 0;
     int den_fused_attn = 1;          // PD_OPT_DENOISER_FUSED_ATTN: in the fp16-plane mode, in_proj + attention as one kernel with Q / K / V in LDS (N <= 32)
@@ -363,7 +366,7 @@ int pd_ggs_launch(pd_engine *eng, float *x, int B, int N, const PdGgsStage *stag
 int pd_build_seq_tables(const double *kp1, const double *kp2, const int64_t *i12, int64_t M, int n_frames, PdSeqTables &out);   // pure: no HIP call, no engine
 void pd_ggs_free_seq(PdSeqHost &h);
 int pd_ggs_ingest_init();   // pd_ggs_ingest.hip: the device builder (pd_ggs_set_matches_csr_async)
-// pd_engine.hip: PD_ERR_UNSUPPORTED (and the message) for a GGS call with PD_MAX_FRAMES < N <= max_N, else PD_OK
+// pd_engine.hip: PD_ERR_UNSUPPORTED (and the message) for a GGS call with ggs_max_frames (PD_OPT_GGS_MAX_FRAMES; 64 by default) < N <= max_N, else PD_OK
 int pd_ggs_frames_unsupported(const pd_engine *eng, int N, const char *who);
 // pd_engine.hip: the frame counts in force for a call of (B, N): *nf_dev = null when none are set, else the device array after checking that
 // B is the B they were set for and every count lies in [1, N] (PD_ERR_INVALID_ARG naming the rule otherwise)

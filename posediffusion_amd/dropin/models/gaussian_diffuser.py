@@ -44,6 +44,8 @@ class GaussianDiffusion(nn.Module):
         self.model = None          # the Denoiser, assigned after construction (pose_diffusion_model.py:61)
         self.use_graph = os.environ.get("PD_USE_GRAPH", "1") != "0"
         self.last_ggs_stats = None
+        self.ggs_max_frames = host.GGS_MAX_FRAMES      # frames guided sampling admits; raise it (<= 256) to guide longer sequences: the engine
+        #                                                then holds a larger exchange region (PD_OPT_GGS_MAX_FRAMES, include/pd_engine.h)
 
     # ---- schedule helpers (:190-216): elementwise on the buffers, same names and argument order; the sampler itself has these
     # fused into pd_tail_kernel and does not call them
@@ -122,10 +124,11 @@ class GaussianDiffusion(nn.Module):
                 raise ValueError(f"sequences {[b for b, h in enumerate(have) if not h]} of the batch have no matches: sample them in a call "
                                  "without cond_fn (demo.py:79-92) and the others with it")
             has_ggs = all(have)
-        if has_ggs and N > host.GGS_MAX_FRAMES:
-            # the denoiser takes up to 256 frames, GGS 64 (include/pd_engine.h): no silent fallback to unguided sampling
-            raise RuntimeError(f"guided sampling (GGS) is limited to {host.GGS_MAX_FRAMES} frames, got {N}: run unguided (GGS.enable=False)")
-        eng = host.get_engine(self.model, self, B, N)
+        ggs_max = int(getattr(self, "ggs_max_frames", host.GGS_MAX_FRAMES))
+        if has_ggs and N > ggs_max:
+            # the denoiser takes up to 256 frames, GGS 64 unless ggs_max_frames was raised (include/pd_engine.h): no silent fallback to unguided sampling
+            raise RuntimeError(f"guided sampling (GGS) is limited to {ggs_max} frames, got {N}: run unguided (GGS.enable=False)")
+        eng = host.get_engine(self.model, self, B, N, ggs_max_frames=ggs_max if has_ggs else host.GGS_MAX_FRAMES)
         if cond_fn is not None and parsed is None and n_frames is not None:
             raise NotImplementedError("n_frames with a guidance callable other than the shipped geometry_guided_sampling partial: "
                                       "a callable sees one padded [B, N, 9] tensor and cannot know the counts")

@@ -44,11 +44,12 @@ class PoseEngine:
     """One engine per device.  ``denoiser_sd`` uses the reference Denoiser's state_dict keys
     (``time_embed.linear.0.weight`` ... ``_last.3.bias``); ``tables`` the GaussianDiffusion buffers.  ``norm_first`` /
     ``pivot``: TransformerEncoderWrapper(norm_first=...) and Denoiser(pivot_cam_onehot=...); ``generic``: run the shape-generic
-    denoiser kernels even at the default shape (PD_WEIGHTS_GENERIC, comparison / testing)."""
+    denoiser kernels even at the default shape (PD_WEIGHTS_GENERIC, comparison / testing); ``ggs_max_frames``: the frames GGS admits
+    (PD_OPT_GGS_MAX_FRAMES: 64 unless given; a value in (64, max_N] sizes the exchange region for such sequences)."""
 
     def __init__(self, denoiser_sd: Dict[str, torch.Tensor], tables: Dict[str, torch.Tensor], device=None,
                  max_B: int = 8, max_N: int = 20, num_layers: int = 8, nhead: int = 4, objective: str = "pred_noise",
-                 norm_first: bool = True, pivot: bool = True, generic: bool = False):
+                 norm_first: bool = True, pivot: bool = True, generic: bool = False, ggs_max_frames: Optional[int] = None):
         if objective not in ("pred_noise", "pred_x0"):                     # models/gaussian_diffuser.py:105-108
             raise AssertionError("objective must be either pred_noise (predict noise) or pred_x0 (predict image start)")
         if not torch.cuda.is_available():
@@ -107,6 +108,12 @@ class PoseEngine:
             if self.has_q_tables:
                 _lib.check(self.lib.pd_engine_set_q_tables(self._h, *(dev(tables[n]) for n in _Q_TABLES)), "pd_engine_set_q_tables")
         del keep
+        if ggs_max_frames is not None:
+            try:
+                self.set_option(_lib.PD_OPT_GGS_MAX_FRAMES, int(ggs_max_frames))
+            except Exception:
+                self.close()
+                raise
 
     # ---------------------------------------------------------------- lifecycle
     def close(self):
@@ -362,6 +369,11 @@ class PoseEngine:
     def set_option(self, option: int, value: int):
         with torch.cuda.device(self.device):
             _lib.check(self.lib.pd_engine_set_option(self._h, int(option), int(value)), "pd_engine_set_option")
+
+    @property
+    def ggs_max_frames(self) -> int:
+        """The frames GGS admits on this engine (PD_OPT_GGS_MAX_FRAMES)."""
+        return self.get_option(_lib.PD_OPT_GGS_MAX_FRAMES)
 
     def get_option(self, option: int) -> int:
         """pd_engine_get_option: e.g. ``_lib.PD_OPT_DENOISER_SPLIT`` -> the encoder GEMM mode in force (0 after the non-finite-weights downgrade)."""

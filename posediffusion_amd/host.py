@@ -16,10 +16,12 @@ from typing import Dict, Optional
 
 import torch
 
+from . import _lib
 from .engine import PoseEngine, make_ggs_cfg
 
 _DENOISER_PREFIXES = ("time_embed.", "_first.", "_trunk.", "_last.")
-GGS_MAX_FRAMES = 64          # PD_MAX_FRAMES: GGS stops here; the denoiser and unguided sampling take up to 256 frames (include/pd_engine.h)
+GGS_MAX_FRAMES = 64          # PD_MAX_FRAMES: GGS stops here unless the engine option PD_OPT_GGS_MAX_FRAMES is raised (get_engine(..., ggs_max_frames=));
+                             # the denoiser and unguided sampling take up to 256 frames (include/pd_engine.h)
 
 
 def _fingerprint(denoiser: torch.nn.Module, diffuser: Optional[torch.nn.Module]):
@@ -34,8 +36,9 @@ def denoiser_state(denoiser: torch.nn.Module) -> Dict[str, torch.Tensor]:
     return {k: v for k, v in denoiser.state_dict().items() if k.startswith(_DENOISER_PREFIXES)}
 
 
-def get_engine(denoiser: torch.nn.Module, diffuser: Optional[torch.nn.Module], B: int, N: int) -> PoseEngine:
-    """Engine for these live modules (rebuilt when weights, device or capacity change)."""
+def get_engine(denoiser: torch.nn.Module, diffuser: Optional[torch.nn.Module], B: int, N: int, ggs_max_frames: int = GGS_MAX_FRAMES) -> PoseEngine:
+    """Engine for these live modules (rebuilt when weights, device or capacity change).  ``ggs_max_frames`` above 64 RAISES the frames GGS
+    admits on the engine (PD_OPT_GGS_MAX_FRAMES; capped at the engine's max_N), never lowers them on a cached one."""
     dev = next(denoiser.parameters()).device
     if dev.type != "cuda":
         raise RuntimeError("the PoseDiffusion sampling path of posediffusion_amd runs only on an AMD GPU "
@@ -48,9 +51,11 @@ def get_engine(denoiser: torch.nn.Module, diffuser: Optional[torch.nn.Module], B
     objective = getattr(diffuser, "objective", None)           # Denoiser.forward alone does not depend on it
     if ent is not None and ent[0][0] == fp_den and (fp_diff is None or ent[0][1] == fp_diff) \
             and ent[1].max_B >= B and ent[1].max_N >= N and objective in (None, ent[1].objective):
+        _raise_ggs_limit(ent[1], ggs_max_frames)
         return ent[1]
     if ent is not None:
         B, N = max(B, ent[1].max_B), max(N, ent[1].max_N)     # never shrink capacity on a rebuild
+        ggs_max_frames = max(int(ggs_max_frames), ent[1].ggs_max_frames)
         ent[1].close()
     fp = (fp_den, fp_diff)
     if diffuser is not None:
@@ -64,9 +69,16 @@ def get_engine(denoiser: torch.nn.Module, diffuser: Optional[torch.nn.Module], B
     pivot = bool(getattr(denoiser, "pivot_cam_onehot", True))
     eng = PoseEngine(denoiser_state(denoiser), tables, device=dev, max_B=max(B, 1), max_N=max(N, 1),
                      num_layers=layers, nhead=nhead, objective=objective or "pred_noise", norm_first=norm_first, pivot=pivot)
+    _raise_ggs_limit(eng, ggs_max_frames)
     cache["e"] = (fp, eng)
     _ENGINES[dev.index if dev.index is not None else torch.cuda.current_device()] = eng
     return eng
+
+
+def _raise_ggs_limit(eng: PoseEngine, ggs_max_frames: int):
+    want = min(int(ggs_max_frames), eng.max_N)
+    if want > GGS_MAX_FRAMES and want > eng.ggs_max_frames:
+        eng.set_option(_lib.PD_OPT_GGS_MAX_FRAMES, want)
 
 
 def parse_ggs_cond_fn(cond_fn):
