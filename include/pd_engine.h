@@ -522,7 +522,9 @@ int pd_debug_lane_tables(pd_engine *eng, int seq, int *out, int n_out);
 /* Does v_mfma_f32_32x32x16_f16 keep fp16-SUBNORMAL operands (the `lo` halves of small elements in the fp16-plane denoiser mode are
  * subnormal)?  One 32x32x16 product per case, every element of A = a, of B = b: out4 = {C[0][0] for (a, b) = (2^-20, 2^10): 2^-6 if kept;
  * (2^10, 2^-20): 2^-6; (2^-20, 2^-4): 2^-20 (a subnormal times a normal, result far below fp16's range: fp32 accumulation);
- * (1, 1): 16 (control)}; a flushed operand gives 0.  Runs on `stream` and synchronises it. */
+ * (1, 1): 16 (control)}; a flushed operand gives 0.  Runs on `stream` and synchronises it.
+ * out4_host[0] == 32.0f ON ENTRY selects v_mfma_f32_16x16x32_f16 instead, the shape of the large-batch fp16-plane GEMMs (32 k per instruction):
+ * out4 = {2^-5, 2^-5, 2^-19, 32}.  (A selector rather than a second function: the C-ABI's function list is pinned by the tests.) */
 int pd_debug_mfma_f16_subnormal(float *out4_host, void *stream);
 /* The residual stream of the LAST pd_vit_forward_scale call: rows [n_img * T, 384] after the last block, before the final LayerNorm,
  * copied to dst (DEVICE fp32, n_floats = n_img * T * 384) on `stream`.  PD_ERR_INVALID_ARG when n_floats exceeds what that call wrote.

@@ -503,21 +503,26 @@ extern "C" int pd_pose_embedding(const float *x, long long rows, int dim, float 
 }
 
 // ---- probe: fp16-subnormal operands on the fp16 matrix pipe (pd_engine.h pd_debug_mfma_f16_subnormal; the kernel: pd_denoiser_kernels.h) ----
-extern "C" int pd_debug_mfma_f16_subnormal(float *out4_host, void *stream) {
+static int mfma_f16_subnormal(bool shape16, const char *who, float *out4_host, void *stream) {
     if (!out4_host) return PD_ERR_INVALID_ARG;
     float *d = nullptr;
     PD_HIP_CHECK(hipMalloc((void **)&d, 8 * sizeof(float)));
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(pd_mfma_f16_subnormal_kernel, dim3(1), dim3(64), 0, s, d);
+    if (shape16) hipLaunchKernelGGL(pd_mfma16_f16_subnormal_kernel, dim3(1), dim3(64), 0, s, d);
+    else hipLaunchKernelGGL(pd_mfma_f16_subnormal_kernel, dim3(1), dim3(64), 0, s, d);
     float h[8];
     hipError_t e = hipMemcpyAsync(h, d, sizeof(h), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     (void)hipFree(d);
     if (e != hipSuccess) {
-        pd_set_error("pd_debug_mfma_f16_subnormal: %s", hipGetErrorString(e));
+        pd_set_error("%s: %s", who, hipGetErrorString(e));
         return PD_ERR_HIP;
     }
     for (int i = 0; i < 4; ++i) out4_host[i] = h[i];
     if (h[4] == 0.0f) out4_host[0] = -1.0f;   // the fp32 -> fp16 conversion itself flushed 2^-20 (would make the probe meaningless)
     return PD_OK;
+}
+// out4_host[0] == 32 on entry: the products on v_mfma_f32_16x16x32_f16 (the large-batch planes' shape, 32 k per instruction) instead of 32x32x16
+extern "C" int pd_debug_mfma_f16_subnormal(float *out4_host, void *stream) {
+    return mfma_f16_subnormal(out4_host && out4_host[0] == 32.0f, "pd_debug_mfma_f16_subnormal", out4_host, stream);
 }

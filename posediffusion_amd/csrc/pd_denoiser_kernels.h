@@ -266,3 +266,22 @@ __global__ __launch_bounds__(64) void pd_mfma_f16_subnormal_kernel(float *out) {
         }
     }
 }
+// the same four products on v_mfma_f32_16x16x32_f16 (the large-batch planes' shape): 32 k per instruction
+__global__ __launch_bounds__(64) void pd_mfma16_f16_subnormal_kernel(float *out) {
+    const float av[4] = {9.5367431640625e-07f, 1024.0f, 9.5367431640625e-07f, 1.0f};
+    const float bv[4] = {1024.0f, 9.5367431640625e-07f, 0.0625f, 1.0f};
+    for (int c = 0; c < 4; ++c) {
+        f16x8 a, b;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            a[e] = (_Float16)av[c];
+            b[e] = (_Float16)bv[c];
+        }
+        f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, acc, 0, 0, 0);
+        if (threadIdx.x == 0) {
+            out[c] = acc[0];
+            out[4 + c] = (float)a[0];
+        }
+    }
+}

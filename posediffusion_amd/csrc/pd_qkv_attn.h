@@ -3,10 +3,10 @@
 // head; BASELINE.json north_star: "attention projections use MFMA tiles with LDS-staged Q/K/V").
 //
 // Before: pd_gemm_strip_kernel wrote QKV [M, 1536] as fp32 (31.5 MB at 5 120 rows), pd_attn_mma_kernel read it back: 63 MB of the 231 MB a
-// layer moved, two launches.  Here a workgroup of 12 wavefronts owns G = 95 / N whole sequences (G N <= 95 token rows in three 32-row MFMA
-// tiles; N = 20: 4 sequences, 80 rows) and ONE head:
-//   1. the head's 384 in_proj columns (q | k | v, 128 each) as twelve 32-column strips, one per wave, over the three row tiles:
-//      the fp16-plane product of pd_gemm_strip_kernel (hi + lo operand pairs, three v_mfma_f32_32x32x16_f16 per 16 k, fp32 accumulation;
+// layer moved, two launches.  Here a workgroup of 12 wavefronts owns G = 95 / N whole sequences (G N <= 95 token rows in up to six 16-row MFMA
+// tiles; N = 20: 4 sequences, 80 rows = five tiles) and ONE head:
+//   1. the head's 384 in_proj columns (q | k | v, 128 each) as twelve 32-column strips, one per wave, over the row tiles that hold rows:
+//      the fp16-plane product of pd_gemm_strip_kernel (hi + lo operand pairs, three v_mfma_f32_16x16x32_f16 per 32 k and 16 x 16 tile, fp32 accumulation;
 //      the A rows -- LayerNorm output as split words -- go L2 -> LDS by LDS-DMA in 64-k chunks, un-zipped at the fragment reads; the weight
 //      fragments go L2 -> registers, hand-issued half a chunk ahead; every vector-memory operation counted by hand-written s_waitcnt);
 //   2. accumulator * c_scale + bias (q also * 1/sqrt(128)) -> fp32 Q, K, V in LDS (the staging buffers are dead by then: aliased);
@@ -22,7 +22,7 @@
 #endif
 #define PD_QA_WAVES 12
 #define PD_QA_THREADS (PD_QA_WAVES * 64)
-#define PD_QA_ROWS 96                       // three 32-row tiles
+#define PD_QA_ROWS 96                       // six 16-row tiles (three of 32 rows on the 32x32x16 form)
 #define PD_QA_LDR (3 * DH + 4)              // row stride of the Q | K | V image in LDS (floats): 388 = 4 mod 32 banks, like DH + 4
 #define PD_QA_LS 36                         // row stride of a team's score tile
 #ifndef PD_QA_DEEP_DEFAULT
@@ -59,6 +59,7 @@ static inline size_t pd_qkv_attn_lds(int N) {
 template <int BARE, bool DEEP = false>
 __global__ __launch_bounds__(PD_QA_THREADS) void pd_qkv_attn_kernel(PdQkvAttnArgs g) {
     constexpr int KC = 32, RT = 3, TM = PD_QA_ROWS, CHA = TM * KC, LDR = PD_QA_LDR, LS = PD_QA_LS;
+    constexpr bool M16 = PD_STRIP_MFMA16 != 0;      // the product's MFMA shape: the in_proj strip instance's (pd_gemm_split.h), which the fused path equals bit for bit
     extern __shared__ __attribute__((aligned(1024))) unsigned qa_lds[];
     const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, hi = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -87,43 +88,86 @@ __global__ __launch_bounds__(PD_QA_THREADS) void pd_qkv_attn_kernel(PdQkvAttnArg
     const int N = g.N, G = g.G, M = g.B * N;
     const int seq0 = grp * G, nseq = min(G, g.B - seq0), m0 = seq0 * N, rows = nseq * N;     // this workgroup's token rows [m0, m0 + rows)
     // ---- 1. the in_proj product ------------------------------------------------------------------------------------------------------
-    // staging: pieces of 1 KiB = 8 rows x 32 words; a 32-k block of A has 12 of them, wave w moves piece w
-    const int prow = lane >> 3, pslot = lane & 7;
+    // The wave's 32-column strip as two 16-column tiles over the 16-row tiles that hold rows: nt16 = ceil(rows / 16) of six (N = 20: 80 rows = five, where three
+    // 32-row tiles multiplied 96), one v_mfma_f32_16x16x32_f16 per (row tile, column tile, product) and 32-k block -- pd_gemm_strip_kernel's M16 form, element for
+    // element: bitwise its C.  The K loop exists once per tile count (nt16 is uniform over the workgroup, and over the launch but for the last group): the
+    // tiles not run cost no fragment read, no un-zip, no MFMA and no staged row, and their accumulators are never written out.
+    // staging: pieces of 1 KiB = 8 rows x 32 words; a 32-k block of A has 12 of them, wave w moves piece w -- if a tile that is run holds its rows
+    const int nt16 = __builtin_amdgcn_readfirstlane((rows + 15) >> 4);
+    const int stages = __builtin_amdgcn_readfirstlane(8 * wave < 16 * nt16 ? 1 : 0);
+    const int prow = lane >> 3, pslot = lane & 7, l15 = lane & 15, kg = lane >> 4;
     unsigned oa;
     {
         const int r = 8 * wave + prow;
-        oa = (unsigned)(((size_t)min(m0 + r, M - 1) * DM + 4 * (pslot ^ ((r >> 1) & 7))) * sizeof(unsigned));
+        oa = (unsigned)(((size_t)min(m0 + r, M - 1) * DM + 4 * (pslot ^ pd_strip_swz<M16>(r))) * sizeof(unsigned));
     }
     const unsigned lds_a = (unsigned)(size_t)(qa_lds + wave * 256);
     const int third = wave >> 2;                                                     // 0 q, 1 k, 2 v
     const int ntile = third * (DM / 32) + head * (DH / 32) + (wave & 3);              // this wave's 32-column tile of the 1536 in_proj rows
     constexpr int KS = DM / 16;
-    const uint4 *wq = (const uint4 *)g.W + (size_t)ntile * KS * 128 + lane;
+    // M16: the lane's (column % 16, k group) of a 32-k block in the planes' 32-column x 16-k fragment order (pd_gemm_strip_kernel)
+    const uint4 *wq = (const uint4 *)g.W + (size_t)ntile * KS * 128 + (M16 ? (kg >> 1) * 128 + (kg & 1) * 32 + l15 : lane);
     typedef unsigned wv4 __attribute__((ext_vector_type(4)));
-    f32x16 acc[RT];
+    f32x16 acc[M16 ? 1 : RT];
+    f32x4 acc4[M16 ? 2 * RT : 1][2];                                                 // M16: [16-row tile][16-column tile]
 #pragma unroll
-    for (int mi = 0; mi < RT; ++mi)
+    for (int mi = 0; mi < (M16 ? 1 : RT); ++mi)
 #pragma unroll
         for (int i = 0; i < 16; ++i) acc[mi][i] = 0.0f;
+#pragma unroll
+    for (int t = 0; t < (M16 ? 2 * RT : 1); ++t) acc4[t][0] = acc4[t][1] = f32x4{0.f, 0.f, 0.f, 0.f};
     auto mmaw = [](const uint4 &a, const wv4 &b, const f32x16 &c) {
         return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
     };
+    auto mma16 = [](const uint4 &a, const wv4 &b, const f32x4 &c) {
+        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+    };
+    // (M16: w0 / w1 = column tile 0 {hi | lo}, w2 / w3 = column tile 1 -- the lo plane 1 KiB, the second column tile 16 lanes further)
 #define PD_QA_WLOAD(w0, w1, w2, w3, b)                                                                                               \
     do {                                                                                                                             \
         const uint4 *wp_ = wq + (size_t)(b) * 256;                                                                                   \
-        asm volatile("global_load_dwordx4 %0, %4, off\n\tglobal_load_dwordx4 %1, %4, off offset:1024\n\t"                           \
-                     "global_load_dwordx4 %2, %4, off offset:2048\n\tglobal_load_dwordx4 %3, %4, off offset:3072"                    \
-                     : "=&v"(w0), "=&v"(w1), "=&v"(w2), "=&v"(w3) : "v"(wp_) : "memory");                                            \
+        if constexpr (M16)                                                                                                           \
+            asm volatile("global_load_dwordx4 %0, %4, off\n\tglobal_load_dwordx4 %1, %4, off offset:1024\n\t"                       \
+                         "global_load_dwordx4 %2, %4, off offset:256\n\tglobal_load_dwordx4 %3, %4, off offset:1280"                 \
+                         : "=&v"(w0), "=&v"(w1), "=&v"(w2), "=&v"(w3) : "v"(wp_) : "memory");                                        \
+        else                                                                                                                         \
+            asm volatile("global_load_dwordx4 %0, %4, off\n\tglobal_load_dwordx4 %1, %4, off offset:1024\n\t"                       \
+                         "global_load_dwordx4 %2, %4, off offset:2048\n\tglobal_load_dwordx4 %3, %4, off offset:3072"                \
+                         : "=&v"(w0), "=&v"(w1), "=&v"(w2), "=&v"(w3) : "v"(wp_) : "memory");                                        \
     } while (0)
 #define PD_QA_WAIT(n, w0, w1, w2, w3) asm volatile("s_waitcnt vmcnt(" #n ")" : "+v"(w0), "+v"(w1), "+v"(w2), "+v"(w3) : : "memory")
-    auto stage64 = [&](int c, int buf) {            // both 32-k blocks of chunk c: two pieces per wave
+    // vmcnt(6) for a wave that stages (its two DMA pieces may fly), vmcnt(4) for one that does not -- ONE statement, the scalar branch inside it: with a wait per
+    // branch the register allocator joins the two definitions of the fragments by copies, which it is free to place ahead of a wait (they read registers still in flight)
+#define PD_QA_WAIT_STAGED(stg, w0, w1, w2, w3)                                                                                       \
+    asm volatile("s_cmp_eq_u32 %4, 0\n\ts_cbranch_scc1 .Lqa_ns%=\n\ts_waitcnt vmcnt(6)\n\ts_branch .Lqa_done%=\n"                   \
+                 ".Lqa_ns%=:\n\ts_waitcnt vmcnt(4)\n.Lqa_done%=:"                                                                   \
+                 : "+v"(w0), "+v"(w1), "+v"(w2), "+v"(w3) : "s"(__builtin_amdgcn_readfirstlane(stg)) : "memory", "scc")
+    auto stage64 = [&](int c, int buf) {            // both 32-k blocks of chunk c: two pieces per wave (none for a wave whose rows lie in tiles not run)
+        if (!stages) return;
         const unsigned da = __builtin_amdgcn_readfirstlane(lds_a + buf * 2 * CHA * 4);
 #pragma unroll
         for (int h = 0; h < 2; ++h) pd_dma_piece((const float *)(g.A + (2 * c + h) * KC), oa, da + h * CHA * 4);
     };
     // one 32-k block: fragment reads + un-zip + 18 MFMAs; w0 / w1 = k step 0 {hi | lo}, w2 / w3 = k step 1.  Per output element and k step:
-    // lo x hi, hi x lo, hi x hi -- pd_gemm_strip_kernel's order
-    auto block = [&](const unsigned *a, const wv4 &w0, const wv4 &w1, const wv4 &w2, const wv4 &w3) {
+    // lo x hi, hi x lo, hi x hi -- pd_gemm_strip_kernel's order.  M16: NT 16-row tiles, 6 MFMAs each, the same order per element over the block's 32 k
+    auto block = [&](auto nt_, const unsigned *a, const wv4 &w0, const wv4 &w1, const wv4 &w2, const wv4 &w3) {
+        constexpr int NT = decltype(nt_)::value;
+        if constexpr (M16) {
+            const int sz = pd_strip_swz<true>(l15);
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+                const uint4 p = *(const uint4 *)(a + t * 16 * KC + 4 * ((2 * kg) ^ sz));
+                const uint4 q = *(const uint4 *)(a + t * 16 * KC + 4 * ((2 * kg + 1) ^ sz));
+                const uint4 h8 = make_uint4(__builtin_amdgcn_perm(p.y, p.x, 0x05040100u), __builtin_amdgcn_perm(p.w, p.z, 0x05040100u),
+                                            __builtin_amdgcn_perm(q.y, q.x, 0x05040100u), __builtin_amdgcn_perm(q.w, q.z, 0x05040100u));
+                const uint4 l8 = make_uint4(__builtin_amdgcn_perm(p.y, p.x, 0x07060302u), __builtin_amdgcn_perm(p.w, p.z, 0x07060302u),
+                                            __builtin_amdgcn_perm(q.y, q.x, 0x07060302u), __builtin_amdgcn_perm(q.w, q.z, 0x07060302u));
+                f32x4 &c0 = acc4[M16 ? t : 0][0], &c1 = acc4[M16 ? t : 0][1];
+                c0 = mma16(l8, w0, c0); c1 = mma16(l8, w2, c1);
+                c0 = mma16(h8, w1, c0); c1 = mma16(h8, w3, c1);
+                c0 = mma16(h8, w0, c0); c1 = mma16(h8, w2, c1);
+            }
+        } else {
         uint4 ah[RT], al[RT];
 #pragma unroll
         for (int st = 0; st < 2; ++st) {
@@ -138,14 +182,16 @@ __global__ __launch_bounds__(PD_QA_THREADS) void pd_qkv_attn_kernel(PdQkvAttnArg
             }
             const wv4 &wh = st ? w2 : w0, &wl = st ? w3 : w1;
 #pragma unroll
-            for (int mi = 0; mi < RT; ++mi) acc[mi] = mmaw(al[mi], wh, acc[mi]);
+            for (int mi = 0; mi < RT; ++mi) acc[M16 ? 0 : mi] = mmaw(al[mi], wh, acc[M16 ? 0 : mi]);
 #pragma unroll
-            for (int mi = 0; mi < RT; ++mi) acc[mi] = mmaw(ah[mi], wl, acc[mi]);
+            for (int mi = 0; mi < RT; ++mi) acc[M16 ? 0 : mi] = mmaw(ah[mi], wl, acc[M16 ? 0 : mi]);
 #pragma unroll
-            for (int mi = 0; mi < RT; ++mi) acc[mi] = mmaw(ah[mi], wh, acc[mi]);
+            for (int mi = 0; mi < RT; ++mi) acc[M16 ? 0 : mi] = mmaw(ah[mi], wh, acc[M16 ? 0 : mi]);
+        }
         }
     };
-    {
+    const int lrow = M16 ? l15 : l31;                // the lane's row within a tile
+    auto kloop = [&](auto nt_) {
         wv4 a0, a1, a2, a3, b0, b1, b2, b3;               // weight fragments of the chunk's first / second 32-k block
         constexpr int nk64 = DM / 64;
         stage64(0, 0);
@@ -159,24 +205,24 @@ __global__ __launch_bounds__(PD_QA_THREADS) void pd_qkv_attn_kernel(PdQkvAttnArg
             wv4 c0, c1, c2, c3, d0, d1, d2, d3;              // the second set: chunk c + 1 while a / b hold chunk c, and vice versa
             for (int c = 0; c < nk64; c += 2) {              // nk64 is even
                 {
-                    const unsigned *a = qa_lds + 0 * 2 * CHA + l31 * KC;
+                    const unsigned *a = qa_lds + 0 * 2 * CHA + lrow * KC;
                     stage64(c + 1, 1);
                     PD_QA_WLOAD(c0, c1, c2, c3, 2 * (c + 1));
                     PD_QA_WLOAD(d0, d1, d2, d3, 2 * (c + 1) + 1);
-                    block(a, a0, a1, a2, a3);
-                    block(a + CHA, b0, b1, b2, b3);
+                    block(nt_, a, a0, a1, a2, a3);
+                    block(nt_, a + CHA, b0, b1, b2, b3);
                     PD_QA_WAIT(0, c0, c1, c2, c3);           // everything requested at the start of this chunk has landed
                     PD_QA_WAIT(0, d0, d1, d2, d3);
                     __syncthreads();
                 }
                 {
                     const int cn = min(c + 2, nk64 - 1);     // the chunk after the last is the last again (never used)
-                    const unsigned *a = qa_lds + 1 * 2 * CHA + l31 * KC;
+                    const unsigned *a = qa_lds + 1 * 2 * CHA + lrow * KC;
                     stage64(cn, 0);
                     PD_QA_WLOAD(a0, a1, a2, a3, 2 * cn);
                     PD_QA_WLOAD(b0, b1, b2, b3, 2 * cn + 1);
-                    block(a, c0, c1, c2, c3);
-                    block(a + CHA, d0, d1, d2, d3);
+                    block(nt_, a, c0, c1, c2, c3);
+                    block(nt_, a + CHA, d0, d1, d2, d3);
                     PD_QA_WAIT(0, a0, a1, a2, a3);
                     PD_QA_WAIT(0, b0, b1, b2, b3);
                     __syncthreads();
@@ -185,26 +231,27 @@ __global__ __launch_bounds__(PD_QA_THREADS) void pd_qkv_attn_kernel(PdQkvAttnArg
         } else
         for (int c = 0; c < nk64; ++c) {
             const int cn = min(c + 1, nk64 - 1);                 // the chunk after the last is the last again (never used)
-            const unsigned *a = qa_lds + (c & 1) * 2 * CHA + l31 * KC;
+            const unsigned *a = qa_lds + (c & 1) * 2 * CHA + lrow * KC;
             if constexpr (BARE == 0) {
                 if (c + 1 < nk64) {
                     stage64(cn, (c + 1) & 1);                    // in flight, oldest first: the second block's weights [4, from the previous turn], this DMA [2]
-                    block(a, a0, a1, a2, a3);
+                    block(nt_, a, a0, a1, a2, a3);
                     PD_QA_WLOAD(a0, a1, a2, a3, 2 * cn);         //   ... + the next chunk's first block [4]
-                    PD_QA_WAIT(6, b0, b1, b2, b3);               // the second block's weights have landed; the DMA [2] and the loads just issued [4] may fly
-                    block(a + CHA, b0, b1, b2, b3);
+                    // the second block's weights have landed; the DMA [2, a wave that stages] and the loads just issued [4] may fly
+                    PD_QA_WAIT_STAGED(stages, b0, b1, b2, b3);
+                    block(nt_, a + CHA, b0, b1, b2, b3);
                     PD_QA_WLOAD(b0, b1, b2, b3, 2 * cn + 1);     //   ... + the next chunk's second block [4]
                     PD_QA_WAIT(4, a0, a1, a2, a3);               // the next chunk's rows and first block have landed; the second block may still fly
                 } else {                                         // the last chunk requests nothing (round 6; it used to re-stage itself: 1 / 8 of the loop's L2 traffic
-                    block(a, a0, a1, a2, a3);                    //   and a whole load latency at the loop's end, for operands never used)
+                    block(nt_, a, a0, a1, a2, a3);               //   and a whole load latency at the loop's end, for operands never used)
                     PD_QA_WAIT(0, b0, b1, b2, b3);
-                    block(a + CHA, b0, b1, b2, b3);
+                    block(nt_, a + CHA, b0, b1, b2, b3);
                 }
             } else {                                             // development variants (see BARE): every wait drains
                 if constexpr (BARE != 2 && BARE != 3) stage64(cn, (c + 1) & 1);
-                if constexpr (BARE != 4) block(a, a0, a1, a2, a3);
+                if constexpr (BARE != 4) block(nt_, a, a0, a1, a2, a3);
                 if constexpr (BARE != 1 && BARE != 3) PD_QA_WLOAD(a0, a1, a2, a3, 2 * cn);
-                if constexpr (BARE != 4) block(a + CHA, b0, b1, b2, b3);
+                if constexpr (BARE != 4) block(nt_, a + CHA, b0, b1, b2, b3);
                 if constexpr (BARE != 1 && BARE != 3) PD_QA_WLOAD(b0, b1, b2, b3, 2 * cn + 1);
                 PD_QA_WAIT(0, a0, a1, a2, a3);
                 PD_QA_WAIT(0, b0, b1, b2, b3);
@@ -212,30 +259,60 @@ __global__ __launch_bounds__(PD_QA_THREADS) void pd_qkv_attn_kernel(PdQkvAttnArg
             __syncthreads();
         }
         PD_QA_WAIT(0, b0, b1, b2, b3);
+    };
+    if constexpr (M16) {
+        switch (nt16) {
+        case 1: kloop(std::integral_constant<int, 1>()); break;
+        case 2: kloop(std::integral_constant<int, 2>()); break;
+        case 3: kloop(std::integral_constant<int, 3>()); break;
+        case 4: kloop(std::integral_constant<int, 4>()); break;
+        case 5: kloop(std::integral_constant<int, 5>()); break;
+        default: kloop(std::integral_constant<int, 6>()); break;
+        }
+    } else {
+        kloop(std::integral_constant<int, 6>());
     }
 #undef PD_QA_WLOAD
 #undef PD_QA_WAIT
+#undef PD_QA_WAIT_STAGED
     if constexpr (BARE == 5) {
-        if (acc[0][0] == 123.456f) g.ctx[tid] = 1u;                // keep the product alive
+        if (acc[0][0] + acc4[0][0][0] == 123.456f) g.ctx[tid] = 1u;                // keep the product alive
         return;
     }
     // ---- 2. Q | K | V of the workgroup's rows as fp32 in LDS (every wave is past its last fragment read: the barrier that ended the loop) ----
     float *img = (float *)qa_lds;                                // [G N + 1][LDR]: columns [0, 128) q / sqrt(dh), [128, 256) k, [256, 384) v; row G N = 0
     float *Sall = img + (size_t)(G * N + 1) * LDR;               // [3 teams][32][LS]
     {
+        const float qscale = 0.08838834764831845f;               // 1/sqrt(128): pd_attn_mma_kernel scales q as it stages it
+        if constexpr (M16) {                                     // 16x16 tiles: lane = column % 16 + 16 (row / 4), register = row % 4; a tile not run holds no row < rows
+#pragma unroll
+            for (int ct = 0; ct < 2; ++ct) {
+                const float bias = g.bias[ntile * 32 + 16 * ct + l15];               // in_proj row = column of the QKV matrix
+                const int lcol = third * DH + (wave & 3) * 32 + 16 * ct + l15;
+#pragma unroll
+                for (int t = 0; t < 2 * RT; ++t)
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const int row = 16 * t + 4 * kg + i;
+                        float v = fmaf(acc4[M16 ? t : 0][ct][i], g.c_scale, bias);   // = what pd_gemm_strip_kernel stored as QKV
+                        if (third == 0) v *= qscale;
+                        if (row < rows) img[row * LDR + lcol] = v;
+                    }
+            }
+        } else {
         const int col = ntile * 32 + l31;                        // in_proj row = column of the QKV matrix
         const float bias = g.bias[col];
         const int lcol = third * DH + (wave & 3) * 32 + l31;
-        const float qscale = 0.08838834764831845f;               // 1/sqrt(128): pd_attn_mma_kernel scales q as it stages it
 #pragma unroll
         for (int mi = 0; mi < RT; ++mi)
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
                 const int row = mi * 32 + 4 * hi + (i & 3) + 8 * (i >> 2);
-                float v = fmaf(acc[mi][i], g.c_scale, bias);     // = what pd_gemm_strip_kernel stored as QKV
+                float v = fmaf(acc[M16 ? 0 : mi][i], g.c_scale, bias);     // = what pd_gemm_strip_kernel stored as QKV
                 if (third == 0) v *= qscale;
                 if (row < rows) img[row * LDR + lcol] = v;
             }
+        }
         for (int c = tid; c < LDR; c += PD_QA_THREADS) img[G * N * LDR + c] = 0.0f;       // the row every index beyond N reads
     }
     __syncthreads();

@@ -127,6 +127,77 @@ static void run_perm(const char *name, float *d_out, unsigned long long *d_cyc, 
     printf("v_mfma_f32_32x32x16_f16 after 4 v_perm_b32, %-44s %6.1f counter ticks / MFMA\n", name, (double)cyc / ((double)iters * 12));
 }
 
+// the fp16-plane GEMMs' two candidate shapes on RANDOM fp16 data (on zeros both rank by cycles alone and the clock the chip holds does not show), the same 64 x 64
+// output tile per wave and 32 k per turn, every operand re-read from LDS by ds_read_b128 each turn: SHAPE 0 = 8 v_mfma_f32_32x32x16_f16 (2 x 2 tiles x 2 k steps),
+// SHAPE 1 = 16 v_mfma_f32_16x16x32_f16 (4 x 4 tiles); 8 fragment reads per turn either way, lane-linear (conflict-free).  One or two waves per SIMD (block size).
+template <int SHAPE>
+__global__ void probe_lds(float *out, int iters, unsigned long long *cyc, const unsigned *src) {
+    typedef unsigned u4 __attribute__((ext_vector_type(4)));
+    __shared__ __attribute__((aligned(16))) unsigned frag[2][8][64 * 4];
+    for (int i = threadIdx.x; i < 2 * 8 * 256; i += blockDim.x) (&frag[0][0][0])[i] = src[i];
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    f32x16 c16[4];
+    f32x4 c4[16];
+    for (int j = 0; j < 4; ++j)
+        for (int i = 0; i < 16; ++i) c16[j][i] = 0.0f;
+    for (int j = 0; j < 16; ++j)
+        for (int i = 0; i < 4; ++i) c4[j][i] = 0.0f;
+    const unsigned long long t0 = __builtin_readcyclecounter();
+    for (int it = 0; it < iters; ++it) {
+        const unsigned base = (unsigned)(size_t)&frag[it & 1][0][lane * 4];
+        u4 f[8];
+        asm volatile("ds_read_b128 %0, %8\n\tds_read_b128 %1, %8 offset:1024\n\tds_read_b128 %2, %8 offset:2048\n\tds_read_b128 %3, %8 offset:3072\n\t"
+                     "ds_read_b128 %4, %8 offset:4096\n\tds_read_b128 %5, %8 offset:5120\n\tds_read_b128 %6, %8 offset:6144\n\tds_read_b128 %7, %8 offset:7168\n\t"
+                     "s_waitcnt lgkmcnt(0)"
+                     : "=&v"(f[0]), "=&v"(f[1]), "=&v"(f[2]), "=&v"(f[3]), "=&v"(f[4]), "=&v"(f[5]), "=&v"(f[6]), "=&v"(f[7]) : "v"(base) : "memory");
+        if (SHAPE == 0) {      // f[0..3]: A (row tile, k step), f[4..7]: B (column tile, k step)
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+                for (int r = 0; r < 2; ++r)
+#pragma unroll
+                    for (int c = 0; c < 2; ++c)
+                        c16[2 * r + c] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, f[2 * r + ks]), __builtin_bit_cast(f16x8, f[4 + 2 * c + ks]), c16[2 * r + c], 0, 0, 0);
+        } else {               // f[0..3]: A row tiles, f[4..7]: B column tiles
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+#pragma unroll
+                for (int c = 0; c < 4; ++c)
+                    c4[4 * r + c] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, f[r]), __builtin_bit_cast(f16x8, f[4 + c]), c4[4 * r + c], 0, 0, 0);
+        }
+    }
+    const unsigned long long t1 = __builtin_readcyclecounter();
+    float s = 0.0f;
+    for (int j = 0; j < 4; ++j)
+        for (int i = 0; i < 16; ++i) s += c16[j][i];
+    for (int j = 0; j < 16; ++j)
+        for (int i = 0; i < 4; ++i) s += c4[j][i];
+    out[(blockIdx.x * blockDim.x + threadIdx.x) & 65535] = s;
+    if (threadIdx.x == 0 && blockIdx.x == 0) *cyc = t1 - t0;
+}
+template <int SHAPE>
+static void run_lds(int waves_per_simd, float *d_out, unsigned long long *d_cyc, const unsigned *src) {
+    const int iters = 20000, threads = 256 * waves_per_simd;
+    hipLaunchKernelGGL((probe_lds<SHAPE>), dim3(256), dim3(threads), 0, 0, d_out, iters, d_cyc, src);
+    hipDeviceSynchronize();
+    hipEvent_t e0, e1;
+    hipEventCreate(&e0);
+    hipEventCreate(&e1);
+    hipEventRecord(e0);
+    hipLaunchKernelGGL((probe_lds<SHAPE>), dim3(256), dim3(threads), 0, 0, d_out, iters, d_cyc, src);
+    hipEventRecord(e1);
+    hipEventSynchronize(e1);
+    float ms;
+    hipEventElapsedTime(&ms, e0, e1);
+    unsigned long long cyc;
+    hipMemcpy(&cyc, d_cyc, 8, hipMemcpyDeviceToHost);
+    const double n = (double)iters * (SHAPE ? 16 : 8);                       // instructions per wave
+    const double flop = 2.0 * 64 * 64 * 32 * iters * (threads / 64) * 256;   // 64 x 64 x 32 per wave and turn
+    printf("%-28s random fp16 from LDS, %d wave(s) / SIMD: %6.1f counter ticks / instruction, %6.1f ticks / 32-k turn, %7.1f TFLOP/s chip (wall)\n",
+           SHAPE ? "v_mfma_f32_16x16x32_f16" : "v_mfma_f32_32x32x16_f16", waves_per_simd, (double)cyc / n, (double)cyc / iters, flop / (ms * 1e-3) / 1e12);
+}
+
 template <int NACC, int BIG>
 static void run(const char *name, float *d_out, unsigned long long *d_cyc, double ghz) {
     const int iters = 2000;
@@ -175,5 +246,25 @@ int main() {
     run_perm<2>("(no un-zips)", d_out, d_cyc, src);
     run_perm<0>("into the SAME registers every time:", d_out, d_cyc, src);
     run_perm<1>("into two alternating register sets:", d_out, d_cyc, src);
+    {   // random fp16 in [-1, 1) (a fixed LCG): 2 sets x 8 fragments x 1 KiB
+        static unsigned h[2 * 8 * 256];
+        unsigned st = 12345u;
+        auto half = [&]() {
+            st = st * 1664525u + 1013904223u;
+            const _Float16 v = (_Float16)(((int)(st >> 8) & 0xffff) / 32768.0f - 1.0f);
+            unsigned short b;
+            __builtin_memcpy(&b, &v, 2);
+            return (unsigned)b;
+        };
+        for (unsigned &w : h) { const unsigned lo = half(); w = lo | (half() << 16); }
+        unsigned *rnd;
+        hipMalloc(&rnd, sizeof(h));
+        hipMemcpy(rnd, h, sizeof(h), hipMemcpyHostToDevice);
+        for (int rep = 0; rep < 2; ++rep)          // alternating, twice: the order must not decide
+            for (int w = 1; w <= 2; ++w) {
+                run_lds<0>(w, d_out, d_cyc, rnd);
+                run_lds<1>(w, d_out, d_cyc, rnd);
+            }
+    }
     return 0;
 }
