@@ -537,6 +537,50 @@ def make_decode_args():
     print("decode_args.npz", os.path.getsize(os.path.join(OUT, "decode_args.npz")))
 
 
+GGS_INPUTS_SCENE = dict(N=6, H=192, W=320, per_pair=40, seed=706, x0_seed=7)
+GGS_INPUTS_SETTINGS = {"default": (1e-4, 1e-2), "never_clipped": (1.0, 1e-4), "crossing": (3e-4, 1e-4)}     # (alpha, learning_rate)
+
+
+def make_ggs_inputs():
+    """tests/golden/ggs_inputs.npz -- the reference's GGS on a NON-SQUARE image (192 x 320: min(H, W) / 2, W / 2 and H / 2 are not one
+    number) and at three settings of (alpha, learning_rate): the default (the clip active in every iteration), one in which it never is,
+    and one that crosses (tests/ggs_input_cases.py states how they were chosen; tests/test_ggs_inputs_cpu.py asserts the regimes).
+
+    The reference's own code, executed in place: compute_sampson_distance, GGS_optimize and geometry_guided_sampling
+    (util/geometry_guided_sampling.py -- mean focal, detach flags, threshold, clip, SGD with its hard-coded momentum 0.9, the five stages),
+    get_fundamental_matrices (util/get_fundamental_matrix.py) and pose_encoding_to_camera (util/camera_transform.py).  Restated, because
+    pytorch3d is absent: opencv_from_cameras_projection (oracle/pd_oracle.py, from the published 0.7.x algorithm) -- the one place where
+    the image size enters (scale = min(h, w) / 2, principal point (w / 2, h / 2)) -- with quaternion_to_matrix and hat.  So the fixture
+    pins how the reference FORWARDS img_shape (geometry_guided_sampling.py:16: b, c, h, w) and everything downstream of K; that the
+    restated conversion matches PyTorch3D's NDC projection is test_opencv_conversion_reproduces_the_ndc_projection's subject."""
+    torch.set_num_threads(1)
+    ref = RS.load_reference()
+    sc = GGS_INPUTS_SCENE
+    N, H, W = sc["N"], sc["H"], sc["W"]
+    enc = synth.make_cameras(N, seed=sc["seed"])
+    md = synth.make_matches(enc, H, W, per_pair=sc["per_pair"], seed=sc["seed"])
+    pm = O.prepare_matches(md["kp1"], md["kp2"], md["i12"], md["img_shape"])
+    pmr = proc_matches(pm, H, W)
+    x0 = synth.perturb_pose(enc, seed=sc["x0_seed"])
+    out = {"enc": enc, "kp1": md["kp1"], "kp2": md["kp2"], "i12": md["i12"], "img_shape": np.array(md["img_shape"]), "x0": x0.numpy()}
+    flag_sets = {"all": (True, True, True), "fl": (False, False, True), "r": (True, False, False), "t": (False, True, False)}
+    for fname, (uR, uT, uF) in flag_sets.items():        # (independent of alpha and learning_rate: stored once)
+        xr = x0.clone().requires_grad_(True)
+        v, pr = ref.compute_sampson_distance(xr, 0, pmr, update_R=uR, update_T=uT, update_FL=uF, sampson_max=GGS_CFG["sampson_max"])
+        (gr,) = torch.autograd.grad(v.mean(), xr)
+        out[f"sam_{fname}_values"], out[f"sam_{fname}_nvalid"], out[f"sam_{fname}_loss"] = v.detach().numpy(), len(v), v.mean().item()
+        out[f"sam_{fname}_print"], out[f"sam_{fname}_grad"] = pr.item(), gr.numpy()
+    for sname, (alpha, lr) in GGS_INPUTS_SETTINGS.items():
+        out[f"{sname}_alpha_lr"] = np.array([alpha, lr], dtype=np.float64)
+        for fname, (uR, uT, uF) in flag_sets.items():
+            cfg = dict(GGS_CFG, alpha=alpha, learning_rate=lr, iter_num=3)
+            out[f"{sname}_opt_{fname}_k3"] = quiet(ref.GGS_optimize, x0.clone(), 0, pmr, update_R=uR, update_T=uT, update_FL=uF, **cfg).numpy()
+        cfg = dict(GGS_CFG, alpha=alpha, learning_rate=lr, iter_num=2)
+        out[f"{sname}_guide_k2"] = quiet(ref.geometry_guided_sampling, x0.clone(), 3, md, cfg).numpy()
+    np.savez_compressed(os.path.join(OUT, "ggs_inputs.npz"), **out)
+    print("ggs_inputs.npz", os.path.getsize(os.path.join(OUT, "ggs_inputs.npz")))
+
+
 def make_live_reference():
     """tests/golden/live_reference.npz -- the reference's Denoiser.forward (models/denoiser.py), geometry_guided_sampling
     (util/geometry_guided_sampling.py) and MultiScaleImageFeatureExtractor (models/image_feature_extractor.py, around the restated ViT
@@ -591,6 +635,8 @@ if __name__ == "__main__":
         make_live_reference()   # only the fixture of the live-reference comparisons
     elif len(sys.argv) > 1 and sys.argv[1] == "decode_args":
         make_decode_args()      # only the decode-parameter fixture
+    elif len(sys.argv) > 1 and sys.argv[1] == "ggs_inputs":
+        make_ggs_inputs()       # only the non-square / non-default-optimiser GGS fixture
     elif len(sys.argv) > 1 and sys.argv[1] == "pred_x0":
         make_pred_x0()          # only the objective="pred_x0" fixture
     elif len(sys.argv) > 1 and sys.argv[1] == "guided_free":
@@ -613,5 +659,6 @@ if __name__ == "__main__":
         make_guided_free()
         make_guided_free(seeds=(0,), N=20, cond_start=10, per_pair=300, name="guided_free_full")
         make_decode_args()
+        make_ggs_inputs()
         make_live_reference()
         make_default_cfg()

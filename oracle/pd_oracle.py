@@ -349,12 +349,13 @@ def prepare_matches(kp1: np.ndarray, kp2: np.ndarray, i12: np.ndarray, img_shape
 
 def ggs_optimize(x: torch.Tensor, pm: Dict, update_R=True, update_T=True, update_FL=True, alpha=1e-4,
                  learning_rate=1e-2, iter_num=100, sampson_max=10, min_matches=10, trace: Optional[list] = None,
-                 **_):
+                 momentum=0.9, **_):
     """Returns (x_new detached, last sampson_to_print, iterations actually stepped).
 
     Autograd-based exactly like the reference; the SGD(momentum=0.9, dampening=0) step and
     clip_grad_norm_ (coef = max_norm / (||g|| + 1e-6), clamped to 1) are written out explicitly.
-    ``trace`` (optional list) receives per-iteration dicts (loss, n_valid, grad, x_after).
+    ``trace`` (optional list) receives per-iteration dicts (loss, n_valid, grad, x_after, gnorm = ||g|| before the clip, coef).
+    ``momentum``: the reference constructs SGD(momentum=0.9) (:89); other values restate what the engine's cfg field admits.
     """
     x = x.detach().clone().requires_grad_(True)
     if update_R and update_T and update_FL:
@@ -372,15 +373,16 @@ def ggs_optimize(x: torch.Tensor, pm: Dict, update_R=True, update_T=True, update
         mask = (g.abs() > 0)                                                          # :116
         x_norm = (x.detach() * mask).norm()                                           # :117
         max_norm = alpha * x_norm / learning_rate                                     # :119
-        coef = torch.clamp(max_norm / (g.norm() + 1e-6), max=1.0)                     # :121 clip_grad_norm_
+        gnorm = g.norm()
+        coef = torch.clamp(max_norm / (gnorm + 1e-6), max=1.0)                        # :121 clip_grad_norm_
         g = g * coef
-        buf = g.clone() if buf is None else 0.9 * buf + g                             # torch.optim.SGD momentum
+        buf = g.clone() if buf is None else momentum * buf + g                        # torch.optim.SGD momentum
         with torch.no_grad():
             x -= learning_rate * buf                                                  # :122
         steps += 1
         if trace is not None:
             trace.append({"loss": loss.detach().clone(), "n_valid": len(valid), "grad": g.detach().clone(),
-                          "x": x.detach().clone()})
+                          "x": x.detach().clone(), "gnorm": gnorm.detach().clone(), "coef": coef.detach().clone()})
     return x.detach(), to_print, steps
 
 

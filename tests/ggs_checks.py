@@ -127,3 +127,47 @@ def check_steps(out, x0, ref64, ref32, tag=""):
     e, bnd = step_group_errs(out, x0, ref64), bounds(step_group_errs(ref32, x0, ref64), K_STEP, FLOOR_STEP)
     assert not within(e, bnd), (tag, "step per group vs fp64", within(e, bnd))
     return e, bnd
+
+
+def trace_rows(trace):
+    """An oracle trace (pd_oracle.ggs_optimize(trace=[..])) as rows (pose after the iteration, loss, valid count, |g| before the clip)."""
+    return [(t["x"], float(t["loss"]), int(t["n_valid"]), float(t["gnorm"])) for t in trace]
+
+
+def engine_trace_rows(tr, n_frames, iters):
+    """The engine's trace of ONE sequence (ggs_optimize(trace=True)[2][b]: [iters, N*9 + 3]) as the same rows."""
+    tr = torch.as_tensor(tr).detach().cpu()
+    w = n_frames * 9
+    return [(tr[i, :w], float(tr[i, w]), int(tr[i, w + 1]), float(tr[i, w + 2])) for i in range(iters)]
+
+
+def trace_errs(rows, x0, trace64, trace32):
+    """Rows of a per-iteration trace against the fp64 oracle's, iteration by iteration: the pose per column group relative to the ORACLE'S
+    step of that iteration (step_group_errs from the oracle's previous iterate), and |g| before the clip relative to the oracle's; each
+    with the bound its rule gives from the fp32 oracle's own distance (K_STEP / FLOOR_STEP, K_GRAD / FLOOR_GRAD).
+    Returns [(step errors, step bounds, gnorm error, gnorm bound)] per iteration."""
+    out = []
+    prev = _x(x0, torch.float64)
+    for (x, _, _, gn), t64, t32 in zip(rows, trace64, trace32):
+        e = step_group_errs(x, prev, t64["x"])
+        bnd = bounds(step_group_errs(t32["x"], prev, t64["x"]), K_STEP, FLOOR_STEP)
+        g64 = float(t64["gnorm"])
+        out.append((e, bnd, abs(gn - g64) / g64, max(K_GRAD * abs(float(t32["gnorm"]) - g64) / g64, FLOOR_GRAD)))
+        prev = t64["x"]
+    return out
+
+
+def check_trace(rows, x0, trace64, trace32, tag=""):
+    """Every iteration of a trace against fp64: pose per group (rule of check_steps, per iteration), valid count equal, loss within 1e-4
+    relative (the bound of test_ggs_per_iteration_trace_vs_oracle), |g| before the clip under the gradient rule.  Returns the worst
+    (step errors per group, gnorm error, gnorm bound at that iteration)."""
+    assert len(rows) == len(trace64) == len(trace32), (tag, len(rows), len(trace64), len(trace32))
+    worst, worst_gn = {g: 0.0 for g in GROUPS}, (0.0, FLOOR_GRAD)
+    for i, ((_, loss, n, _), t64, (e, bnd, egn, bgn)) in enumerate(zip(rows, trace64, trace_errs(rows, x0, trace64, trace32))):
+        assert n == t64["n_valid"], (tag, i, "valid count", n, t64["n_valid"])
+        assert abs(loss - float(t64["loss"])) < 1e-4 * abs(float(t64["loss"])), (tag, i, "loss", loss, float(t64["loss"]))
+        assert not within(e, bnd), (tag, i, "step of this iteration per group vs fp64", within(e, bnd))
+        assert egn <= bgn, (tag, i, "|g| before the clip vs fp64", egn, bgn)
+        worst = {g: max(worst[g], e[g]) for g in GROUPS}
+        worst_gn = max(worst_gn, (egn, bgn))
+    return worst, worst_gn[0], worst_gn[1]

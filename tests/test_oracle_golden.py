@@ -160,6 +160,41 @@ def test_geometry_guided_sampling_golden(golden):
     assert rel_err(xo, g["guide_k10"]) < 2e-5
 
 
+@pytest.mark.parametrize("setting", ["default", "never_clipped", "crossing"])
+def test_ggs_on_a_non_square_image_and_outside_the_clipped_regime_golden(golden, setting):
+    """The oracle in fp32 against tests/golden/ggs_inputs.npz (the reference executed in place on a 192 x 320 scene at three settings of
+    (alpha, learning_rate): oracle/make_golden.py ggs_inputs), under the bounds of the square fixture's tests above.  The scene and the
+    settings are the ones tests/ggs_input_cases.py hands the GPU tests."""
+    import ggs_input_cases as Cs
+    g = golden["ggs_inputs"]
+    md, _, x0c = Cs.scene(*Cs.FIXTURE_SCENE)
+    assert tuple(int(v) for v in g["img_shape"]) == (6, 3, 192, 320) == tuple(md["img_shape"])
+    assert np.array_equal(g["kp1"], md["kp1"]) and np.array_equal(g["kp2"], md["kp2"]) and np.array_equal(g["i12"], md["i12"])
+    assert np.array_equal(g["x0"], x0c.numpy())
+    cfg = Cs.cfg_of(setting, Cs.FIXTURE_SCENE)
+    assert [cfg["alpha"], cfg["learning_rate"]] == g[f"{setting}_alpha_lr"].tolist()
+    pm, x0 = _pm(g), torch.from_numpy(g["x0"])
+    for fname, flags in FLAGS.items():
+        if setting == "default":                                 # (the Sampson values do not depend on the optimiser's settings)
+            x = x0.clone().requires_grad_(True)
+            v, pr = O.compute_sampson_distance(x, pm, *flags)
+            (grad,) = torch.autograd.grad(v.mean(), x)
+            tag = f"sam_{fname}"
+            assert len(v) == int(g[tag + "_nvalid"])
+            assert rel_err(v, g[tag + "_values"]) < 2e-5
+            assert abs(v.mean().item() - float(g[tag + "_loss"])) < 2e-5 * abs(float(g[tag + "_loss"]))
+            assert abs(pr.item() - float(g[tag + "_print"])) < 2e-5 * abs(float(g[tag + "_print"]))
+            assert rel_err(grad, g[tag + "_grad"]) < 1e-4
+        xo, _, steps = O.ggs_optimize(x0.clone(), pm, *flags, **dict(cfg, iter_num=3))
+        assert steps == (6 if fname == "all" else 3)
+        assert rel_err(xo, g[f"{setting}_opt_{fname}_k3"]) < 1e-5
+    md_g = {"kp1": g["kp1"], "kp2": g["kp2"], "i12": g["i12"], "img_shape": tuple(int(v) for v in g["img_shape"])}
+    assert rel_err(O.geometry_guided_sampling(x0.clone(), 3, md_g, dict(cfg, iter_num=2)), g[f"{setting}_guide_k2"]) < 2e-5
+    # the settings differ where they should: the stored results are not one result three times
+    if setting != "default":
+        assert rel_err(g[f"{setting}_opt_all_k3"], g["default_opt_all_k3"]) > 1e-4
+
+
 def test_early_exit_golden(golden):
     g = golden["ggs"]
     md = {"kp1": g["bad_kp1"], "kp2": g["bad_kp2"], "i12": g["bad_i12"], "img_shape": tuple(int(v) for v in g["img_shape"])}
