@@ -266,6 +266,9 @@ int pd_ggs_set_matches_csr_async(pd_engine *eng, int seq_first, int n_seqs, cons
                                  const double *kp2, const int64_t *i12, int n_frames, int height, int width,
                                  const pd_match_hints *hints, void *stream);
 
+/* The same ingestion with one frame count per sequence -- ragged batches in one call, sequences of 65 .. 256 frames -- is the export
+ * pd_ggs_set_matches_csr_async_nf, declared with its contract in pd_engine_ingest.h (the function list of THIS header is pinned). */
+
 /* model_mean[B,N,9] (DEVICE, in/out) <- geometry_guided_sampling(model_mean, t, ...) for every
  * sequence b using match slot b: the five GGS_optimize calls (all, FL, R, T, all) of
  * geometry_guided_sampling.py:48-63.  stats_out (DEVICE, may be NULL) receives [B,5,4] floats:
@@ -334,8 +337,9 @@ int pd_ggs_loss_grad(pd_engine *eng, const float *x, int B, int N, int update_R,
  *        returns PD_ERR_INVALID_ARG.  A launch above 64 frames needs, and is refused with PD_ERR_UNSUPPORTED naming the number otherwise:
  *        every frame pair <= 512 matches; 2 <= workgroups per sequence <= 256 (so B <= CUs / 2; wgs_per_seq = 1 is refused); the item
  *        slots of a workgroup, ceil(pairs / (8 wgs)) x 8, within its LDS image (<= 208); 2 pairs + wgs + N exchange lines within the
- *        region.  Matches of such sequences are uploaded with pd_ggs_set_matches; pd_ggs_set_matches_csr_async stays limited to 64
- *        frames (PD_ERR_UNSUPPORTED above).  Every launch at N <= 64 is what it is without the option. */
+ *        region.  Matches of such sequences are uploaded with pd_ggs_set_matches or, on the device, with
+ *        pd_ggs_set_matches_csr_async_nf (pd_engine_ingest.h); pd_ggs_set_matches_csr_async itself stays limited to 64 frames (PD_ERR_UNSUPPORTED above).
+ *        Every launch at N <= 64 is what it is without the option. */
 #define PD_OPT_GGS_MAX_FRAMES 7
 int pd_engine_set_option(pd_engine *eng, int option, int value);
 /* Reads an option back.  PD_OPT_DENOISER_SPLIT: the mode in force (an engine created from weights that hold inf / NaN stays on 0 although

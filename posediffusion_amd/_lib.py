@@ -128,6 +128,10 @@ SIGNATURES = {
     "pd_debug_mfma_f16_subnormal": (_i, [C.POINTER(C.c_float), _vp]),
     "pd_debug_vit_tokens": (_i, [_vp, _vp, C.c_longlong, _vp]),
 }
+# the exports of include/pd_engine_ingest.h (the function list of pd_engine.h, and with it SIGNATURES, is pinned by the tests)
+EXT_SIGNATURES = {
+    "pd_ggs_set_matches_csr_async_nf": (_i, [_vp, _i, _i, C.POINTER(_i64), _vp, _vp, _vp, C.POINTER(_i), _i, _i, C.POINTER(pd_match_hints), _vp]),
+}
 
 _lib = None
 
@@ -157,7 +161,7 @@ def load():
             "There is no CPU fallback.")
     import torch  # noqa: F401  (loads the HIP runtime first)
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES}.items():
         if os.environ.get("PD_ENGINE_LIB") and not hasattr(lib, name):
             continue              # an older build under A / B lacks the newest debug exports
         fn = getattr(lib, name)   # AttributeError here = library does not match the header

@@ -20,6 +20,8 @@
 // kernels read the actual counts from the device descriptor.  A violated hint / out-of-range frame index empties the
 // slot and raises bit 2 / bit 1 of the engine's async error word (pd_check_async_error).
 #include "pd_internal.h"
+#include "pd_ggs_ingest_layout.h"
+#include "../../include/pd_engine_ingest.h"
 
 #include <algorithm>
 #include <string.h>
@@ -511,81 +513,486 @@ __global__ __launch_bounds__(64) void ingest_interleave_kernel(IngestArgs A) {
     }
 }
 
+// ==== sequences of more than PD_MAX_FRAMES frames (pd_ggs_set_matches_csr_async_nf) ==================================================
+// Up to 65 536 keys: no table of N * N entries fits LDS, and a histogram per (tile, key) would be gigabytes.  The stable sort by key
+// = i * N + j is therefore two stable passes over <= 257 digits, by j and then by i, each with the per-tile histogram and the
+// ballot-rank scatter of the kernels above; pass 1 moves a 4-byte row index, pass 2 gathers the fp64 points and casts them.  The
+// matches of a key are counted by global integer atomics (order-free sums).  Blob and scratch: pd_ggs_ingest_layout.h.
+//   ingest_nf_zero     cnt = 0
+//   ingest_nf_keys     tile of 1024 rows: validate, keys[m], cnt[key] += 1, digit j -> hist[j][tile]
+//   ingest_nf_prefix   one workgroup per digit: hist[d][.] becomes its exclusive prefix over the tiles, btot[d] the total
+//   ingest_nf_scatter<0>  one wavefront per tile, rows in order: src[first row of digit + rows of earlier tiles + rank] = m
+//   ingest_nf_hist2    tile of 1024 rows of src: digit i -> hist[i][tile];  ingest_nf_prefix again
+//   ingest_nf_scatter<1>  pts[sorted row] = (float) kp1 / kp2 of row src[q]
+//   ingest_nf_tables   one workgroup per sequence: scans over the keys (first row, pair index, work items), incidence positions
+//                      from per-frame row / column counts and a pair's rank in its row and column, the descriptor
+//   ingest_interleave  as above
+// A row without a key (frame index out of range) takes digit 256 in both passes: src stays a permutation of the rows, such rows
+// end behind every keyed one and are never written to pts.
+template <int THREADS>
+__device__ __forceinline__ int block_scan_incl_t(int v, int *scratch, int &total) {   // scratch: [THREADS / 64] ints of LDS
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int x = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const int y = __shfl_up(x, d, 64);
+        if (lane >= d) x += y;
+    }
+    __syncthreads();
+    if (lane == 63) scratch[wave] = x;
+    __syncthreads();
+    int base = 0, tot = 0;
+#pragma unroll
+    for (int w = 0; w < THREADS / 64; ++w) {
+        const int s = scratch[w];
+        if (w < wave) base += s;
+        tot += s;
+    }
+    total = tot;
+    return x + base;
+}
+
+__global__ __launch_bounds__(256) void ingest_nf_zero_kernel(IngestArgs A) {
+    const IngestSeq S = A.s[blockIdx.y];
+    PdIngestNfLayout L;
+    pd_ingest_nf_layout(S.M, A.N, A.P_cap, A.I_cap, L);
+    int *cnt = (int *)(S.blob + L.cnt);
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q <= A.N * A.N) cnt[q] = 0;
+}
+
+__global__ __launch_bounds__(256) void ingest_nf_keys_kernel(IngestArgs A) {
+    __shared__ int sh_hist[PD_ING_DIGITS];
+    const IngestSeq S = A.s[blockIdx.y];
+    const int tile = blockIdx.x;
+    if (tile >= S.n_tiles) return;
+    PdIngestNfLayout L;
+    pd_ingest_nf_layout(S.M, A.N, A.P_cap, A.I_cap, L);
+    for (int q = threadIdx.x; q < PD_ING_DIGITS; q += 256) sh_hist[q] = 0;
+    __syncthreads();
+    int *keys = (int *)(S.blob + L.keys), *cnt = (int *)(S.blob + L.cnt);
+    const int m0 = tile * ING_TILE, m1 = min(S.M, m0 + ING_TILE);
+    for (int m = m0 + threadIdx.x; m < m1; m += 256) {
+        const long long a = A.i12[2 * (S.first + m)], c = A.i12[2 * (S.first + m) + 1];
+        int key = -1;                                                         // (as ingest_hist_kernel: error bit 1, the slot is emptied)
+        if (a < 0 || a >= A.N || c < 0 || c >= A.N) atomicOr(A.err_flag, 2u);
+        else key = (int)(a * A.N + c);
+        keys[m] = key;
+        atomicAdd(&sh_hist[key < 0 ? PD_ING_DIGITS - 1 : (int)c], 1);
+        if (key >= 0) atomicAdd(&cnt[key], 1);
+    }
+    __syncthreads();
+    int *hist = (int *)(S.blob + L.hist);
+    for (int q = threadIdx.x; q < PD_ING_DIGITS; q += 256) hist[(size_t)q * S.n_tiles + tile] = sh_hist[q];
+}
+
+__global__ __launch_bounds__(256) void ingest_nf_hist2_kernel(IngestArgs A) {
+    __shared__ int sh_hist[PD_ING_DIGITS];
+    const IngestSeq S = A.s[blockIdx.y];
+    const int tile = blockIdx.x;
+    if (tile >= S.n_tiles) return;
+    PdIngestNfLayout L;
+    pd_ingest_nf_layout(S.M, A.N, A.P_cap, A.I_cap, L);
+    for (int q = threadIdx.x; q < PD_ING_DIGITS; q += 256) sh_hist[q] = 0;
+    __syncthreads();
+    const int *keys = (const int *)(S.blob + L.keys), *src = (const int *)(S.blob + L.src);
+    const int m0 = tile * ING_TILE, m1 = min(S.M, m0 + ING_TILE);
+    for (int q = m0 + threadIdx.x; q < m1; q += 256) {
+        const int key = keys[src[q]];
+        atomicAdd(&sh_hist[key < 0 ? PD_ING_DIGITS - 1 : key / A.N], 1);
+    }
+    __syncthreads();
+    int *hist = (int *)(S.blob + L.hist);
+    for (int q = threadIdx.x; q < PD_ING_DIGITS; q += 256) hist[(size_t)q * S.n_tiles + tile] = sh_hist[q];
+}
+
+// grid (PD_ING_DIGITS, sequences): the tiles of one digit, 256 per pass of the scan
+__global__ __launch_bounds__(256) void ingest_nf_prefix_kernel(IngestArgs A) {
+    __shared__ int scratch[4];
+    const IngestSeq S = A.s[blockIdx.y];
+    PdIngestNfLayout L;
+    pd_ingest_nf_layout(S.M, A.N, A.P_cap, A.I_cap, L);
+    int *h = (int *)(S.blob + L.hist) + (size_t)blockIdx.x * S.n_tiles;
+    int run = 0;
+    for (int t0 = 0; t0 < S.n_tiles; t0 += 256) {
+        const int t = t0 + threadIdx.x;
+        const int v = t < S.n_tiles ? h[t] : 0;
+        int tot;
+        const int incl = block_scan_incl_t<256>(v, scratch, tot);
+        if (t < S.n_tiles) h[t] = run + incl - v;
+        run += tot;
+    }
+    if (threadIdx.x == 0) ((int *)(S.blob + L.btot))[blockIdx.x] = run;
+}
+
+template <int PASS>
+__global__ __launch_bounds__(64) void ingest_nf_scatter_kernel(IngestArgs A) {
+    __shared__ int sh_next[PD_ING_DIGITS];             // next free output row of each digit for THIS tile
+    const IngestSeq S = A.s[blockIdx.y];
+    const int tile = blockIdx.x, lane = threadIdx.x;
+    if (tile >= S.n_tiles) return;
+    PdIngestNfLayout L;
+    pd_ingest_nf_layout(S.M, A.N, A.P_cap, A.I_cap, L);
+    const int *btot = (const int *)(S.blob + L.btot);
+    const int *hist = (const int *)(S.blob + L.hist);
+    int run = 0;
+    for (int q0 = 0; q0 < PD_ING_DIGITS; q0 += 64) {    // first row of a digit: exclusive scan over the digit totals, 64 at a time
+        const int q = q0 + lane;
+        const int v = q < PD_ING_DIGITS ? btot[q] : 0;
+        int x = v;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const int y = __shfl_up(x, d, 64);
+            if (lane >= d) x += y;
+        }
+        if (q < PD_ING_DIGITS) sh_next[q] = run + x - v + hist[(size_t)q * S.n_tiles + tile];
+        run += __shfl(x, 63, 64);
+    }
+    __syncthreads();
+    const int *keys = (const int *)(S.blob + L.keys);
+    int *src = (int *)(S.blob + L.src);
+    float4 *pts = (float4 *)(S.blob + L.pts);
+    const int m0 = tile * ING_TILE, m1 = min(S.M, m0 + ING_TILE);
+    for (int r0 = m0; r0 < m1; r0 += 64) {
+        const bool act = r0 + lane < m1;
+        const int m = !act ? 0 : PASS == 0 ? r0 + lane : src[r0 + lane];       // the upload row
+        const int key = act ? keys[m] : -1;
+        const int digit = key < 0 ? PD_ING_DIGITS - 1 : PASS == 0 ? key % A.N : key / A.N;
+        int dst = 0;
+        unsigned long long todo = __builtin_amdgcn_ballot_w64(act);
+        while (todo) {                                 // one pass per distinct digit of the round (at most 64)
+            const int leader = __builtin_ctzll(todo);
+            const int k = __builtin_amdgcn_readlane(digit, leader);
+            const unsigned long long same = __builtin_amdgcn_ballot_w64(act && digit == k);
+            if (act && digit == k) dst = sh_next[k] + __builtin_popcountll(same & ((1ull << lane) - 1ull));
+            __builtin_amdgcn_wave_barrier();
+            if (lane == leader) sh_next[k] += __builtin_popcountll(same);
+            __builtin_amdgcn_wave_barrier();
+            todo &= ~same;
+        }
+        if (PASS == 0) {
+            if (act) src[dst] = m;
+        } else if (key >= 0) {
+            const long long g = S.first + m;
+            pts[dst] = make_float4((float)A.kp1[2 * g], (float)A.kp1[2 * g + 1], (float)A.kp2[2 * g], (float)A.kp2[2 * g + 1]);
+        }
+    }
+}
+
+__global__ __launch_bounds__(ING_TABLE_THREADS) void ingest_nf_tables_kernel(IngestArgs A) {
+    __shared__ int scratch[ING_TABLE_THREADS / 64], flags[2];
+    __shared__ int col_lt[PD_GGS_LONG_MAX_FRAMES], self_p[PD_GGS_LONG_MAX_FRAMES], row_n[PD_GGS_LONG_MAX_FRAMES], goff[PD_GGS_LONG_MAX_FRAMES + 1];
+    const IngestSeq S = A.s[blockIdx.x];
+    PdIngestNfLayout L;
+    pd_ingest_nf_layout(S.M, A.N, A.P_cap, A.I_cap, L);
+    const int N = A.N, NN = N * N, tid = threadIdx.x;
+    int *cnt = (int *)(S.blob + L.cnt), *pex = (int *)(S.blob + L.pex), *crk = (int *)(S.blob + L.crk);
+    int4 *items = (int4 *)(S.blob + L.itm);
+    int2 *pair_ij = (int2 *)(S.blob + L.pij), *gpos = (int2 *)(S.blob + L.gps);
+    int *pair_item_off = (int *)(S.blob + L.pio), *ginc_off = (int *)(S.blob + L.gio);
+    if (tid < 2) flags[tid] = 0;
+    __syncthreads();
+    // (1) scans over the keys, ING_TABLE_THREADS per pass: first sorted row (cnt, in place), pair index (pex), first work item
+    int off_base = 0, pair_base = 0, item_base = 0, multi = 0, viol = 0;
+    for (int k0 = 0; k0 < NN; k0 += ING_TABLE_THREADS) {
+        const int key = k0 + tid;
+        const int m = key < NN ? cnt[key] : 0;
+        const int nch = (m + PD_ITEM_MAX_MATCHES - 1) / PD_ITEM_MAX_MATCHES;
+        int t_off, t_pair, t_item;
+        const int off = block_scan_incl_t<ING_TABLE_THREADS>(m, scratch, t_off) - m + off_base;
+        const int p = block_scan_incl_t<ING_TABLE_THREADS>(m > 0 ? 1 : 0, scratch, t_pair) - (m > 0 ? 1 : 0) + pair_base;
+        const int it = block_scan_incl_t<ING_TABLE_THREADS>(nch, scratch, t_item) - nch + item_base;
+        if (key < NN) {
+            cnt[key] = off;
+            pex[key] = p;
+            if (m > 0 && p < A.P_cap && it + nch <= A.I_cap) {
+                const int i = key / N, j = key - i * N;
+                pair_ij[p] = make_int2(i, j);
+                pair_item_off[p] = it;
+                int start = off;
+                for (int c = 0; c < nch; ++c) {
+                    const int len = pd_cut_len(m, nch, c);
+                    items[it + c] = make_int4(p, start, len, 0);
+                    start += len;
+                }
+                if (nch > 1) multi = 1;
+                if (A.per_pair_cap > 0 && m > A.per_pair_cap) viol = 1;
+            }
+        }
+        off_base += t_off;
+        pair_base += t_pair;
+        item_base += t_item;
+    }
+    const int n_pairs = pair_base, n_items = item_base;
+    if (multi) atomicOr(&flags[1], 1);
+    if (viol || (tid == 0 && (n_pairs > A.P_cap || n_items > A.I_cap || off_base != S.M))) atomicOr(&flags[0], 1);
+    if (tid == 0) {
+        cnt[NN] = off_base;
+        pex[NN] = n_pairs;
+    }
+    __syncthreads();                                       // pex, written by this workgroup, is read below
+    // (2) frame j: the pairs of its column (a, j) -- how many lie above the diagonal, whether (j, j) is one, the rank of each -- and of its row
+    if (tid < N) {
+        int c = 0;
+        for (int i = 0; i < N; ++i) {
+            const int key = i * N + tid;
+            const int has = pex[key + 1] > pex[key];
+            if (i == tid) {
+                col_lt[tid] = c;
+                self_p[tid] = has;
+            }
+            if (has) crk[key] = c++;
+        }
+        const int rows = pex[(tid + 1) * N] - pex[tid * N];
+        row_n[tid] = rows;
+        if (rows + c > A.deg_cap) atomicOr(&flags[0], 1);   // a frame in more pairs than the hint allows
+        goff[tid] = rows + c;                               // incidence rows of the frame ((j, j) has two)
+    }
+    __syncthreads();
+    const bool bad = flags[0] != 0;                         // (block-uniform)
+    {
+        const int d = tid < N ? goff[tid] : 0;
+        int tot;
+        const int incl = block_scan_incl_t<ING_TABLE_THREADS>(d, scratch, tot);
+        __syncthreads();
+        if (tid < N) goff[tid] = incl - d;
+        if (tid == 0) goff[N] = tot;
+    }
+    __syncthreads();
+    // (3) the rows of frame n, in pair order: (a, n) with a < n | (n, b) for every b, two rows for (n, n) | (a, n) with a > n
+    if (!bad) {
+        for (int q = tid; q <= N; q += ING_TABLE_THREADS) ginc_off[q] = goff[q];
+        if (tid == 0) pair_item_off[n_pairs] = n_items;
+        for (int key = tid; key < NN; key += ING_TABLE_THREADS) {
+            const int p = pex[key];
+            if (pex[key + 1] == p) continue;
+            const int i = key / N, j = key - i * N;
+            const int x = goff[i] + col_lt[i] + (p - pex[i * N]) + ((self_p[i] && j > i) ? 1 : 0);
+            const int y = i == j ? x + 1 : goff[j] + (i > j ? row_n[j] : 0) + crk[key];
+            gpos[p] = make_int2(x, y);
+        }
+    }
+    // (4) the descriptor: the fields pd_ggs_set_matches leaves above PD_MAX_FRAMES frames (no chunk tables, no lane tables)
+    if (tid == 0) {
+        PdSeqDesc D;
+        memset(&D, 0, sizeof(D));
+        D.pts = (const float4 *)(S.blob + L.pts);
+        D.pair_ij = pair_ij;
+        D.pair_item_off = pair_item_off;
+        D.items = items;
+        D.ptab = (const int4 *)(S.blob + L.gps);            // (zero entries, like the host builder's)
+        D.pchunk_off = (const int *)(S.blob + L.gps);
+        D.n_pchunks = bad ? 0 : (n_pairs + PD_GGS_THREADS - 1) / PD_GGS_THREADS;
+        D.gpos = gpos;
+        D.ginc_off = ginc_off;
+        D.single_item_pairs = flags[1] ? 0 : 1;
+        D.lstream = (const float4 *)(S.blob + L.cnt);
+        D.litems = (const int4 *)(S.blob + L.cnt);
+        D.lwave = (const int2 *)(S.blob + L.cnt);
+        D.lptab = (const int2 *)(S.blob + L.cnt);
+        D.M = bad ? 1 : S.M;
+        D.n_pairs = bad ? 0 : n_pairs;
+        D.n_items = bad ? 0 : n_items;
+        D.n_frames = N;
+        D.sc = A.sc;
+        D.cx = A.cx;
+        D.cy = A.cy;
+        *S.desc = D;
+        if (bad) atomicOr(A.err_flag, 4u);
+    }
+}
+
 // ---- host side ------------------------------------------------------------------------------------------------------
 static size_t tables_lds_bytes(int N, int P_cap, int C_cap) {
     // (+ 3 N^2 for the cut-rule candidates of the lane tables, which exist up to PD_LANE_MAX_FRAMES frames)
     return sizeof(int) * ((size_t)(N <= PD_LANE_MAX_FRAMES ? 7 : 4) * N * N + 2 * PD_LANE_WAVES + 2 * (size_t)P_cap + (size_t)(C_cap + 1) * (N + 1) + 16 + 4);
 }
 
-extern "C" int pd_ggs_set_matches_csr_async(pd_engine *eng, int seq_first, int n_seqs, const int64_t *seq_offsets,
-                                            const double *kp1, const double *kp2, const int64_t *i12, int n_frames, int height,
-                                            int width, const pd_match_hints *hints, void *stream) {
-    if (!eng || n_seqs <= 0 || seq_first < 0 || seq_first + n_seqs > eng->max_B || !seq_offsets || !kp1 || !kp2 || !i12) {
-        pd_set_error("pd_ggs_set_matches_csr_async: bad engine, slot range [%d, %d) or NULL pointer", seq_first, seq_first + n_seqs);
+// One launch group of a call: up to ING_MAX_SEQS sequences of ONE frame count, with one capacity set (the kernels index the layout by it)
+struct IngestItem {
+    int slot;
+    long long first;             // first row of the sequence in kp1 / kp2 / i12
+    int M;
+};
+struct IngestHints {
+    bool one_order;
+    int pairs, per_pair;
+};
+struct IngestSlice {
+    int N;
+    bool nf;                     // more than PD_MAX_FRAMES frames: the ingest_nf_* kernels
+    bool own_caps;               // pd_ggs_set_matches_csr_async_nf: the pair hint is capped by what the group's frame count admits
+    std::vector<IngestItem> items;
+    int P_cap, I_cap, C_cap, LS_cap;
+    bool single;
+    size_t lds_tab;
+};
+
+static int read_hints(const char *who, const pd_match_hints *hints, IngestHints &h) {
+    h.one_order = hints && hints->max_pairs > 0 && (hints->max_pairs & PD_MATCH_HINT_ONE_ORDER);
+    h.pairs = hints ? (hints->max_pairs > 0 ? (hints->max_pairs & ~PD_MATCH_HINT_ONE_ORDER) : hints->max_pairs) : 0;
+    h.per_pair = hints ? hints->max_matches_per_pair : 0;
+    if (h.pairs < 0 || h.per_pair < 0) {
+        pd_set_error("%s: negative hint", who);
         return PD_ERR_INVALID_ARG;
     }
-    const int N = n_frames;
-    PD_TRY(pd_ggs_frames_unsupported(eng, N, "pd_ggs_set_matches_csr_async"));
-    if (N > PD_MAX_FRAMES && N <= eng->max_N) {      // (PD_OPT_GGS_MAX_FRAMES above 64: the ingestion kernels keep N^2 counters in LDS)
-        pd_set_error("pd_ggs_set_matches_csr_async: device-side ingestion is limited to %d frames (n_frames=%d); upload the matches of longer "
-                     "sequences with pd_ggs_set_matches", PD_MAX_FRAMES, N);
+    return PD_OK;
+}
+
+// the matches of sequence b of a call -> items; 1 .. 2^31 - 1 of them
+static int add_item(const char *who, IngestSlice &sl, int slot, const int64_t *seq_offsets, int b) {
+    const long long M = seq_offsets[b + 1] - seq_offsets[b];
+    if (M <= 0 || M > 0x7fffffff) {
+        pd_set_error("%s: sequence %d holds %lld matches (need 1 .. 2^31-1; clear a slot with pd_ggs_set_matches(M = 0))", who, slot, M);
+        return PD_ERR_INVALID_ARG;
+    }
+    sl.items.push_back({slot, seq_offsets[b], (int)M});
+    return PD_OK;
+}
+
+// sizes the capacities of a group from its largest sequence and the hints; refuses what its kernels cannot take
+static int plan_slice(const char *who, IngestSlice &sl, const IngestHints &h) {
+    const int N = sl.N;
+    long long M_max = 0;
+    for (const IngestItem &it : sl.items) M_max = std::max<long long>(M_max, it.M);
+    sl.P_cap = h.pairs > 0 ? h.pairs : (int)std::min<long long>((long long)N * N, M_max);
+    // one hint serves every count of a ragged call: N frames hold at most N^2 pairs, N (N - 1) / 2 when no frame is in more than N - 1
+    // (PD_MATCH_HINT_ONE_ORDER: the degrees sum to twice the pairs) -- with an exact hint the plan is then the host-built tables'
+    if (sl.own_caps) sl.P_cap = (int)std::min<long long>(sl.P_cap, h.one_order ? std::max(1, N * (N - 1) / 2) : (long long)N * N);
+    sl.single = h.per_pair > 0 && h.per_pair <= PD_ITEM_MAX_MATCHES;
+    sl.I_cap = sl.single ? sl.P_cap : sl.P_cap + (int)(M_max / PD_ITEM_MAX_MATCHES) + 1;
+    sl.C_cap = (sl.P_cap + PD_GGS_THREADS - 1) / PD_GGS_THREADS;
+    sl.LS_cap = 0;
+    sl.lds_tab = 0;
+    if (sl.nf) return PD_OK;     // (only pd_ggs_long_kernel runs there: no chunk tables, no lane tables, every table kernel's LDS is static)
+    if (sl.C_cap > PD_GGS_MAX_PCHUNKS) {
+        pd_set_error("%s: up to %d frame pairs (max %d): pass pd_match_hints.max_pairs", who, sl.P_cap, PD_GGS_MAX_PCHUNKS * PD_GGS_THREADS);
         return PD_ERR_UNSUPPORTED;
     }
-    if (N <= 0 || N > PD_MAX_FRAMES || N > eng->max_N || height <= 0 || width <= 0) {
-        pd_set_error("pd_ggs_set_matches_csr_async: invalid n_frames=%d (<= %d) or image size %dx%d", N, std::min(PD_MAX_FRAMES, eng->max_N),
-                     height, width);
-        return PD_ERR_INVALID_ARG;
+    sl.lds_tab = tables_lds_bytes(N, sl.P_cap, sl.C_cap);
+    if (sl.lds_tab > 160 * 1024) {
+        pd_set_error("%s: tables need %zu B of LDS", who, sl.lds_tab);
+        return PD_ERR_UNSUPPORTED;
     }
-    PD_HIP_CHECK(hipSetDevice(eng->device));
-    hipStream_t s = (hipStream_t)stream;
-    const bool one_order = hints && hints->max_pairs > 0 && (hints->max_pairs & PD_MATCH_HINT_ONE_ORDER);
-    const int hint_pairs = hints ? (hints->max_pairs > 0 ? (hints->max_pairs & ~PD_MATCH_HINT_ONE_ORDER) : hints->max_pairs) : 0;
-    const int hint_per_pair = hints ? hints->max_matches_per_pair : 0;
-    if (hint_pairs < 0 || hint_per_pair < 0) {
-        pd_set_error("pd_ggs_set_matches_csr_async: negative hint");
-        return PD_ERR_INVALID_ARG;
-    }
-    // pass 1: validate every slice and size its capacities -- nothing is enqueued before the whole call is known to be launchable
-    struct Slice {
-        int nb, P_cap, I_cap, C_cap, LS_cap;
-        bool single;
-        size_t lds_tab;
-    };
-    std::vector<Slice> slices;
-    for (int b0 = 0; b0 < n_seqs; b0 += ING_MAX_SEQS) {
-        Slice sl;
-        sl.nb = std::min(ING_MAX_SEQS, n_seqs - b0);
-        // one capacity set for the whole slice (the kernels index the layout by it): from the largest sequence
-        long long M_max = 0;
-        for (int b = 0; b < sl.nb; ++b) {
-            const long long M = seq_offsets[b0 + b + 1] - seq_offsets[b0 + b];
-            if (M <= 0 || M > 0x7fffffff) {
-                pd_set_error("pd_ggs_set_matches_csr_async: sequence %d holds %lld matches (need 1 .. 2^31-1; clear a slot with "
-                             "pd_ggs_set_matches(M = 0))", seq_first + b0 + b, M);
-                return PD_ERR_INVALID_ARG;
+    // lane-per-item tables: sum_p ceil(m_p / len) <= M / len + P, so the item length never exceeds ceil(M / (items - P))
+    const bool lane_ok = sl.P_cap < PD_LANE_MAX_ITEMS && sl.C_cap == 1 && N <= PD_LANE_MAX_FRAMES;
+    const int len_cap = lane_ok ? (int)((M_max + (PD_LANE_MAX_ITEMS - sl.P_cap) - 1) / (PD_LANE_MAX_ITEMS - sl.P_cap)) : 0;
+    sl.LS_cap = lane_ok ? (len_cap + 1) / 2 : 0;
+    return PD_OK;
+}
+
+// blobs, host shadows and the kernels of one group.  `enqueued` is set with the first launch.
+static int enqueue_slice(pd_engine *eng, const char *who, const IngestSlice &sl, const IngestHints &hn, const double *kp1, const double *kp2,
+                         const int64_t *i12, int height, int width, hipStream_t s, bool &enqueued) {
+    const int nb = (int)sl.items.size(), N = sl.N, P_cap = sl.P_cap, I_cap = sl.I_cap, C_cap = sl.C_cap;
+    const bool single = sl.single, lane_ok = sl.LS_cap > 0;
+    IngestArgs A;
+    memset(&A, 0, sizeof(A));
+    A.kp1 = kp1;
+    A.kp2 = kp2;
+    A.i12 = (const long long *)i12;
+    A.N = N;
+    A.per_pair_cap = hn.per_pair;
+    A.sc = (float)std::min(height, width) / 2.0f;   // opencv_from_cameras_projection scale
+    A.cx = (float)width / 2.0f;
+    A.cy = (float)height / 2.0f;
+    A.err_flag = eng->d_err;
+    A.P_cap = P_cap;
+    A.I_cap = I_cap;
+    A.C_cap = sl.nf ? 0 : C_cap;                    // (ingest_interleave_kernel finds the items of either layout with these)
+    A.LS_cap = sl.LS_cap;
+    A.deg_cap = (hn.one_order ? 1 : 2) * (N - 1);
+    int max_tiles = 0;
+    for (int b = 0; b < nb; ++b) {
+        const int slot = sl.items[b].slot, M = sl.items[b].M;
+        size_t total;
+        if (sl.nf) {
+            PdIngestNfLayout L;
+            pd_ingest_nf_layout(M, N, P_cap, I_cap, L);
+            total = L.total;
+        } else {
+            IngestLayout L;
+            ingest_layout(M, N, P_cap, I_cap, C_cap, A.LS_cap, L);
+            total = L.total;
+        }
+        PdSeqHost &h = eng->seqs[slot];
+        if (h.blob_bytes < total) {
+            // first use of the slot at this capacity: the only allocation (synchronous).  The old blob may still be read by work
+            // in flight: it is parked behind an event on this stream (which has just waited for every use) and freed by a later upload
+            if (h.blob) {
+                hipEvent_t ev = nullptr;
+                if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess || hipEventRecord(ev, s) != hipSuccess) {
+                    pd_set_error("%s: cannot park the outgrown blob of slot %d", who, slot);
+                    return PD_ERR_HIP;
+                }
+                eng->retired_blobs.push_back({h.blob, ev});
             }
-            M_max = std::max(M_max, M);
+            h.blob = nullptr;
+            h.blob_bytes = 0;
+            if (hipMalloc(&h.blob, total + total / 4) != hipSuccess) {   // headroom for ragged batches
+                h.blob = nullptr;
+                memset(&h.desc, 0, sizeof(h.desc));
+                pd_set_error("%s: out of device memory for slot %d (%zu B)", who, slot, total + total / 4);
+                return PD_ERR_HIP;
+            }
+            h.blob_bytes = total + total / 4;
         }
-        sl.P_cap = hint_pairs > 0 ? hint_pairs : (int)std::min<long long>((long long)N * N, M_max);
-        sl.single = hint_per_pair > 0 && hint_per_pair <= PD_ITEM_MAX_MATCHES;
-        sl.I_cap = sl.single ? sl.P_cap : sl.P_cap + (int)(M_max / PD_ITEM_MAX_MATCHES) + 1;
-        sl.C_cap = (sl.P_cap + PD_GGS_THREADS - 1) / PD_GGS_THREADS;
-        if (sl.C_cap > PD_GGS_MAX_PCHUNKS) {
-            pd_set_error("pd_ggs_set_matches_csr_async: up to %d frame pairs (max %d): pass pd_match_hints.max_pairs", sl.P_cap,
-                         PD_GGS_MAX_PCHUNKS * PD_GGS_THREADS);
-            return PD_ERR_UNSUPPORTED;
-        }
-        sl.lds_tab = tables_lds_bytes(N, sl.P_cap, sl.C_cap);
-        if (sl.lds_tab > 160 * 1024) {
-            pd_set_error("pd_ggs_set_matches_csr_async: tables need %zu B of LDS", sl.lds_tab);
-            return PD_ERR_UNSUPPORTED;
-        }
-        // lane-per-item tables: sum_p ceil(m_p / len) <= M / len + P, so the item length never exceeds ceil(M / (items - P))
-        const bool lane_ok = sl.P_cap < PD_LANE_MAX_ITEMS && sl.C_cap == 1 && N <= PD_LANE_MAX_FRAMES;
-        const int len_cap = lane_ok ? (int)((M_max + (PD_LANE_MAX_ITEMS - sl.P_cap) - 1) / (PD_LANE_MAX_ITEMS - sl.P_cap)) : 0;
-        sl.LS_cap = lane_ok ? (len_cap + 1) / 2 : 0;
-        slices.push_back(sl);
+        A.s[b].first = sl.items[b].first;
+        A.s[b].M = M;
+        A.s[b].n_tiles = (M + ING_TILE - 1) / ING_TILE;
+        A.s[b].blob = (char *)h.blob;
+        A.s[b].desc = eng->d_seqs + slot;
+        max_tiles = std::max(max_tiles, A.s[b].n_tiles);
+        // host shadow = CAPACITIES: launch shapes are planned from these, kernels read the actual counts on the device
+        memset(&h.desc, 0, sizeof(h.desc));
+        h.desc.M = M;
+        h.desc.n_pairs = P_cap;
+        h.desc.n_items = I_cap;
+        h.desc.n_pchunks = C_cap;
+        h.desc.single_item_pairs = single ? 1 : 0;
+        h.desc.n_litems = lane_ok ? PD_LANE_MAX_ITEMS : 0;   // capacities again (the plan only asks whether the tables exist)
+        h.desc.n_lwaves = lane_ok ? PD_LANE_WAVES : 0;
+        h.desc.l_max_steps = A.LS_cap;
+        h.desc.n_frames = N;
+        h.desc.sc = A.sc;
+        h.desc.cx = A.cx;
+        h.desc.cy = A.cy;
+        h.max_item_len = single ? hn.per_pair : PD_ITEM_MAX_MATCHES;
+        // an upper bound (the host never learns the pair list): every pair in both orders, or one (PD_MATCH_HINT_ONE_ORDER; the tables
+        // kernel checks the degrees against it)
+        h.max_deg = std::min(P_cap, (hn.one_order ? 1 : 2) * (N - 1));
+        h.device_built = true;
     }
+    if (sl.nf) {
+        const dim3 tiles(max_tiles, nb), digits(PD_ING_DIGITS, nb);
+        hipLaunchKernelGGL(ingest_nf_zero_kernel, dim3((N * N + 1 + 255) / 256, nb), dim3(256), 0, s, A);
+        enqueued = true;
+        hipLaunchKernelGGL(ingest_nf_keys_kernel, tiles, dim3(256), 0, s, A);
+        hipLaunchKernelGGL(ingest_nf_prefix_kernel, digits, dim3(256), 0, s, A);
+        hipLaunchKernelGGL(ingest_nf_scatter_kernel<0>, tiles, dim3(64), 0, s, A);
+        hipLaunchKernelGGL(ingest_nf_hist2_kernel, tiles, dim3(256), 0, s, A);
+        hipLaunchKernelGGL(ingest_nf_prefix_kernel, digits, dim3(256), 0, s, A);
+        hipLaunchKernelGGL(ingest_nf_scatter_kernel<1>, tiles, dim3(64), 0, s, A);
+        hipLaunchKernelGGL(ingest_nf_tables_kernel, dim3(nb), dim3(ING_TABLE_THREADS), 0, s, A);
+    } else {
+        const size_t lds_hist = sizeof(int) * (size_t)N * N;
+        hipLaunchKernelGGL(ingest_hist_kernel, dim3(max_tiles, nb), dim3(256), lds_hist, s, A);
+        enqueued = true;
+        hipLaunchKernelGGL(ingest_tables_kernel, dim3(nb), dim3(ING_TABLE_THREADS), sl.lds_tab, s, A);
+        hipLaunchKernelGGL(ingest_scatter_kernel, dim3(max_tiles, nb), dim3(64), lds_hist, s, A);
+        if (A.LS_cap > 0) hipLaunchKernelGGL(ingest_lane_stream_kernel, dim3(PD_LANE_WAVES, nb), dim3(256), 0, s, A);
+    }
+    hipLaunchKernelGGL(ingest_interleave_kernel, dim3(I_cap, nb), dim3(64), 0, s, A);
+    if (hipGetLastError() != hipSuccess) {
+        pd_set_error("%s: a table kernel failed to launch", who);
+        return PD_ERR_HIP;
+    }
+    return PD_OK;
+}
+
+// the planned groups of a call, in order, on stream s
+static int run_slices(pd_engine *eng, const char *who, const std::vector<IngestSlice> &slices, const IngestHints &hn, const double *kp1,
+                      const double *kp2, const int64_t *i12, int height, int width, hipStream_t s) {
     const bool capturing = pd_stream_capturing(s);
     // the engine's own in-flight work (on whatever streams) may still read the slots' tables: a DEVICE-side wait, the host does not
     // block; and earlier uploads on other streams are ordered before this one, so the event recorded at the end covers them too
@@ -597,100 +1004,100 @@ extern "C" int pd_ggs_set_matches_csr_async(pd_engine *eng, int seq_first, int n
     }
     pd_free_retired_blobs(eng);
     bool enqueued = false;
+    int rc = PD_OK;
+    for (const IngestSlice &sl : slices) {
+        rc = enqueue_slice(eng, who, sl, hn, kp1, kp2, i12, height, width, s, enqueued);
+        if (rc) break;
+    }
     // every exit after the first enqueue records the upload event: later GGS launches on OTHER streams wait for it (pd_sample_phase /
     // pd_ggs_launch), on the device
-    auto finish = [&](int rc) {
-        if (enqueued && !capturing && pd_record_stream_event(eng->uploads, s) != PD_OK && rc == PD_OK) return (int)PD_ERR_HIP;
-        return rc;
-    };
-    int b0 = 0;
-    for (const Slice &sl : slices) {
-        const int nb = sl.nb, P_cap = sl.P_cap, I_cap = sl.I_cap, C_cap = sl.C_cap;
-        const bool single = sl.single, lane_ok = sl.LS_cap > 0;
-        IngestArgs A;
-        memset(&A, 0, sizeof(A));
-        A.kp1 = kp1;
-        A.kp2 = kp2;
-        A.i12 = (const long long *)i12;
-        A.N = N;
-        A.per_pair_cap = hint_per_pair;
-        A.sc = (float)std::min(height, width) / 2.0f;   // opencv_from_cameras_projection scale
-        A.cx = (float)width / 2.0f;
-        A.cy = (float)height / 2.0f;
-        A.err_flag = eng->d_err;
-        A.P_cap = P_cap;
-        A.I_cap = I_cap;
-        A.C_cap = C_cap;
-        A.LS_cap = sl.LS_cap;
-        A.deg_cap = (one_order ? 1 : 2) * (N - 1);
-        int max_tiles = 0;
-        for (int b = 0; b < nb; ++b) {
-            const int slot = seq_first + b0 + b;
-            const int M = (int)(seq_offsets[b0 + b + 1] - seq_offsets[b0 + b]);
-            IngestLayout L;
-            ingest_layout(M, N, P_cap, I_cap, C_cap, A.LS_cap, L);
-            PdSeqHost &h = eng->seqs[slot];
-            if (h.blob_bytes < L.total) {
-                // first use of the slot at this capacity: the only allocation (synchronous).  The old blob may still be read by work
-                // in flight: it is parked behind an event on this stream (which has just waited for every use) and freed by a later upload
-                if (h.blob) {
-                    hipEvent_t ev = nullptr;
-                    if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess || hipEventRecord(ev, s) != hipSuccess) {
-                        pd_set_error("pd_ggs_set_matches_csr_async: cannot park the outgrown blob of slot %d", slot);
-                        return finish(PD_ERR_HIP);
-                    }
-                    eng->retired_blobs.push_back({h.blob, ev});
-                }
-                h.blob = nullptr;
-                h.blob_bytes = 0;
-                if (hipMalloc(&h.blob, L.total + L.total / 4) != hipSuccess) {   // headroom for ragged batches
-                    h.blob = nullptr;
-                    memset(&h.desc, 0, sizeof(h.desc));
-                    pd_set_error("pd_ggs_set_matches_csr_async: out of device memory for slot %d (%zu B)", slot, L.total + L.total / 4);
-                    return finish(PD_ERR_HIP);
-                }
-                h.blob_bytes = L.total + L.total / 4;
-            }
-            A.s[b].first = seq_offsets[b0 + b];
-            A.s[b].M = M;
-            A.s[b].n_tiles = (M + ING_TILE - 1) / ING_TILE;
-            A.s[b].blob = (char *)h.blob;
-            A.s[b].desc = eng->d_seqs + slot;
-            max_tiles = std::max(max_tiles, A.s[b].n_tiles);
-            // host shadow = CAPACITIES: launch shapes are planned from these, kernels read the actual counts on the device
-            memset(&h.desc, 0, sizeof(h.desc));
-            h.desc.M = M;
-            h.desc.n_pairs = P_cap;
-            h.desc.n_items = I_cap;
-            h.desc.n_pchunks = C_cap;
-            h.desc.single_item_pairs = single ? 1 : 0;
-            h.desc.n_litems = lane_ok ? PD_LANE_MAX_ITEMS : 0;   // capacities again (the plan only asks whether the tables exist)
-            h.desc.n_lwaves = lane_ok ? PD_LANE_WAVES : 0;
-            h.desc.l_max_steps = A.LS_cap;
-            h.desc.n_frames = N;
-            h.desc.sc = A.sc;
-            h.desc.cx = A.cx;
-            h.desc.cy = A.cy;
-            h.max_item_len = single ? hint_per_pair : PD_ITEM_MAX_MATCHES;
-            // an upper bound (the host never learns the pair list): every pair in both orders, or one (PD_MATCH_HINT_ONE_ORDER; the tables
-            // kernel checks the degrees against it)
-            h.max_deg = std::min(P_cap, (one_order ? 1 : 2) * (N - 1));
-            h.device_built = true;
-        }
-        const size_t lds_hist = sizeof(int) * (size_t)N * N;
-        hipLaunchKernelGGL(ingest_hist_kernel, dim3(max_tiles, nb), dim3(256), lds_hist, s, A);
-        enqueued = true;
-        hipLaunchKernelGGL(ingest_tables_kernel, dim3(nb), dim3(ING_TABLE_THREADS), sl.lds_tab, s, A);
-        hipLaunchKernelGGL(ingest_scatter_kernel, dim3(max_tiles, nb), dim3(64), lds_hist, s, A);
-        if (A.LS_cap > 0) hipLaunchKernelGGL(ingest_lane_stream_kernel, dim3(PD_LANE_WAVES, nb), dim3(256), 0, s, A);
-        hipLaunchKernelGGL(ingest_interleave_kernel, dim3(I_cap, nb), dim3(64), 0, s, A);
-        if (hipGetLastError() != hipSuccess) {
-            pd_set_error("pd_ggs_set_matches_csr_async: a table kernel failed to launch");
-            return finish(PD_ERR_HIP);
-        }
-        b0 += nb;
+    if (enqueued && !capturing && pd_record_stream_event(eng->uploads, s) != PD_OK && rc == PD_OK) return PD_ERR_HIP;
+    return rc;
+}
+
+extern "C" int pd_ggs_set_matches_csr_async(pd_engine *eng, int seq_first, int n_seqs, const int64_t *seq_offsets,
+                                            const double *kp1, const double *kp2, const int64_t *i12, int n_frames, int height,
+                                            int width, const pd_match_hints *hints, void *stream) {
+    const char *who = "pd_ggs_set_matches_csr_async";
+    if (!eng || n_seqs <= 0 || seq_first < 0 || seq_first + n_seqs > eng->max_B || !seq_offsets || !kp1 || !kp2 || !i12) {
+        pd_set_error("pd_ggs_set_matches_csr_async: bad engine, slot range [%d, %d) or NULL pointer", seq_first, seq_first + n_seqs);
+        return PD_ERR_INVALID_ARG;
     }
-    return finish(PD_OK);
+    const int N = n_frames;
+    PD_TRY(pd_ggs_frames_unsupported(eng, N, who));
+    if (N > PD_MAX_FRAMES && N <= eng->max_N) {      // (PD_OPT_GGS_MAX_FRAMES above 64: this entry's kernels keep N^2 counters in LDS)
+        pd_set_error("pd_ggs_set_matches_csr_async: device-side ingestion is limited to %d frames (n_frames=%d); upload the matches of longer "
+                     "sequences with pd_ggs_set_matches", PD_MAX_FRAMES, N);
+        return PD_ERR_UNSUPPORTED;
+    }
+    if (N <= 0 || N > PD_MAX_FRAMES || N > eng->max_N || height <= 0 || width <= 0) {
+        pd_set_error("pd_ggs_set_matches_csr_async: invalid n_frames=%d (<= %d) or image size %dx%d", N, std::min(PD_MAX_FRAMES, eng->max_N),
+                     height, width);
+        return PD_ERR_INVALID_ARG;
+    }
+    PD_HIP_CHECK(hipSetDevice(eng->device));
+    IngestHints hn;
+    PD_TRY(read_hints(who, hints, hn));
+    // pass 1: validate every slice and size its capacities -- nothing is enqueued before the whole call is known to be launchable
+    std::vector<IngestSlice> slices;
+    for (int b0 = 0; b0 < n_seqs; b0 += ING_MAX_SEQS) {
+        IngestSlice sl{};
+        sl.N = N;
+        for (int b = b0; b < std::min(n_seqs, b0 + ING_MAX_SEQS); ++b) PD_TRY(add_item(who, sl, seq_first + b, seq_offsets, b));
+        PD_TRY(plan_slice(who, sl, hn));
+        slices.push_back(sl);
+    }
+    return run_slices(eng, who, slices, hn, kp1, kp2, i12, height, width, (hipStream_t)stream);
+}
+
+// One frame count per sequence.  Sequences of equal count form the launch groups (in order of first appearance, ING_MAX_SEQS at most each):
+// a group of <= PD_MAX_FRAMES frames runs the kernels of pd_ggs_set_matches_csr_async with its count as their N -- the same tables, and
+// frame indices checked against the sequence's own count --, a longer one the ingest_nf_* kernels.
+extern "C" int pd_ggs_set_matches_csr_async_nf(pd_engine *eng, int seq_first, int n_seqs, const int64_t *seq_offsets, const double *kp1,
+                                               const double *kp2, const int64_t *i12, const int *n_frames, int height, int width,
+                                               const pd_match_hints *hints, void *stream) {
+    const char *who = "pd_ggs_set_matches_csr_async_nf";
+    if (!eng || n_seqs <= 0 || seq_first < 0 || seq_first + n_seqs > eng->max_B || !seq_offsets || !kp1 || !kp2 || !i12 || !n_frames) {
+        pd_set_error("%s: bad engine, slot range [%d, %d) or NULL pointer", who, seq_first, seq_first + n_seqs);
+        return PD_ERR_INVALID_ARG;
+    }
+    bool any_long = false;
+    for (int b = 0; b < n_seqs; ++b) {
+        const int N = n_frames[b];
+        PD_TRY(pd_ggs_frames_unsupported(eng, N, who));
+        if (N <= 0 || N > eng->max_N || N > PD_GGS_LONG_MAX_FRAMES || height <= 0 || width <= 0) {
+            pd_set_error("%s: invalid n_frames[%d]=%d (1 .. %d) or image size %dx%d", who, b, N, std::min(eng->ggs_max_frames, eng->max_N), height,
+                         width);
+            return PD_ERR_INVALID_ARG;
+        }
+        any_long = any_long || N > PD_MAX_FRAMES;
+    }
+    IngestHints hn;
+    PD_TRY(read_hints(who, hints, hn));
+    if (any_long && (hn.per_pair < 1 || hn.per_pair > PD_ITEM_MAX_MATCHES)) {
+        // (the kernel for more than 64 frames takes one work item per frame pair, and the host never learns the counts)
+        pd_set_error("%s: a sequence of more than %d frames needs pd_match_hints.max_matches_per_pair in 1 .. %d (got %d)", who, PD_MAX_FRAMES,
+                     PD_ITEM_MAX_MATCHES, hn.per_pair);
+        return PD_ERR_UNSUPPORTED;
+    }
+    PD_HIP_CHECK(hipSetDevice(eng->device));
+    // pass 1: group, validate and size -- nothing is enqueued before the whole call is known to be launchable
+    std::vector<IngestSlice> slices;
+    for (int b = 0; b < n_seqs; ++b) {
+        IngestSlice *sl = nullptr;
+        for (IngestSlice &c : slices)
+            if (c.N == n_frames[b] && (int)c.items.size() < ING_MAX_SEQS) sl = &c;
+        if (!sl) {
+            slices.push_back(IngestSlice{});
+            sl = &slices.back();
+            sl->N = n_frames[b];
+            sl->nf = sl->N > PD_MAX_FRAMES;
+            sl->own_caps = true;
+        }
+        PD_TRY(add_item(who, *sl, seq_first + b, seq_offsets, b));
+    }
+    for (IngestSlice &sl : slices) PD_TRY(plan_slice(who, sl, hn));
+    return run_slices(eng, who, slices, hn, kp1, kp2, i12, height, width, (hipStream_t)stream);
 }
 
 int pd_ggs_ingest_init() {

@@ -249,7 +249,8 @@ class PoseEngine:
                                                    kp1.shape[0], n, h, w), "pd_ggs_set_matches")
 
     def set_matches_async(self, seq_first: int, kp1: torch.Tensor, kp2: torch.Tensor, i12: torch.Tensor, offsets,
-                          img_shape: Sequence[int], max_pairs: int = 0, max_matches_per_pair: int = 0, one_order: bool = False):
+                          img_shape: Sequence[int], max_pairs: int = 0, max_matches_per_pair: int = 0, one_order: bool = False,
+                          n_frames=None):
         """Asynchronous, device-resident upload of the matches of consecutive slots (pd_ggs_set_matches_csr_async).
 
         kp1 / kp2: float64 [total, 2], i12: int64 [total, 2] -- CUDA tensors on this device or PINNED host tensors (the
@@ -257,7 +258,11 @@ class PoseEngine:
         Runs on torch's current stream; returns at once.  The engine keeps the tensors alive until the upload has
         executed.  ``max_pairs`` / ``max_matches_per_pair``: capacity hints (include/pd_engine.h pd_match_hints); ``one_order``: every
         frame pair occurs in one order only (hloc's exhaustive i < j pairs: PD_MATCH_HINT_ONE_ORDER) -- with it the engine plans the same
-        launch shape as for host-uploaded tables."""
+        launch shape as for host-uploaded tables.
+
+        ``n_frames`` [n]: one frame count per sequence (pd_ggs_set_matches_csr_async_nf) -- a ragged batch in one call, and the way in
+        for sequences of 65 .. 256 frames (engines with ``ggs_max_frames`` raised; ``max_matches_per_pair`` in 1 .. 512 is then
+        required).  ``img_shape[0]`` must then only be >= every count.  Without it the call is the one frame count ``img_shape[0]``."""
         for name, t, dt in (("kp1", kp1, torch.float64), ("kp2", kp2, torch.float64), ("i12", i12, torch.int64)):
             if t.dtype != dt or t.dim() != 2 or t.shape[1] != 2 or not t.is_contiguous():
                 raise ValueError(f"{name} must be a contiguous {dt} tensor of shape [total, 2]")
@@ -272,10 +277,25 @@ class PoseEngine:
         cache = self.__dict__.setdefault("_match_ids", {})
         for b in range(len(off) - 1):
             cache.pop(int(seq_first) + b, None)                    # host.upload_matches' identity cache
+        counts = None
+        if n_frames is not None:
+            if isinstance(n_frames, torch.Tensor):
+                n_frames = n_frames.detach().cpu().tolist()
+            counts = [int(v) for v in n_frames]
+            if len(counts) != len(off) - 1:
+                raise ValueError(f"n_frames must hold one frame count per sequence ({len(off) - 1}), got {len(counts)}")
+            if counts and max(counts) > n:
+                raise ValueError(f"img_shape[0]={n} is below the largest frame count {max(counts)}")
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.pd_ggs_set_matches_csr_async(
-                self._h, int(seq_first), len(off) - 1, off.ctypes.data_as(C.POINTER(C.c_int64)), kp1.data_ptr(), kp2.data_ptr(),
-                i12.data_ptr(), n, h, w, C.byref(hints), self._stream()), "pd_ggs_set_matches_csr_async")
+            if counts is None:
+                _lib.check(self.lib.pd_ggs_set_matches_csr_async(
+                    self._h, int(seq_first), len(off) - 1, off.ctypes.data_as(C.POINTER(C.c_int64)), kp1.data_ptr(), kp2.data_ptr(),
+                    i12.data_ptr(), n, h, w, C.byref(hints), self._stream()), "pd_ggs_set_matches_csr_async")
+            else:
+                _lib.check(self.lib.pd_ggs_set_matches_csr_async_nf(
+                    self._h, int(seq_first), len(off) - 1, off.ctypes.data_as(C.POINTER(C.c_int64)), kp1.data_ptr(), kp2.data_ptr(),
+                    i12.data_ptr(), (C.c_int * max(len(counts), 1))(*counts), h, w, C.byref(hints), self._stream()),
+                    "pd_ggs_set_matches_csr_async_nf")
             ev = torch.cuda.Event()
             ev.record(torch.cuda.current_stream(self.device))
         keep = self.__dict__.setdefault("_upload_keep", [])

@@ -171,16 +171,21 @@ def has_matches(md) -> bool:
     return md is not None and md.get("kp1") is not None and len(md["kp1"]) > 0
 
 
-def upload_matches(engine: PoseEngine, matches, B: int, n_frames=None):
+def upload_matches(engine: PoseEngine, matches, B: int, n_frames=None, device_side: bool = False):
     """matches: one reference-style matches_dict (B == 1) or a list of B of them.  Uploads are cached per slot so
     the five calls per guided step upload once: a slot is skipped only when it still holds the SAME arrays (the cache
     keeps references, so their ids cannot be recycled) with the same content fingerprint.  Every sequence is uploaded with ITS
-    frame count, ``img_shape[0]``; ``n_frames`` [B] (the counts of a padded batch) must agree with it."""
+    frame count, ``img_shape[0]``; ``n_frames`` [B] (the counts of a padded batch) must agree with it.
+
+    ``device_side``: the slots that need an upload go up through ONE ragged device-side call per run of consecutive slots
+    (``pack_matches_ragged`` + ``PoseEngine.set_matches_async(..., n_frames=)``, ``max_matches_per_pair`` taken from the data) in
+    place of the synchronous host builder, which stays the default."""
     lst = list(matches) if isinstance(matches, (list, tuple)) else [matches]
     if len(lst) != B:
         raise ValueError(f"GGS needs one matches_dict per sequence: got {len(lst)} for B={B} "
                          "(the reference defines GGS only for B = 1, geometry_guided_sampling.py:16)")
     cache = engine.__dict__.setdefault("_match_ids", {})
+    todo = []
     for b, md in enumerate(lst):
         if not has_matches(md):
             raise ValueError(f"matches_dict of sequence {b} holds no matches (kp1 is None or empty); "
@@ -192,8 +197,26 @@ def upload_matches(engine: PoseEngine, matches, B: int, n_frames=None):
         ent = cache.get(b)
         if ent is not None and ent[0] is md["kp1"] and ent[1] is md["kp2"] and ent[2] is md["i12"] and ent[3] == fp:
             continue
+        if device_side:
+            todo.append((b, md, fp))
+            continue
         engine.set_matches(b, md["kp1"], md["kp2"], md["i12"], tuple(md["img_shape"]))
         cache[b] = (md["kp1"], md["kp2"], md["i12"], fp)
+    while todo:                                                    # runs of consecutive slots, one call each
+        run = [todo.pop(0)]
+        while todo and todo[0][0] == run[-1][0] + 1:
+            run.append(todo.pop(0))
+        kp1, kp2, i12, offsets, img_shape, counts = pack_matches_ragged([md for _, md, _ in run])
+        engine.set_matches_async(run[0][0], kp1, kp2, i12, offsets, img_shape, n_frames=counts,
+                                 max_matches_per_pair=max(_max_matches_per_pair(md) for _, md, _ in run))
+        for b, md, fp in run:                                      # (set_matches_async dropped the slots' entries)
+            cache[b] = (md["kp1"], md["kp2"], md["i12"], fp)
+
+
+def _max_matches_per_pair(md) -> int:
+    import numpy as np
+    i12 = np.asarray(md["i12"], dtype=np.int64)
+    return int(np.unique(i12[:, 0] * (int(i12.max()) + 1) + i12[:, 1], return_counts=True)[1].max())
 
 
 def pack_matches(matches_list, pin: bool = True):
@@ -216,3 +239,15 @@ def pack_matches(matches_list, pin: bool = True):
         kp2[a:e] = torch.from_numpy(np.ascontiguousarray(md["kp2"], dtype=np.float64))
         i12[a:e] = torch.from_numpy(np.ascontiguousarray(md["i12"], dtype=np.int64))
     return kp1, kp2, i12, offsets, shapes.pop()
+
+
+def pack_matches_ragged(matches_list, pin: bool = True):
+    """``pack_matches`` for sequences of DIFFERENT frame counts (one image size): -> (kp1, kp2, i12, offsets, img_shape, counts) for
+    ``PoseEngine.set_matches_async(..., n_frames=counts)``.  ``img_shape`` carries the largest count, ``counts`` [n] every sequence's own."""
+    sizes = {tuple(int(v) for v in md["img_shape"][1:]) for md in matches_list}
+    if len(sizes) != 1:
+        raise ValueError(f"all sequences of a batch must share the image size (img_shape[1:]): {sorted(sizes)}")
+    counts = [int(md["img_shape"][0]) for md in matches_list]
+    same = [dict(md, img_shape=(max(counts), *next(iter(sizes)))) for md in matches_list]
+    kp1, kp2, i12, offsets, img_shape = pack_matches(same, pin=pin)
+    return kp1, kp2, i12, offsets, img_shape, counts
