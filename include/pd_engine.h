@@ -133,7 +133,8 @@ typedef struct pd_ggs_cfg {
 #define PD_GGS_CFG_LONG_FRAMES 64     /* pd_ggs_cfg.reserved: run the kernel for sequences of more than 64 frames (pd_ggs_long_kernel: the two-hop
                                        * scheme with frame tables for 256 frames, one thread per frame in the update phase) at any N; at
                                        * N <= 64 bitwise the two-hop kernel's results -- comparison / testing.  Its requirements are those
-                                       * listed under PD_OPT_GGS_MAX_FRAMES */
+                                       * listed under PD_OPT_GGS_MAX_FRAMES; with PD_OPT_GGS_LONG_PAIR_ITEMS on, tables that hold a frame pair
+                                       * of more than 512 matches run pd_ggs_longm_kernel here as they do above 64 frames */
 
 /* ---- lifecycle -------------------------------------------------------------------------- */
 
@@ -216,7 +217,7 @@ int pd_p_losses(pd_engine *eng, const float *x_start, const float *z, const int6
  *             of pairs in every slot.  Where the plan refuses a mix the call returns the plan's PD_ERR_UNSUPPORTED and the engine stays
  *             usable: GROUPING SEQUENCES INTO LAUNCHES THE PLAN ACCEPTS IS THE CALLER'S JOB.  The GGS frame limit (64, or PD_OPT_GGS_MAX_FRAMES)
  *             applies to N and the 256-frame denoiser limit is unchanged.  With the option raised, a launch in which any slot's count
- *             exceeds 64 runs pd_ggs_long_kernel for ALL its slots; that kernel does not need several chunks of pairs in a slot, so short
+ *             exceeds 64 runs pd_ggs_long_kernel (pd_ggs_longm_kernel where PD_OPT_GGS_LONG_PAIR_ITEMS admits a pair of several work items) for ALL its slots; that kernel does not need several chunks of pairs in a slot, so short
  *             sequences with few pairs share such a launch.
  *   graphs    "counts are set" is part of the key of a captured loop, the counts are not: a loop replayed after another
  *             pd_engine_set_frame_counts with the same B uses the new counts.
@@ -260,7 +261,8 @@ int pd_ggs_set_matches(pd_engine *eng, int seq, const double *kp1, const double 
                                             * for device-built ones too; checked on the device like every hint */
 typedef struct pd_match_hints {
     int32_t max_pairs;               /* 0 = unknown; else an upper bound on the frame pairs that own matches (| PD_MATCH_HINT_ONE_ORDER) */
-    int32_t max_matches_per_pair;    /* 0 = unknown; else an upper bound on the matches of one frame pair               */
+    int32_t max_matches_per_pair;    /* 0 = unknown; else an upper bound on the matches of one frame pair (above 64 frames: 1 .. 512
+                                      * unless PD_OPT_GGS_LONG_PAIR_ITEMS is on, pd_engine_ingest.h) */
 } pd_match_hints;
 int pd_ggs_set_matches_csr_async(pd_engine *eng, int seq_first, int n_seqs, const int64_t *seq_offsets, const double *kp1,
                                  const double *kp2, const int64_t *i12, int n_frames, int height, int width,
@@ -335,12 +337,23 @@ int pd_ggs_loss_grad(pd_engine *eng, const float *x, int B, int N, int update_R,
  *        (2 v^2 + 512) lines of 128 bytes per sequence slot and epoch (v = 256: 33.7 MB per slot; 64: 2.2 MB) and drops the cached
  *        hipGraphs.  If that allocation fails it returns PD_ERR_HIP and the previous limit and region stay in force; any other value
  *        returns PD_ERR_INVALID_ARG.  A launch above 64 frames needs, and is refused with PD_ERR_UNSUPPORTED naming the number otherwise:
- *        every frame pair <= 512 matches; 2 <= workgroups per sequence <= 256 (so B <= CUs / 2; wgs_per_seq = 1 is refused); the item
+ *        every frame pair <= 512 matches (any number with PD_OPT_GGS_LONG_PAIR_ITEMS, below); 2 <= workgroups per sequence <= 256 (so B <= CUs / 2; wgs_per_seq = 1 is refused); the item
  *        slots of a workgroup, ceil(pairs / (8 wgs)) x 8, within its LDS image (<= 208); 2 pairs + wgs + N exchange lines within the
  *        region.  Matches of such sequences are uploaded with pd_ggs_set_matches or, on the device, with
  *        pd_ggs_set_matches_csr_async_nf (pd_engine_ingest.h); pd_ggs_set_matches_csr_async itself stays limited to 64 frames (PD_ERR_UNSUPPORTED above).
  *        Every launch at N <= 64 is what it is without the option. */
 #define PD_OPT_GGS_MAX_FRAMES 7
+/*   PD_OPT_GGS_LONG_PAIR_ITEMS  0 (default): above 64 frames a frame pair holds at most 512 matches (one work item; a launch over tables
+ *        with a longer pair, and pd_ggs_set_matches_csr_async_nf without a hint of 1 .. 512, return PD_ERR_UNSUPPORTED).  1: any number of
+ *        matches per frame pair, as geometry_guided_sampling takes them.  A launch above 64 frames (or with PD_GGS_CFG_LONG_FRAMES) in which
+ *        some slot's tables are not one work item per pair runs pd_ggs_longm_kernel for all its slots: pd_ggs_long_kernel's scheme with one
+ *        slot per frame PAIR, whose wave adds the sums of the pair's work items (the balanced cuts of <= 512 matches both table builders
+ *        make) in item order.  Gradient, valid count, poses and iterations do not depend on the workgroup count, and a pair of <= 512
+ *        matches gets bitwise what pd_ggs_long_kernel gives it.  The launch is sized by frame pairs: the limits listed under
+ *        PD_OPT_GGS_MAX_FRAMES hold with "pairs" read as frame pairs.  Launches whose slots are all one item per pair stay on
+ *        pd_ggs_long_kernel.  Setting the option allocates nothing and does not synchronise; tables uploaded before stay valid (the item
+ *        tables are always built); any other value returns PD_ERR_INVALID_ARG. */
+#define PD_OPT_GGS_LONG_PAIR_ITEMS 8
 int pd_engine_set_option(pd_engine *eng, int option, int value);
 /* Reads an option back.  PD_OPT_DENOISER_SPLIT: the mode in force (an engine created from weights that hold inf / NaN stays on 0 although
  * it is large enough for 2 -- the only downgrade pd_engine_create performs by itself; PD_OPT_WEIGHTS_NON_FINITE (read-only) then reads 1). */
@@ -516,7 +529,7 @@ int pd_check_async_error(pd_engine *eng);
  * read them: {P1 pair F, P2 matches, exchange, P3 backward, P4 update, iterations} of workgroup 0. */
 int pd_debug_ggs_prof(pd_engine *eng, int enable, long long *out6);   /* enable = 1 + wave index to record; out6 holds 16 values */
 /* The launch shape pd_ggs_guide / pd_sample would use for (B, N, cfg) with the matches uploaded now:
- * out8 = {workgroups per sequence, item slots per workgroup, LDS bytes, two-hop kernel, waves per workgroup, LDS-DMA staging pieces,
+ * out8 = {workgroups per sequence, item slots per workgroup, LDS bytes, two-hop kernel (2: pd_ggs_long_kernel, 3: pd_ggs_longm_kernel), waves per workgroup, LDS-DMA staging pieces,
  * lane-per-item kernel, its LDS-resident steps}.  Lets a test pin which kernel the engine picks by itself. */
 int pd_debug_ggs_plan(pd_engine *eng, int B, int N, const pd_ggs_cfg *cfg, int *out8);
 /* The lane-per-item tables of match slot `seq` as the device holds them (host- or device-built): out[0..3] = {lane items, waves, base item length in

@@ -23,7 +23,9 @@ extern "C" {
  *     pair_item_off, items, gpos, ginc_off; no chunk tables, no lane tables, no limit on the chunks of pairs) from a stable two-pass
  *     sort by (j, then i) whose scratch is O(M + n_frames^2).  pd_ggs_long_kernel takes one work item per frame pair and the host
  *     never learns the counts, so a call that holds a count above 64 needs hints->max_matches_per_pair in 1 .. 512
- *     (PD_ERR_UNSUPPORTED naming the hint otherwise).
+ *     (PD_ERR_UNSUPPORTED naming the hint otherwise).  With the engine option PD_OPT_GGS_LONG_PAIR_ITEMS on, such a call also takes 0
+ *     (unknown) or a value above 512: the slot's capacities are then P_cap + M / 512 + 1 work items and a host shadow that is not one
+ *     item per pair, so its launches run pd_ggs_longm_kernel; a positive hint is still enforced on the device.
  * A frame index is checked against the sequence's OWN count: an index outside it, or a violated hint, empties THAT slot and raises
  * the asynchronous error word (bits 1 / 2); the other slots of the call are built.  Every count lies in
  * [1, min(max_N, PD_OPT_GGS_MAX_FRAMES)]: above the GGS limit in force PD_ERR_UNSUPPORTED (naming the limit), otherwise -- or with

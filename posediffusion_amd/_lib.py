@@ -67,6 +67,7 @@ PD_OPT_WEIGHTS_NON_FINITE = 4   # pd_engine_get_option only
 PD_OPT_DENOISER_FUSED_ATTN = 5  # in_proj + attention as one kernel, Q / K / V in LDS (default 1)
 PD_OPT_DENOISER_LONG_ATTN = 6   # 1: the key-tiled attention kernel of sequences above 64 frames for every N (default 0; comparison / testing)
 PD_OPT_GGS_MAX_FRAMES = 7       # frames GGS admits: 64 (default) or a value in (64, max_N]; reallocates the exchange region, synchronous
+PD_OPT_GGS_LONG_PAIR_ITEMS = 8  # 0 (default) / 1: above 64 frames a frame pair may hold more than 512 matches (pd_ggs_longm_kernel)
 PD_MATCH_HINT_ONE_ORDER = 1 << 30   # pd_match_hints.max_pairs flag: every frame pair in one order only (hloc's i < j pairs)
 
 

@@ -795,6 +795,13 @@ extern "C" int pd_engine_set_option(pd_engine *eng, int option, int value) {
         eng->ggs_max_frames = value;
         break;
     }
+    case PD_OPT_GGS_LONG_PAIR_ITEMS:      // (no allocation, no synchronisation: the plan reads it, and the plan is part of every graph key)
+        if (value < 0 || value > 1) {
+            pd_set_error("pd_engine_set_option: PD_OPT_GGS_LONG_PAIR_ITEMS takes 0 or 1 (got %d)", value);
+            return PD_ERR_INVALID_ARG;
+        }
+        eng->ggs_long_pair_items = value;
+        break;
     case 3:      // (PD_OPT_DENOISER_PERSISTENT of round 3: the persistent small-batch kernel was measured 2.4 x slower and parked, tools/parked/)
         if (value == 0) break;
         pd_set_error("pd_engine_set_option: option 3 (the persistent small-batch denoiser launch of round 3) is no longer built: it measured "
@@ -817,6 +824,7 @@ extern "C" int pd_engine_get_option(pd_engine *eng, int option, int *value_out) 
     case PD_OPT_DENOISER_FUSED_ATTN: *value_out = eng->den_fused_attn; break;
     case PD_OPT_DENOISER_LONG_ATTN: *value_out = eng->den_long_attn; break;
     case PD_OPT_GGS_MAX_FRAMES: *value_out = eng->ggs_max_frames; break;
+    case PD_OPT_GGS_LONG_PAIR_ITEMS: *value_out = eng->ggs_long_pair_items; break;
     case PD_OPT_WEIGHTS_NON_FINITE: *value_out = pd_denoiser_weights_non_finite(eng) ? 1 : 0; break;
     default:
         pd_set_error("pd_engine_get_option: unknown option %d", option);
@@ -957,7 +965,7 @@ extern "C" int pd_debug_ggs_plan(pd_engine *eng, int B, int N, const pd_ggs_cfg 
     PdGgsPlan plan;
     int rc = pd_ggs_plan(eng, B, N, cfg, &plan);
     if (rc) return rc;
-    const int v[8] = {plan.k, plan.n_slots, plan.lds, plan.long_frames ? 2 : plan.two_hop, plan.waves, plan.stage_p, plan.lane, plan.lane_rl};
+    const int v[8] = {plan.k, plan.n_slots, plan.lds, plan.long_frames ? 1 + plan.long_frames : plan.two_hop, plan.waves, plan.stage_p, plan.lane, plan.lane_rl};
     for (int i = 0; i < 8; ++i) out8[i] = v[i];
     return PD_OK;
 }

@@ -31,7 +31,7 @@
 // switches below govern all of their code -- and the host code bound to them: pd_ggs_init, pd_ggs_plan, pd_ggs_launch.  The device code
 // itself is in the headers included below: pd_ggs_lds.h (the LDS images and their sizes), pd_ggs_dev.h (cross-lane sums, pair geometry, pose
 // decode), pd_ggs_sampson.h (the match pass), pd_ggs_kernels.h (pd_ggs_kernel, pd_ggs2_kernel), pd_ggs_lane.inc (pd_ggs_lane_kernel), and the
-// statement fragments those include (pd_ggs_pairbwd.inc, pd_ggs_p3b.inc, pd_ggs_p4.inc, pd_ggs_p4_long.inc, pd_ggs_p4q.inc).  The match tables the kernels read are
+// statement fragments those include (pd_ggs_pairbwd.inc, pd_ggs_p3b.inc, pd_ggs_p4.inc, pd_ggs_p4_long.inc, pd_ggs_long_hop2.inc, pd_ggs_p4q.inc).  The match tables the kernels read are
 // built elsewhere: on the host by pd_ggs_tables.hip (pd_ggs_set_matches), on the device by pd_ggs_ingest.hip; the stream events that order
 // uploads against launches belong to pd_engine.hip.
 #include "pd_internal.h"
@@ -63,7 +63,7 @@
 #include "pd_ggs_lds.h"        // the two LDS images: struct Lds, carve / carve_lane and the byte counts derived from them
 #include "pd_ggs_dev.h"        // cross-lane sums, pair geometry, pose decode, quaternion Jacobian
 #include "pd_ggs_sampson.h"    // the match pass: Sampson steps, item passes, LDS-DMA staging
-#include "pd_ggs_kernels.h"    // pd_ggs_kernel, pd_ggs2_kernel, pd_ggs_long_kernel, pd_ggs_zero_kernel
+#include "pd_ggs_kernels.h"    // pd_ggs_kernel, pd_ggs2_kernel, pd_ggs_long_kernel, pd_ggs_longm_kernel, pd_ggs_zero_kernel
 #include "pd_ggs_lane.inc"     // pd_ggs_lane_kernel
 
 // --------------------------------------------------------------------------------------------
@@ -99,6 +99,7 @@ int pd_ggs_init() {
                     PD_HIP_CHECK(hipFuncSetAttribute((const void *)f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     PD_HIP_CHECK(hipFuncSetAttribute((const void *)pd_ggs2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     PD_HIP_CHECK(hipFuncSetAttribute((const void *)pd_ggs_long_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    PD_HIP_CHECK(hipFuncSetAttribute((const void *)pd_ggs_longm_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     PD_HIP_CHECK(hipFuncSetAttribute((const void *)pd_ggs_lane_kernel<PD_LANE_RV>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     if (!lane_pinc_aligned()) {
         pd_set_error("pd_ggs: the lane kernel's LDS image puts its float4 rows off a 16-byte boundary");
@@ -289,10 +290,19 @@ static int plan_wave_items(const pd_engine *eng, int B, int N, const pd_ggs_cfg 
     return PD_OK;
 }
 
-// pd_ggs_plan, part 4: pd_ggs_long_kernel -- more than PD_MAX_FRAMES frames in the launch (or in one of its slots, with frame counts per
+// pd_ggs_plan, part 4: pd_ggs_long_kernel / pd_ggs_longm_kernel -- more than PD_MAX_FRAMES frames in the launch (or in one of its slots, with frame counts per
 // sequence), or PD_GGS_CFG_LONG_FRAMES.  One shape, no fall-back: what it needs and does not find is refused, naming the number.
 static int plan_long(const pd_engine *eng, int B, int N, const pd_ggs_cfg *cfg, int device_cus, int max_items, PdGgsPlan *out) {
-    for (int b = 0; b < B; ++b)
+    // PD_OPT_GGS_LONG_PAIR_ITEMS and a slot whose pairs are not all one work item: pd_ggs_longm_kernel for the whole launch -- a slot is a
+    // frame PAIR there, so the shape below is sized by the most pairs of a slot (== max_items wherever every pair is one item)
+    bool multi = false;
+    for (int b = 0; b < B; ++b) multi = multi || !eng->seqs[b].desc.single_item_pairs;
+    multi = multi && eng->ggs_long_pair_items;
+    if (multi) {
+        max_items = 0;
+        for (int b = 0; b < B; ++b) max_items = std::max(max_items, eng->seqs[b].desc.n_pairs);
+    }
+    for (int b = 0; b < B && !multi; ++b)
         if (!eng->seqs[b].desc.single_item_pairs) {
             pd_set_error("pd_ggs: slot %d holds a frame pair of more than %d matches (its longest work item has %d after the cut): the kernel for "
                          "more than %d frames takes at most %d matches per frame pair", b, PD_ITEM_MAX_MATCHES, eng->seqs[b].max_item_len,
@@ -328,7 +338,7 @@ static int plan_long(const pd_engine *eng, int B, int N, const pd_ggs_cfg *cfg, 
         }
     }
     (void)N;
-    out->long_frames = 1;
+    out->long_frames = multi ? 2 : 1;
     out->k = k;
     out->waves = PD_GGS_WAVES;
     out->n_slots = n_slots;
@@ -417,7 +427,9 @@ int pd_ggs_launch(pd_engine *eng, float *x, int B, int N, const PdGgsStage *stag
     }
     const size_t lds = (size_t)plan.lds;
     const int B_map = plan.xchg_local ? ((B + 7) & ~7) : B;     // the kernels' block -> (sequence, workgroup) mapping
-    if (plan.long_frames)
+    if (plan.long_frames == 2)
+        hipLaunchKernelGGL(pd_ggs_longm_kernel, dim3(B * plan.k), dim3(PD_GGS_THREADS), lds, s, P, B, plan.n_slots, plan.pinc_rows / 2);
+    else if (plan.long_frames)
         hipLaunchKernelGGL(pd_ggs_long_kernel, dim3(B * plan.k), dim3(PD_GGS_THREADS), lds, s, P, B, plan.n_slots, plan.pinc_rows / 2);
     else if (plan.lane)
         hipLaunchKernelGGL(pd_ggs_lane_kernel<PD_LANE_RV>, dim3(B), dim3(PD_LANE_THREADS), lds, s, P, plan.pinc_rows);

@@ -864,7 +864,7 @@ static int plan_slice(const char *who, IngestSlice &sl, const IngestHints &h) {
     sl.C_cap = (sl.P_cap + PD_GGS_THREADS - 1) / PD_GGS_THREADS;
     sl.LS_cap = 0;
     sl.lds_tab = 0;
-    if (sl.nf) return PD_OK;     // (only pd_ggs_long_kernel runs there: no chunk tables, no lane tables, every table kernel's LDS is static)
+    if (sl.nf) return PD_OK;     // (only pd_ggs_long_kernel / pd_ggs_longm_kernel run there: no chunk tables, no lane tables, every table kernel's LDS is static)
     if (sl.C_cap > PD_GGS_MAX_PCHUNKS) {
         pd_set_error("%s: up to %d frame pairs (max %d): pass pd_match_hints.max_pairs", who, sl.P_cap, PD_GGS_MAX_PCHUNKS * PD_GGS_THREADS);
         return PD_ERR_UNSUPPORTED;
@@ -1074,8 +1074,9 @@ extern "C" int pd_ggs_set_matches_csr_async_nf(pd_engine *eng, int seq_first, in
     }
     IngestHints hn;
     PD_TRY(read_hints(who, hints, hn));
-    if (any_long && (hn.per_pair < 1 || hn.per_pair > PD_ITEM_MAX_MATCHES)) {
-        // (the kernel for more than 64 frames takes one work item per frame pair, and the host never learns the counts)
+    if (any_long && !eng->ggs_long_pair_items && (hn.per_pair < 1 || hn.per_pair > PD_ITEM_MAX_MATCHES)) {
+        // (pd_ggs_long_kernel takes one work item per frame pair, and the host never learns the counts.  PD_OPT_GGS_LONG_PAIR_ITEMS: no or
+        // a larger hint gives plan_slice's capacities for several items per pair and a host shadow pd_ggs_plan sends to pd_ggs_longm_kernel)
         pd_set_error("%s: a sequence of more than %d frames needs pd_match_hints.max_matches_per_pair in 1 .. %d (got %d)", who, PD_MAX_FRAMES,
                      PD_ITEM_MAX_MATCHES, hn.per_pair);
         return PD_ERR_UNSUPPORTED;

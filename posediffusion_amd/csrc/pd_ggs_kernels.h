@@ -1,6 +1,6 @@
 // pd_ggs_kernels.h -- the wave-per-item GGS kernels: pd_ggs_kernel (one exchange hop per iteration; every workgroup of a sequence runs the whole
 // backward), pd_ggs2_kernel (two hops, the backward distributed: many frames) and pd_ggs_zero_kernel (clears the exchange granules before a launch).
-// The lane-per-item kernel is pd_ggs_lane.inc.  Statement fragments shared by the kernels: pd_ggs_pairbwd.inc, pd_ggs_p3b.inc, pd_ggs_p4.inc, pd_ggs_p4_long.inc, pd_ggs_p4q.inc.
+// The lane-per-item kernel is pd_ggs_lane.inc.  Statement fragments shared by the kernels: pd_ggs_pairbwd.inc, pd_ggs_p3b.inc, pd_ggs_p4.inc, pd_ggs_p4_long.inc, pd_ggs_long_hop2.inc, pd_ggs_p4q.inc.
 // Textually part of pd_ggs.hip, which holds the development switches read here (PD_GGS_PROF12, PD_GGS_ABLATE, PD_GGS_MIN_WAVES_PER_SIMD, PD_GGS_PROF2).
 #pragma once
 #include "pd_ggs_sampson.h"
@@ -1079,69 +1079,242 @@ __global__ __launch_bounds__(PD_GGS_THREADS) void pd_ggs_long_kernel(PdGgsParams
                 }
             }
             PD_PROF2H(q3);
-            // ---- P3b: the owner of frame n sums that frame's rows in row order and publishes the frame line
-            bool ok = true;
-            for (int n = wg; n < N; n += k) {
-                const int lo = L.incoff[n], cn = L.incoff[n + 1] - lo;   // <= 2 (N - 1) <= 510 rows: PD_GGS_LONG_FRAME_ROWS
-                ok = ggs2_gather<1>(xs + (size_t)lo * PD_XCHG_LINE, tid, cn * 8, 8, epoch, frame_rows, 16, P.err_flag) && ok;
-                __syncthreads();
-                if (tid < 64) {
-                    // the frame's rows summed in a FIXED order that does not depend on the workgroup count: the four 16-lane rows of wave 0 each sum
-                    // every fourth row (rows p, p + 4, ...: eight LDS reads in flight at a time), then (p0 + p1) + (p2 + p3) on the permlane swaps.
-                    // History (tools/ggs_prof_n50.py, round 5): a plain loop over the rows was a chain of <= 63 dependent LDS round trips -- 5 700 of the
-                    // 22 100 cycles of an iteration at 50 frames; eight reads in flight on 16 lanes: 3 300; this form: see profiles/round5_ggs_n50_phase_clocks.txt
-                    const int c16 = tid & 15, part = tid >> 4;
-                    float a = 0.0f;
-                    for (int e0 = part; e0 < cn; e0 += 32) {              // (cn <= 2 (N - 1) rows; the loop bound differs between the four parts: no cross-lane operation inside)
-                        float r[8];
+#include "pd_ggs_long_hop2.inc"
+#include "pd_ggs_p4_long.inc"
+            __syncthreads();
+            PD_PROF2H(q7);
+            if (L.ctl[0] != 0.0f) break;
+        }
+        if (tid == 0 && wg == 0 && P.stats) {
+            float *so = P.stats + ((size_t)b * P.n_stages + st) * 4;
+            so[0] = last_print;
+            so[1] = (float)stepped;
+            so[2] = last_cnt;
+            so[3] = last_loss;
+        }
+        if (P.eval_only) break;
+    }
+    if (prof2 && lane == 0) {
+        long long *o = P.prof + (wg == 0 ? 0 : 8);
+        o[0] = q0; o[1] = q1; o[2] = q2; o[3] = q3; o[4] = q4; o[5] = q5; o[6] = q6; o[7] = q7;
+    }
+#undef PD_PROF2H
+    if (own && wg == 0 && !P.eval_only) {
 #pragma unroll
-                        for (int u = 0; u < 8; ++u) r[u] = e0 + 4 * u < cn ? frame_rows[(e0 + 4 * u) * 16 + c16] : 0.0f;
+        for (int c = 0; c < 9; ++c) xg[tid * 9 + c] = L.xst[tid * PD_XS_STRIDE + c];
+    }
+}
+
+// pd_ggs_long_kernel with a slot = a frame PAIR instead of a work item (PD_OPT_GGS_LONG_PAIR_ITEMS): for launches in which some pair holds more
+// than PD_ITEM_MAX_MATCHES matches.  Slot s of workgroup wg owns pair wg * 8 + (s & 7) + (s >> 3) * nW; the wave that owns the slot runs the
+// match pass once per work item of the pair (the balanced cuts both table builders write: items[pair_item_off[p] ..]), in item order, and
+// adds the twelve item totals.  One wave forms a pair's sums in a fixed order, so -- as in pd_ggs_long_kernel -- nothing the update reads
+// depends on the workgroup count or the slot batches; a pair of one item goes through that kernel's very operations (same bits).  Everything
+// outside the slot table, the resident matches and P2 is that kernel's text.
+__global__ __launch_bounds__(PD_GGS_THREADS) void pd_ggs_longm_kernel(PdGgsParams P, int B, int n_slots, int n_batch) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int b = blockIdx.x % B, wg = blockIdx.x / B;
+    if (b >= P.n_seqs) return;
+    const PdSeqDesc D = P.seqs[b];
+    const int N = D.n_frames, k = P.k;   // this sequence's own frame count (pd_ggs_plan checked it: P.N, or its entry of pd_engine_set_frame_counts); rows of x stay P.N apart
+    const int nW = k * PD_GGS_WAVES;
+    const int n_pairs = D.n_pairs;          // a slot is a PAIR here; its items are D.items[pair_item_off[p] .. pair_item_off[p + 1])
+    const int n_inc = 2 * D.n_pairs;
+    const LdsLong L = carve_long(smem, n_slots, n_batch);
+    float *xg = P.x + (size_t)b * P.N * PD_POSE_DIM;
+    u64 *xbase = P.xchg + (size_t)b * 2 * P.xchg_stride;
+    // the hop windows of the image (carve_long): L.item the item sums of a batch of this workgroup's slots [n_batch][12]; own_rows the results
+    // of its pairs [2 n_batch][16]; frame_rows the gathered rows of an owned frame (<= 2 (N - 1) <= 510); tot_rows the gathered totals [k <= 256][4];
+    // grow the exchange row of each local (pair, side); L.psum the gathered frame sums [N][16]
+    float *own_rows = L.own_rows;
+    float *frame_rows = L.frame_rows;
+    float *tot_rows = L.tot_rows;
+    int *grow = L.grow;
+
+    // thread tid < 256 (waves 0 .. 3) owns frame tid: parameters + momentum live in LDS (L.xst / L.mst) and visit registers only inside P4
+    const bool own = tid < N;
+    if (tid < PD_GGS_LONG_FRAMES) {
 #pragma unroll
-                        for (int u = 0; u < 8; ++u) a += r[u];
+        for (int c = 0; c < 9; ++c) {
+            L.xst[tid * PD_XS_STRIDE + c] = own ? xg[tid * 9 + c] : 0.0f;
+            L.mst[tid * PD_XS_STRIDE + c] = 0.0f;
+        }
+    }
+    for (int s = tid; s < n_slots; s += PD_GGS_THREADS) {
+        const int p = wg * PD_GGS_WAVES + (s & 7) + (s >> 3) * nW;
+        int4 e = make_int4(0, 0, 0, 0);        // (first item, items, i, j): .y > 0 marks an active slot, as the item's match count does in pd_ggs_long_kernel
+        int2 gp = make_int2(0, 0);
+        if (p < n_pairs) {
+            const int first = D.pair_item_off[p];
+            const int2 ij = D.pair_ij[p];
+            e = make_int4(first, D.pair_item_off[p + 1] - first, ij.x, ij.y);
+            gp = D.gpos[p];
+        }
+        L.itab[s] = e;
+        grow[2 * s] = gp.x;
+        grow[2 * s + 1] = gp.y;
+    }
+    for (int q = tid; q <= N; q += PD_GGS_THREADS) L.incoff[q] = D.ginc_off[q];
+    if (tid == 0) {
+        L.ctl[0] = 0.0f;
+        L.ctl[1] = 0.0f;
+    }
+    {
+        float xr0[9];
+#pragma unroll
+        for (int c = 0; c < 9; ++c) xr0[c] = 0.0f;
+        if (tid < PD_GGS_LONG_FRAMES) params_load(L.xst, tid, xr0);
+        decode_all_long(L, xr0, tid, N, D);
+    }
+    __syncthreads();
+    // one pair per wave (the usual case here: k = ceil(pairs / 8)) and that pair ONE item: its matches stay in registers for the whole launch
+    // (wave-uniform); a pair of several items streams every item from memory
+    const int4 it_res = L.itab[wave].y == 1 ? D.items[L.itab[wave].x] : make_int4(0, 0, 0, 0);     // (pair, first match, matches, 0)
+    const bool resident = (n_slots == PD_GGS_WAVES) && it_res.z > 0;
+    float4 mres[8];
+    {
+        const int last = it_res.z > 0 ? it_res.z - 1 : 0;
+        const float4 *pts = D.pts + it_res.y;
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            const int m = lane + 64 * q;
+            mres[q] = resident ? pts[m < it_res.z ? m : last] : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+    }
+    unsigned epoch = 0;
+    int trace_row = 0;
+    const float inv_M = 1.0f / (float)D.M;
+    // phase clocks (pd_debug_ggs_prof; round 5): wave 0 of workgroup 0 (owner of frame 0) -> prof[0..7], of the last workgroup (owns no frame when
+    // k > N) -> prof[8..15]: {P1, P2, P3a, hop-1 publish + totals, P3b owner loop, hop-2 gathers, frame gradients + totals, P4}, shader cycles
+    const bool prof2 = P.prof != nullptr && b == 0 && wave == 0 && (wg == 0 || wg == k - 1);
+    long long q0 = 0, q1 = 0, q2 = 0, q3 = 0, q4 = 0, q5 = 0, q6 = 0, q7 = 0, qc = 0;
+#define PD_PROF2H(acc) do { if (prof2) { const long long n_ = __builtin_amdgcn_s_memtime(); acc += n_ - qc; qc = n_; } } while (0)
+    for (int st = 0; st < P.n_stages; ++st) {
+        const PdGgsStage S = P.stages[st];
+        int stepped = 0;
+        float last_print = __int_as_float(0x7fc00000), last_cnt = 0.0f, last_loss = __int_as_float(0x7fc00000);
+        const bool need_rt = S.update_R || S.update_T;
+        for (int it = 0; it < S.iters; ++it) {
+            if (prof2) qc = __builtin_amdgcn_s_memtime();
+            // P1 .. hop 1 run over the workgroup's slots in batches of n_batch (pd_ggs_plan: all of them in one batch where the image has the
+            // room; a multiple of 64 otherwise): F, the item sums and the own rows live in LDS for one batch at a time, indexed by the slot's
+            // position in its batch.  Nothing a pair computes depends on its batch, and the lanes of the totals wave keep their slots
+            // (s % 64) across batches: the results are those of one batch.
+            const Cam cam = {L.cam[0], L.cam[1], L.cam[2], L.cam[3]};
+            ++epoch;
+            u64 *xs = xbase + (size_t)(epoch & 1) * P.xchg_stride;
+            float t0 = 0.0f, t1 = 0.0f, t2 = 0.0f;      // (totals wave) this workgroup's loss totals, per lane until the last batch is in
+            for (int s0 = 0; s0 < n_slots; s0 += n_batch) {
+                const int nb = min(n_batch, n_slots - s0);
+                // ---- P1: F for this workgroup's pairs
+                for (int sl = tid; sl < nb; sl += PD_GGS_THREADS) {
+                    const int4 e = L.itab[s0 + sl];
+                    if (e.y > 0) {
+                        float Ri[9], Rj[9], ti[3], tj[3];
+                        frame_load(L, e.z, Ri, ti);
+                        frame_load(L, e.w, Rj, tj);
+                        PairFwd f;
+                        pair_forward(Ri, ti, Rj, tj, f);
+                        float F[9];
+                        fundamental_from_E(f.E, cam, F);
+#pragma unroll
+                        for (int c = 0; c < 9; ++c) L.F[sl * PD_F_STRIDE + c] = F[c];
                     }
-                    a = add_xor16(a);
-                    a = add_xor32(a);
-                    if (tid < 16)
-                        __hip_atomic_store(xs + (size_t)(n_inc + k + n) * PD_XCHG_LINE + tid, ((u64)epoch << 32) | (u64)__float_as_uint(a),
-                                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 }
                 __syncthreads();
+                PD_PROF2H(q0);
+                // ---- P2: per-match Sampson residual + dL/dF, a wave per PAIR: the pair's items in ascending order, each the pass and the totals
+                // of pd_ggs_long_kernel (the exact-threshold re-run stays per item); the 12 values are added on the lanes that hold them -- item
+                // 0's as they are, so a pair of one item gets that kernel's bits -- and only the sums reach this workgroup's LDS
+                for (int r = 0; r * PD_GGS_WAVES < nb; ++r) {
+                    const int sl = wave + PD_GGS_WAVES * r;
+                    const int4 e = L.itab[s0 + sl];
+                    if (e.y > 0) {
+                        float Fm[9];
+                        {   // three LDS reads (slot stride 12 floats, 16-byte aligned) instead of nine 4-byte ones
+                            const float4 f0 = *(const float4 *)(L.F + sl * PD_F_STRIDE), f1 = *(const float4 *)(L.F + sl * PD_F_STRIDE + 4);
+                            Fm[0] = f0.x; Fm[1] = f0.y; Fm[2] = f0.z; Fm[3] = f0.w;
+                            Fm[4] = f1.x; Fm[5] = f1.y; Fm[6] = f1.z; Fm[7] = f1.w;
+                            Fm[8] = L.F[sl * PD_F_STRIDE + 8];
+                        }
+                        int slot = PD_ITEM_VALS;
+                        float sum = 0.0f;
+                        if (resident) {
+                            v2f acc2[PD_ITEM_VALS];
+                            int nv;
+                            item_pass<false>(MatchRegs{mres}, it_res.z, lane, Fm, P.sampson_max, acc2, nv);
+                            sum = item_totals(acc2, nv, it_res.z, P.sampson_max, lane, slot);
+                        } else {
+                            for (int c = 0; c < e.y; ++c) {
+                                const int4 it = D.items[e.x + c];          // (pair, first match, matches, 0): the tables are the one definition of the cuts
+                                v2f acc2[PD_ITEM_VALS];
+                                int nv;
+                                float4 mb[8];
+                                const float4 *pts = D.pts + it.y;
+                                const int last = it.z - 1;
+#pragma unroll
+                                for (int q = 0; q < 8; ++q) {
+                                    const int m = lane + 64 * q;
+                                    mb[q] = pts[m < it.z ? m : last];
+                                }
+                                item_pass<false>(MatchRegs{mb}, it.z, lane, Fm, P.sampson_max, acc2, nv);
+                                const float tot = item_totals(acc2, nv, it.z, P.sampson_max, lane, slot);
+                                sum = c == 0 ? tot : sum + tot;
+                            }
+                        }
+                        if (lane < 16 && slot < PD_ITEM_VALS) L.item[sl * PD_ITEM_VALS + slot] = sum;
+                    }
+                }
+                __syncthreads();
+                PD_PROF2H(q1);
+                // ---- P3a: backward of this workgroup's pairs (thread per pair of the batch), rows 2 sl (side 0), 2 sl + 1 (side 1)
+                if (tid < nb && L.itab[s0 + tid].y > 0) {
+                    const int4 e = L.itab[s0 + tid];
+                    const int pi = e.z, pj = e.w;
+                    const int4 mp = make_int4(0, 0, 1, (2 * tid) | ((2 * tid + 1) << 16));
+                    float G[9];
+#pragma unroll
+                    for (int c = 0; c < 9; ++c) G[c] = L.item[tid * PD_ITEM_VALS + c];
+#include "pd_ggs_pairbwd.inc"
+                }
+                __syncthreads();
+                PD_PROF2H(q2);
+                // ---- hop 1: publish the (pair, side) rows; thread (row = tid / 16, component = tid % 16), 32 rows per pass
+                for (int r0 = 0; r0 < 2 * nb; r0 += PD_GGS_THREADS / 16) {
+                    const int row = r0 + (tid >> 4);
+                    if (row < 2 * nb && L.itab[s0 + (row >> 1)].y > 0) {
+                        u64 *g = xs + (size_t)grow[2 * s0 + row] * PD_XCHG_LINE + (tid & 15);
+                        __hip_atomic_store(g, ((u64)epoch << 32) | (u64)__float_as_uint(own_rows[row * 16 + (tid & 15)]), __ATOMIC_RELAXED,
+                                           __HIP_MEMORY_SCOPE_AGENT);
+                    }
+                }
+                // this workgroup's loss totals {sum s valid, n valid, sum min(s, max)}: lane l takes slots l, l + 64, ... (n_batch % 64 == 0
+                // whenever there are several batches)
+                if (wave == PD_GGS_WAVES - 1) {
+                    for (int sl = lane; sl < nb; sl += 64) {
+                        if (L.itab[s0 + sl].y > 0) {
+                            t0 += L.item[sl * PD_ITEM_VALS + 9];
+                            t1 += L.item[sl * PD_ITEM_VALS + 10];
+                            t2 += L.item[sl * PD_ITEM_VALS + 11];
+                        }
+                    }
+                }
+                // (the next batch's P1 writes L.F only, and its barrier stands before anything overwrites L.item or the own rows)
             }
-            PD_PROF2H(q4);
-            // ---- hop 2: everybody gathers the N frame lines and the k totals lines
-            ok = ggs2_gather<2>(xs + (size_t)(n_inc + k) * PD_XCHG_LINE, tid, N * 8, 8, epoch, L.psum, 16, P.err_flag) && ok;
-            ok = ggs2_gather<1>(xs + (size_t)n_inc * PD_XCHG_LINE, tid, k * 2, 2, epoch, tot_rows, 4, P.err_flag) && ok;
-            if (!ok) {
-                atomicOr(P.err_flag, 1u);
-                L.ctl[1] = 1.0f;
-            }
-            __syncthreads();
-            if (L.ctl[1] != 0.0f) return;
-            PD_PROF2H(q5);
-            // per-frame gradients back through tc = D T and Rc[a][b] = D[a] R[b][a]; totals in workgroup order
-            for (int q = tid; q < N * 16; q += PD_GGS_THREADS) {
-                const int n = q >> 4, c = q & 15;
-                const float v = L.psum[n * 16 + c];
-                if (c < 9) {
-                    const int aa = c / 3, bb = c % 3;
-                    L.gR[n * 9 + bb * 3 + aa] = (aa < 2 ? -v : v);
-                } else if (c < 12) {
-                    L.gT[n * 3 + (c - 9)] = (c - 9 < 2 ? -v : v);
-                } else {
-                    L.gA[n * 4 + (c - 12)] = v;
+            // ... -> its totals line
+            if (wave == PD_GGS_WAVES - 1) {
+                t0 = wave_allsum(t0);
+                t1 = wave_allsum(t1);
+                t2 = wave_allsum(t2);
+                if (lane < 4) {
+                    const float v = lane == 0 ? t0 : (lane == 1 ? t1 : (lane == 2 ? t2 : 0.0f));
+                    __hip_atomic_store(xs + (size_t)(n_inc + wg) * PD_XCHG_LINE + lane, ((u64)epoch << 32) | (u64)__float_as_uint(v),
+                                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 }
             }
-            if (wave >= PD_GGS_WAVES - 3) {                 // one wave per total (round 5: one wave ran the 3 x ceil(k / 64) reductions back to back)
-                const int c = wave - (PD_GGS_WAVES - 3);
-                float t = 0.0f;
-                for (int w0 = 0; w0 < k; w0 += 64) {      // fixed order: 64 workgroups at a time, tree inside
-                    const int w = w0 + lane;
-                    t += wave_allsum(w < k ? tot_rows[w * 4 + c] : 0.0f);
-                }
-                if (lane == 0) *(c == 0 ? &L.cam[6] : (c == 1 ? &L.cam[7] : &L.ctl[2])) = t;
-            }
-            __syncthreads();
-            PD_PROF2H(q6);
+            PD_PROF2H(q3);
+#include "pd_ggs_long_hop2.inc"
 #include "pd_ggs_p4_long.inc"
             __syncthreads();
             PD_PROF2H(q7);

@@ -145,7 +145,9 @@ struct PdGgsPlan {
     int lane, lane_rl;         // lane-per-item kernel chosen; steps RV .. RV + lane_rl - 1 of its longest wave's stream live in LDS for the whole
                                //   launch (<= PD_LANE_RL; the PD_LANE_RING slots of the ring come on top)
     int xchg_local;            // one-hop kernel: XCD-local placement of a sequence's workgroups (see PdGgsParams)
-    int long_frames;           // pd_ggs_long_kernel (more than PD_MAX_FRAMES frames, or PD_GGS_CFG_LONG_FRAMES): k, n_slots, lds and max_items are its shape
+    int long_frames;           // 1: pd_ggs_long_kernel (more than PD_MAX_FRAMES frames, or PD_GGS_CFG_LONG_FRAMES): k, n_slots, lds and max_items are its shape;
+                               //   2: pd_ggs_longm_kernel (PD_OPT_GGS_LONG_PAIR_ITEMS, a slot whose pairs are not all one item): the same shape, sized by
+                               //   frame pairs (max_items = the most pairs of a slot)
 };
 
 // lane items of one frame pair with m matches at lane-item length len: ceil(m / len) items of balanced size (host and device builders)
@@ -284,6 +286,7 @@ struct pd_engine {
     unsigned long long *d_xchg = nullptr;
     size_t xchg_granules = 0;            // per (sequence, slot)
     int ggs_max_frames = PD_MAX_FRAMES;  // PD_OPT_GGS_MAX_FRAMES: frames GGS admits on this engine; d_xchg is sized for it
+    int ggs_long_pair_items = 0;         // PD_OPT_GGS_LONG_PAIR_ITEMS: 1 = above PD_MAX_FRAMES frames a pair may hold several work items (pd_ggs_longm_kernel)
     unsigned int *d_err = nullptr;       // [0] async error word; [2..] debug phase counters
     int ggs_prof_on = 0;
     int den_fused_attn = 1;          // PD_OPT_DENOISER_FUSED_ATTN: in the fp16-plane mode, in_proj + attention as one kernel with Q / K / V in LDS (N <= 32)

@@ -46,6 +46,7 @@ class GaussianDiffusion(nn.Module):
         self.last_ggs_stats = None
         self.ggs_max_frames = host.GGS_MAX_FRAMES      # frames guided sampling admits; raise it (<= 256) to guide longer sequences: the engine
         #                                                then holds a larger exchange region (PD_OPT_GGS_MAX_FRAMES, include/pd_engine.h)
+        self.ggs_long_pair_items = False               # True: above 64 frames, take frame pairs of more than 512 matches (PD_OPT_GGS_LONG_PAIR_ITEMS)
 
     # ---- schedule helpers (:190-216): elementwise on the buffers, same names and argument order; the sampler itself has these
     # fused into pd_tail_kernel and does not call them
@@ -128,7 +129,8 @@ class GaussianDiffusion(nn.Module):
         if has_ggs and N > ggs_max:
             # the denoiser takes up to 256 frames, GGS 64 unless ggs_max_frames was raised (include/pd_engine.h): no silent fallback to unguided sampling
             raise RuntimeError(f"guided sampling (GGS) is limited to {ggs_max} frames, got {N}: run unguided (GGS.enable=False)")
-        eng = host.get_engine(self.model, self, B, N, ggs_max_frames=ggs_max if has_ggs else host.GGS_MAX_FRAMES)
+        eng = host.get_engine(self.model, self, B, N, ggs_max_frames=ggs_max if has_ggs else host.GGS_MAX_FRAMES,
+                              ggs_long_pair_items=has_ggs and bool(getattr(self, "ggs_long_pair_items", False)))
         if cond_fn is not None and parsed is None and n_frames is not None:
             raise NotImplementedError("n_frames with a guidance callable other than the shipped geometry_guided_sampling partial: "
                                       "a callable sees one padded [B, N, 9] tensor and cannot know the counts")

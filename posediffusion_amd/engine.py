@@ -45,11 +45,13 @@ class PoseEngine:
     (``time_embed.linear.0.weight`` ... ``_last.3.bias``); ``tables`` the GaussianDiffusion buffers.  ``norm_first`` /
     ``pivot``: TransformerEncoderWrapper(norm_first=...) and Denoiser(pivot_cam_onehot=...); ``generic``: run the shape-generic
     denoiser kernels even at the default shape (PD_WEIGHTS_GENERIC, comparison / testing); ``ggs_max_frames``: the frames GGS admits
-    (PD_OPT_GGS_MAX_FRAMES: 64 unless given; a value in (64, max_N] sizes the exchange region for such sequences)."""
+    (PD_OPT_GGS_MAX_FRAMES: 64 unless given; a value in (64, max_N] sizes the exchange region for such sequences);
+    ``ggs_long_pair_items``: above 64 frames, admit frame pairs of more than 512 matches (PD_OPT_GGS_LONG_PAIR_ITEMS, off by default)."""
 
     def __init__(self, denoiser_sd: Dict[str, torch.Tensor], tables: Dict[str, torch.Tensor], device=None,
                  max_B: int = 8, max_N: int = 20, num_layers: int = 8, nhead: int = 4, objective: str = "pred_noise",
-                 norm_first: bool = True, pivot: bool = True, generic: bool = False, ggs_max_frames: Optional[int] = None):
+                 norm_first: bool = True, pivot: bool = True, generic: bool = False, ggs_max_frames: Optional[int] = None,
+                 ggs_long_pair_items: bool = False):
         if objective not in ("pred_noise", "pred_x0"):                     # models/gaussian_diffuser.py:105-108
             raise AssertionError("objective must be either pred_noise (predict noise) or pred_x0 (predict image start)")
         if not torch.cuda.is_available():
@@ -108,12 +110,14 @@ class PoseEngine:
             if self.has_q_tables:
                 _lib.check(self.lib.pd_engine_set_q_tables(self._h, *(dev(tables[n]) for n in _Q_TABLES)), "pd_engine_set_q_tables")
         del keep
-        if ggs_max_frames is not None:
-            try:
+        try:
+            if ggs_max_frames is not None:
                 self.set_option(_lib.PD_OPT_GGS_MAX_FRAMES, int(ggs_max_frames))
-            except Exception:
-                self.close()
-                raise
+            if ggs_long_pair_items:
+                self.set_option(_lib.PD_OPT_GGS_LONG_PAIR_ITEMS, 1)
+        except Exception:
+            self.close()
+            raise
 
     # ---------------------------------------------------------------- lifecycle
     def close(self):
@@ -262,7 +266,7 @@ class PoseEngine:
 
         ``n_frames`` [n]: one frame count per sequence (pd_ggs_set_matches_csr_async_nf) -- a ragged batch in one call, and the way in
         for sequences of 65 .. 256 frames (engines with ``ggs_max_frames`` raised; ``max_matches_per_pair`` in 1 .. 512 is then
-        required).  ``img_shape[0]`` must then only be >= every count.  Without it the call is the one frame count ``img_shape[0]``."""
+        required, unless the engine has ``ggs_long_pair_items``: then 0 = unknown and values above 512 are taken too).  ``img_shape[0]`` must then only be >= every count.  Without it the call is the one frame count ``img_shape[0]``."""
         for name, t, dt in (("kp1", kp1, torch.float64), ("kp2", kp2, torch.float64), ("i12", i12, torch.int64)):
             if t.dtype != dt or t.dim() != 2 or t.shape[1] != 2 or not t.is_contiguous():
                 raise ValueError(f"{name} must be a contiguous {dt} tensor of shape [total, 2]")
@@ -315,7 +319,7 @@ class PoseEngine:
         return x, stats
 
     def ggs_plan(self, B: int, N: int, cfg=None, n_frames=None):
-        """pd_debug_ggs_plan: {workgroups per sequence, item slots, LDS bytes, two-hop, waves, staging pieces, lane kernel, its LDS steps}."""
+        """pd_debug_ggs_plan: {workgroups per sequence, item slots, LDS bytes, two-hop (2 / 3: the kernels for more than 64 frames), waves, staging pieces, lane kernel, its LDS steps}."""
         c = cfg if isinstance(cfg, _lib.pd_ggs_cfg) else make_ggs_cfg(cfg)
         out = (C.c_int * 8)()
         with self._counts(n_frames):
@@ -394,6 +398,11 @@ class PoseEngine:
     def ggs_max_frames(self) -> int:
         """The frames GGS admits on this engine (PD_OPT_GGS_MAX_FRAMES)."""
         return self.get_option(_lib.PD_OPT_GGS_MAX_FRAMES)
+
+    @property
+    def ggs_long_pair_items(self) -> bool:
+        """Whether GGS above 64 frames takes frame pairs of more than 512 matches on this engine (PD_OPT_GGS_LONG_PAIR_ITEMS)."""
+        return bool(self.get_option(_lib.PD_OPT_GGS_LONG_PAIR_ITEMS))
 
     def get_option(self, option: int) -> int:
         """pd_engine_get_option: e.g. ``_lib.PD_OPT_DENOISER_SPLIT`` -> the encoder GEMM mode in force (0 after the non-finite-weights downgrade)."""

@@ -36,9 +36,11 @@ def denoiser_state(denoiser: torch.nn.Module) -> Dict[str, torch.Tensor]:
     return {k: v for k, v in denoiser.state_dict().items() if k.startswith(_DENOISER_PREFIXES)}
 
 
-def get_engine(denoiser: torch.nn.Module, diffuser: Optional[torch.nn.Module], B: int, N: int, ggs_max_frames: int = GGS_MAX_FRAMES) -> PoseEngine:
+def get_engine(denoiser: torch.nn.Module, diffuser: Optional[torch.nn.Module], B: int, N: int, ggs_max_frames: int = GGS_MAX_FRAMES,
+               ggs_long_pair_items: bool = False) -> PoseEngine:
     """Engine for these live modules (rebuilt when weights, device or capacity change).  ``ggs_max_frames`` above 64 RAISES the frames GGS
-    admits on the engine (PD_OPT_GGS_MAX_FRAMES; capped at the engine's max_N), never lowers them on a cached one."""
+    admits on the engine (PD_OPT_GGS_MAX_FRAMES; capped at the engine's max_N), never lowers them on a cached one; ``ggs_long_pair_items``
+    likewise only ever switches PD_OPT_GGS_LONG_PAIR_ITEMS (frame pairs of more than 512 matches above 64 frames) ON."""
     dev = next(denoiser.parameters()).device
     if dev.type != "cuda":
         raise RuntimeError("the PoseDiffusion sampling path of posediffusion_amd runs only on an AMD GPU "
@@ -51,11 +53,12 @@ def get_engine(denoiser: torch.nn.Module, diffuser: Optional[torch.nn.Module], B
     objective = getattr(diffuser, "objective", None)           # Denoiser.forward alone does not depend on it
     if ent is not None and ent[0][0] == fp_den and (fp_diff is None or ent[0][1] == fp_diff) \
             and ent[1].max_B >= B and ent[1].max_N >= N and objective in (None, ent[1].objective):
-        _raise_ggs_limit(ent[1], ggs_max_frames)
+        _raise_ggs_limit(ent[1], ggs_max_frames, ggs_long_pair_items)
         return ent[1]
     if ent is not None:
         B, N = max(B, ent[1].max_B), max(N, ent[1].max_N)     # never shrink capacity on a rebuild
         ggs_max_frames = max(int(ggs_max_frames), ent[1].ggs_max_frames)
+        ggs_long_pair_items = bool(ggs_long_pair_items) or ent[1].ggs_long_pair_items
         ent[1].close()
     fp = (fp_den, fp_diff)
     if diffuser is not None:
@@ -69,16 +72,18 @@ def get_engine(denoiser: torch.nn.Module, diffuser: Optional[torch.nn.Module], B
     pivot = bool(getattr(denoiser, "pivot_cam_onehot", True))
     eng = PoseEngine(denoiser_state(denoiser), tables, device=dev, max_B=max(B, 1), max_N=max(N, 1),
                      num_layers=layers, nhead=nhead, objective=objective or "pred_noise", norm_first=norm_first, pivot=pivot)
-    _raise_ggs_limit(eng, ggs_max_frames)
+    _raise_ggs_limit(eng, ggs_max_frames, ggs_long_pair_items)
     cache["e"] = (fp, eng)
     _ENGINES[dev.index if dev.index is not None else torch.cuda.current_device()] = eng
     return eng
 
 
-def _raise_ggs_limit(eng: PoseEngine, ggs_max_frames: int):
+def _raise_ggs_limit(eng: PoseEngine, ggs_max_frames: int, ggs_long_pair_items: bool = False):
     want = min(int(ggs_max_frames), eng.max_N)
     if want > GGS_MAX_FRAMES and want > eng.ggs_max_frames:
         eng.set_option(_lib.PD_OPT_GGS_MAX_FRAMES, want)
+    if ggs_long_pair_items and not eng.ggs_long_pair_items:
+        eng.set_option(_lib.PD_OPT_GGS_LONG_PAIR_ITEMS, 1)
 
 
 def parse_ggs_cond_fn(cond_fn):
@@ -179,7 +184,8 @@ def upload_matches(engine: PoseEngine, matches, B: int, n_frames=None, device_si
 
     ``device_side``: the slots that need an upload go up through ONE ragged device-side call per run of consecutive slots
     (``pack_matches_ragged`` + ``PoseEngine.set_matches_async(..., n_frames=)``, ``max_matches_per_pair`` taken from the data) in
-    place of the synchronous host builder, which stays the default."""
+    place of the synchronous host builder, which stays the default.  Above 64 frames a pair of more than 512 matches needs an engine
+    with ``ggs_long_pair_items`` on either path (the device-side call is refused at once, the host-built tables at the first GGS launch)."""
     lst = list(matches) if isinstance(matches, (list, tuple)) else [matches]
     if len(lst) != B:
         raise ValueError(f"GGS needs one matches_dict per sequence: got {len(lst)} for B={B} "
