@@ -179,8 +179,9 @@ int pd_p_finish(pd_engine *eng, const float *mean, const float *noise, int t, in
  * GaussianDiffusion.forward / p_losses draw one t per sequence (gaussian_diffuser.py:331).  These entry points run that forward pass
  * in ONE pass of the denoiser: `_first` and the tail look the timestep of every token row up on the device (t_seq[row / N]); a
  * t_seq whose entries are all equal gives bitwise the results of the single-t entry points.  Forward only: nothing here computes
- * a gradient, and the network is evaluated as under model.eval() -- dropout off (the reference under model.train() applies
- * dropout 0.1, which the engine deliberately does not reproduce).
+ * a gradient (the loss WITH its parameter gradients is pd_train_forward / pd_train_backward, pd_engine_train.h), and the network is
+ * evaluated as under model.eval() -- dropout off (the reference under model.train() applies dropout 0.1, which the engine
+ * deliberately does not reproduce).
  * An entry of t_seq outside [0, timesteps) cannot be seen by the host without a synchronisation: the device clamps it into the
  * range (so no table is read out of bounds) and raises bit 3 of the asynchronous error word (pd_check_async_error).
  * Argument checks and limits are those of pd_denoise_step: N <= 256, B <= max_B, N <= max_N; default-shape and generic engines,

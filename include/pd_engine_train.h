@@ -1,0 +1,82 @@
+/*
+ * pd_engine_train.h -- the training branch with gradients: GaussianDiffusion.p_losses (models/gaussian_diffuser.py:308-327) forward
+ * AND backward through the Denoiser (models/denoiser.py:53-76) on hand-written gfx950 kernels (csrc/pd_train.hip).
+ *
+ * An extension header like pd_engine_ingest.h: the function list of pd_engine.h is pinned.  The surface is a separate opaque object,
+ * pd_trainer; pd_engine and all its launches are untouched.
+ *
+ * What a trainer is
+ *   - it keeps NO weight copy: every call reads the caller's LIVE tensors (DEVICE pointers, PyTorch layout [out, in]) through the
+ *     pd_weights it is handed, so an optimiser step needs no rebuild and no repacking;
+ *   - it owns one activation stash sized at creation for max_B x max_N token rows, and the two q_sample tables;
+ *   - exact fp32 everywhere (v_mfma_f32_32x32x2_f32), eval-mode function (no dropout), pre-norm only, N <= 64 frames, head dim <= 128,
+ *     pivot column on or off, both objectives, both loss types;
+ *   - no float atomics in any reduction: gradients are bitwise reproducible and do not depend on the trainer's capacity (every
+ *     reduction over token rows is chunked by a function of M = B x N alone and its partial sums are added in chunk order);
+ *   - the image backbone is not differentiated: dz is handed back for whoever owns z.
+ * Conventions are those of pd_engine.h (return codes, pd_last_error, `stream` = hipStream_t as void *).  Both calls are asynchronous on
+ * `stream`; after pd_trainer_create nothing synchronises with the host and nothing is allocated.
+ */
+#ifndef PD_ENGINE_TRAIN_H
+#define PD_ENGINE_TRAIN_H
+
+#include "pd_engine.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+typedef struct pd_trainer pd_trainer;
+
+/* mirrors pd_layer_weights: where the gradient of each tensor goes (DEVICE fp32, the parameter's own layout); NULL = not wanted */
+typedef struct pd_layer_grads {
+    float *norm1_w, *norm1_b;
+    float *in_proj_w, *in_proj_b;
+    float *out_proj_w, *out_proj_b;
+    float *norm2_w, *norm2_b;
+    float *linear1_w, *linear1_b;
+    float *linear2_w, *linear2_b;
+} pd_layer_grads;
+
+/* mirrors the weight members of pd_weights */
+typedef struct pd_weight_grads {
+    float *time_w0, *time_b0, *time_w2, *time_b2, *first_w, *first_b;
+    pd_layer_grads layers[PD_MAX_LAYERS];
+    float *last0_w, *last0_b, *last_ln_w, *last_ln_b, *last3_w, *last3_b;
+} pd_weight_grads;
+
+/* Reads only the shape fields, the flags and the schedule tables of `shape` (no weight pointer is touched) and copies the two q_sample
+ * tables ([timesteps] DEVICE fp32 each, gaussian_diffuser.py:164-165) plus shape->sqrt_recip / sqrt_recipm1_alphas_cumprod (x_0_pred
+ * under pred_noise; NULL there makes x0_pred_out unavailable).  Sizes the stash for max_B x max_N token rows.  Synchronous.
+ * PD_ERR_UNSUPPORTED, naming the limit, for PD_WEIGHTS_POST_NORM, a head dim above 128, and anything outside pd_weights' family. */
+int pd_trainer_create(const pd_weights *shape, const float *sqrt_alphas_cumprod, const float *sqrt_one_minus_alphas_cumprod,
+                      int max_B, int max_N, pd_trainer **out);
+void pd_trainer_destroy(pd_trainer *tr);
+
+/* The contract of pd_p_losses (same outputs, same t_seq clamping -- a clamped timestep raises the trainer's own error word,
+ * pd_trainer_check_async) with the weights taken from `w` at the time of the call, and the stash the backward needs:
+ * per layer the residual stream at both sublayer inputs, both LayerNorm (mean, rstd) pairs, qkv, ctx and the post-ReLU FF activations;
+ * _first's input rows; _last's LayerNorm input, statistics and post-ReLU hidden; the time embedding's SiLU input.  Attention
+ * probabilities are recomputed by the backward.  N > 64: PD_ERR_UNSUPPORTED before anything is launched.  loss_type 1 = l1, 2 = l2. */
+int pd_train_forward(pd_trainer *tr, const pd_weights *w, const float *x_start, const float *z, const int64_t *t_seq,
+                     const float *noise, int B, int N, int loss_type,
+                     float *loss_out, float *x0_pred_out, float *xt_out, float *model_out, void *stream);
+
+/* With S = sum(g_loss * loss) over the [B, N, 9] elements: writes dS/dtheta for every non-NULL member of `grads` (an overwrite, in the
+ * parameter's own layout; a NULL member's weight-gradient launch is not issued) and dS/dz [B, N, z_dim] when dz_out is non-NULL.
+ * Loss derivative: sign(d) with sign(0) = 0 (l1), 2 d (l2), d = model_out - target; x_0_pred carries no gradient.
+ * Consumes the stash: PD_ERR_STATE when no forward is pending.  `w` must point to the same unmodified tensors as the forward's. */
+int pd_train_backward(pd_trainer *tr, const pd_weights *w, const float *g_loss, const pd_weight_grads *grads, float *dz_out,
+                      void *stream);
+
+/* The tests' window into the stash of the pending (or last) forward: layer < num_layers -> that layer's [B x N, dim_ff] post-ReLU FF
+ * activations; layer == num_layers -> _last's [B x N, mlp_hidden] post-ReLU values.  n_floats must be exactly that size. */
+int pd_train_debug_relu(pd_trainer *tr, int layer, float *dst, long long n_floats, void *stream);
+
+/* Synchronises the device; PD_ERR_STATE if pd_train_forward met (and clamped) a timestep outside [0, timesteps) since the last check. */
+int pd_trainer_check_async(pd_trainer *tr);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* PD_ENGINE_TRAIN_H */

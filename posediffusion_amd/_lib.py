@@ -39,6 +39,20 @@ class pd_weights(C.Structure):
     )
 
 
+class pd_layer_grads(C.Structure):
+    """include/pd_engine_train.h: where each tensor's gradient goes (mirrors pd_layer_weights; None = not wanted)"""
+    _fields_ = list(pd_layer_weights._fields_)
+
+
+class pd_weight_grads(C.Structure):
+    """include/pd_engine_train.h: mirrors the weight members of pd_weights"""
+    _fields_ = (
+        [(n, C.c_void_p) for n in ("time_w0", "time_b0", "time_w2", "time_b2", "first_w", "first_b")]
+        + [("layers", pd_layer_grads * PD_MAX_LAYERS)]
+        + [(n, C.c_void_p) for n in ("last0_w", "last0_b", "last_ln_w", "last_ln_b", "last3_w", "last3_b")]
+    )
+
+
 class pd_vit_layer_weights(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("norm1_w", "norm1_b", "qkv_w", "qkv_b", "proj_w", "proj_b", "norm2_w", "norm2_b",
                                           "fc1_w", "fc1_b", "fc2_w", "fc2_b")]
@@ -133,6 +147,15 @@ SIGNATURES = {
 EXT_SIGNATURES = {
     "pd_ggs_set_matches_csr_async_nf": (_i, [_vp, _i, _i, C.POINTER(_i64), _vp, _vp, _vp, C.POINTER(_i), _i, _i, C.POINTER(pd_match_hints), _vp]),
 }
+# the exports of include/pd_engine_train.h: the training branch with gradients (a table of its own -- tests pin the other two lists)
+TRAIN_SIGNATURES = {
+    "pd_trainer_create": (_i, [C.POINTER(pd_weights), _vp, _vp, _i, _i, C.POINTER(_vp)]),
+    "pd_trainer_destroy": (None, [_vp]),
+    "pd_train_forward": (_i, [_vp, C.POINTER(pd_weights), _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "pd_train_backward": (_i, [_vp, C.POINTER(pd_weights), _vp, C.POINTER(pd_weight_grads), _vp, _vp]),
+    "pd_train_debug_relu": (_i, [_vp, _i, _vp, C.c_longlong, _vp]),
+    "pd_trainer_check_async": (_i, [_vp]),
+}
 
 _lib = None
 
@@ -162,7 +185,7 @@ def load():
             "There is no CPU fallback.")
     import torch  # noqa: F401  (loads the HIP runtime first)
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-    for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **TRAIN_SIGNATURES}.items():
         if os.environ.get("PD_ENGINE_LIB") and not hasattr(lib, name):
             continue              # an older build under A / B lacks the newest debug exports
         fn = getattr(lib, name)   # AttributeError here = library does not match the header

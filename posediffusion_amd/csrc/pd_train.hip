@@ -1,0 +1,396 @@
+// pd_train.hip -- the training branch with gradients (include/pd_engine_train.h): GaussianDiffusion.p_losses forward with an activation
+// stash, and the backward of the diffusion loss through the Denoiser to every parameter and to z.  Kernels: pd_train_kernels.h.
+//
+// Replaces (paths relative to the reference's pose_diffusion/): the autograd graph of models/gaussian_diffuser.py:308-327 over
+// models/denoiser.py:53-76 that train.py:245-251 back-propagates.  The optimiser, LR schedule and clipping stay PyTorch's.
+//
+// Forward (the generic path's structure, DESIGN 3.5, on the caller's live weights):
+//   q_sample -> time embedding of the B timesteps -> _first's rows -> _first GEMM -> per layer { LN1 (+stats) -> in_proj GEMM -> attention ->
+//   out_proj GEMM + residual -> LN2 (+stats) -> linear1 GEMM + ReLU -> linear2 GEMM + residual } -> _last.0 GEMM -> tail (+loss)
+// The residual stream is never updated in place: hres[i] is the stream at sublayer input i (2 L + 1 arrays), which IS the stash.
+// Backward: tail -> _last.0 -> per layer in reverse { linear2, ReLU mask, linear1, LN2, out_proj, attention, in_proj, LN1 } -> _first
+//   (weight gradient over all columns, data gradient for the t_emb and z columns only) -> time embedding.
+#include "pd_train_kernels.h"
+#include "../../include/pd_engine_train.h"
+
+#include <algorithm>
+#include <string.h>
+
+struct PdTrLayerStash {
+    float *stats1, *stats2;         // [M, 2] (mean, rstd)
+    float *qkv, *ctx, *ffa;         // [M, 3 d], [M, d], [M, ff] (post-ReLU)
+};
+
+struct pd_trainer {
+    int d = 0, nhead = 0, hd = 0, ff = 0, z = 0, hid = 0, layers = 0, timesteps = 0, pivot = 1, pred_x0 = 0, Kf = 0;
+    int max_B = 0, max_N = 0, m_cap = 0;
+    // tables (copies)
+    float *qa = nullptr, *qb = nullptr, *c_recip = nullptr, *c_recipm1 = nullptr;
+    // stash
+    float *xt = nullptr, *emb = nullptr;                 // [M, 9], [M, Kf]
+    float *hres[2 * PD_MAX_LAYERS + 1] = {};             // [M, d] each
+    PdTrLayerStash L[PD_MAX_LAYERS] = {};
+    float *hid_pre = nullptr, *hid_post = nullptr, *hid_stats = nullptr, *dl = nullptr;   // [M, hid] x 2, [M, 2], [M, 9]
+    float *t_emb256 = nullptr, *t_a0 = nullptr, *t_sact = nullptr, *t_emb = nullptr;      // [B, 256], [B, 128] x 3
+    int *t_b = nullptr;                                  // [B]
+    // scratch
+    float *hn = nullptr, *dres = nullptr, *dhn = nullptr, *dff = nullptr, *dqkv = nullptr;
+    float *dy_hid = nullptr, *dhid = nullptr, *gout = nullptr, *demb_t = nullptr, *dtemb = nullptr, *dts = nullptr;
+    float *ws = nullptr;                                 // split-reduction workspaces: weight-gradient partials [chunks][Nout x K] ...
+    double *ws_col = nullptr;                            // ... and column-sum partials [2][chunks][C]
+    size_t ws_floats = 0, ws_col_floats = 0;
+    unsigned int *d_err = nullptr;
+    int pend_B = 0, pend_N = 0;                          // B, N of the pending forward (0: none)
+    int last_B = 0, last_N = 0;                          // of the last forward (pd_train_debug_relu)
+    PdDevAllocs mem{"pd_trainer_create"};
+};
+
+// ---- launch helpers ------------------------------------------------------------------------
+// the chunks of a reduction over M token rows: a function of M alone
+static void pd_tr_chunks(int M, int *n_chunks, int *rows) {
+    int n = std::min(PD_TR_MAX_CHUNKS, (M + 255) / 256);
+    int r = (M + n - 1) / n;
+    r = (r + 31) / 32 * 32;
+    *rows = r;
+    *n_chunks = (M + r - 1) / r;
+}
+
+static void tr_gemm_launch(const PdTrGemm &g, int nz, hipStream_t s) {
+    hipLaunchKernelGGL(pd_tr_gemm_kernel, dim3((g.J + 63) / 64, (g.I + 63) / 64, nz), dim3(256), 0, s, g);
+}
+
+// Y[M, Nout] = X[M, K] W[Nout, K]^T + b (+ ReLU) (+ resid)
+static void tr_linear(const float *X, const float *W, const float *b, float *Y, int M, int Nout, int K, int relu, const float *resid, hipStream_t s) {
+    PdTrGemm g;
+    memset(&g, 0, sizeof(g));
+    g.A = X; g.a_rs = K; g.a_cs = 1; g.a_rfast = 1;
+    g.B = W; g.b_rs = 1; g.b_cs = K; g.b_rfast = 1;
+    g.C = Y; g.ldc = Nout; g.bias = b; g.relu = relu; g.resid = resid; g.ldr = Nout;
+    g.I = M; g.J = Nout; g.R = K; g.r_chunk = K;
+    tr_gemm_launch(g, 1, s);
+}
+
+// dX[M, Kw] = dY[M, Nout] W[:, koff : koff + Kw] (W [Nout, ldw]), masked by aux (mode 1 / 2), written or accumulated into dX
+static void tr_dgrad(const float *dY, const float *W, int ldw, int koff, float *dX, int M, int Nout, int Kw, const float *aux, int mask_mode,
+                     bool accumulate, hipStream_t s) {
+    PdTrGemm g;
+    memset(&g, 0, sizeof(g));
+    g.A = dY; g.a_rs = Nout; g.a_cs = 1; g.a_rfast = 1;
+    g.B = W + koff; g.b_rs = ldw; g.b_cs = 1; g.b_rfast = 0;
+    g.C = dX; g.ldc = Kw; g.aux = aux; g.ldaux = Kw; g.mask_mode = aux ? mask_mode : 0;
+    if (accumulate) {
+        g.resid = dX;
+        g.ldr = Kw;
+    }
+    g.I = M; g.J = Kw; g.R = Nout; g.r_chunk = Nout;
+    tr_gemm_launch(g, 1, s);
+}
+
+// dW[Nout, K] = sum_m dY[m, :]^T X[m, :] over the chunks of M, partials added in chunk order; db[Nout] = sum_m dY[m, :] likewise
+static void tr_wgrad(pd_trainer *tr, const float *dY, const float *X, float *dW, float *db, int M, int Nout, int K, hipStream_t s) {
+    int nch, rows;
+    pd_tr_chunks(M, &nch, &rows);
+    if (dW) {
+        PdTrGemm g;
+        memset(&g, 0, sizeof(g));
+        g.A = dY; g.a_rs = 1; g.a_cs = Nout; g.a_rfast = 0;
+        g.B = X; g.b_rs = K; g.b_cs = 1; g.b_rfast = 0;
+        g.C = nch > 1 ? tr->ws : dW; g.ldc = K;
+        g.I = Nout; g.J = K; g.R = M; g.r_chunk = rows;
+        tr_gemm_launch(g, nch, s);
+        if (nch > 1) {
+            const long long total = (long long)Nout * K;
+            hipLaunchKernelGGL(pd_tr_reduce_kernel<float>, dim3((unsigned)std::min<long long>((total + 255) / 256, 2048)), dim3(256), 0, s, tr->ws, total, nch, dW);
+        }
+    }
+    if (db) {
+        hipLaunchKernelGGL(pd_tr_colsum_kernel<false>, dim3((Nout + 63) / 64, nch), dim3(256), 0, s, dY, (long long)Nout, nullptr, 0LL, nullptr, M, Nout, rows,
+                           nullptr, tr->ws_col);
+        hipLaunchKernelGGL(pd_tr_reduce_kernel<double>, dim3((Nout + 255) / 256), dim3(256), 0, s, tr->ws_col, (long long)Nout, nch, db);
+    }
+}
+
+// LayerNorm's dgamma = sum_m dy xhat, dbeta = sum_m dy
+static void tr_ln_param_grads(pd_trainer *tr, const float *dy, const float *x, const float *stats, float *dgamma, float *dbeta, int M, int D, hipStream_t s) {
+    if (!dgamma && !dbeta) return;
+    int nch, rows;
+    pd_tr_chunks(M, &nch, &rows);
+    double *pa = tr->ws_col, *pb = tr->ws_col + (size_t)PD_TR_MAX_CHUNKS * D;     // [chunks][D] each
+    hipLaunchKernelGGL(pd_tr_colsum_kernel<true>, dim3((D + 63) / 64, nch), dim3(256), 0, s, dy, (long long)D, x, (long long)D, stats, M, D, rows, pa, pb);
+    if (dgamma) hipLaunchKernelGGL(pd_tr_reduce_kernel<double>, dim3((D + 255) / 256), dim3(256), 0, s, pa, (long long)D, nch, dgamma);
+    if (dbeta) hipLaunchKernelGGL(pd_tr_reduce_kernel<double>, dim3((D + 255) / 256), dim3(256), 0, s, pb, (long long)D, nch, dbeta);
+}
+
+// ---- shape checks ----------------------------------------------------------------------------
+static int tr_shape_check(const pd_weights *w, const char *who) {
+    const int d = w->d_model, nh = w->nhead;
+    const char *msg = nullptr;
+    if (d < 32 || d > 2048 || d % 32) msg = "d_model must be a multiple of 32 in [32, 2048]";
+    else if (nh < 1 || d % nh) msg = "nhead must divide d_model";
+    else if ((d / nh) % 4 || d / nh < 8) msg = "the head dim d_model / nhead must be a multiple of 4, at least 8";
+    else if (d / nh > PD_TR_MAX_HD) msg = "the trainer's attention backward takes a head dim of at most 128";
+    else if (w->reserved & PD_WEIGHTS_POST_NORM) msg = "the trainer is pre-norm only (norm_first=True); post-norm has no backward";
+    else if (w->dim_ff < 1 || w->dim_ff > 8192) msg = "dim_feedforward must be in [1, 8192]";
+    else if (w->num_layers < 1 || w->num_layers > PD_MAX_LAYERS) msg = "num_encoder_layers must be in [1, PD_MAX_LAYERS = 16]";
+    else if (w->z_dim < 1 || w->z_dim > 4096) msg = "z_dim must be in [1, 4096]";
+    else if (w->mlp_hidden < 1 || w->mlp_hidden > 1024) msg = "mlp_hidden_dim must be in [1, 1024]";
+    else if (w->n_harmonic != 10 || w->t_emb_dim != 256) msg = "the pose / time embeddings must be the reference's (10 harmonics, t_emb 256)";
+    else if (w->timesteps < 1) msg = "timesteps must be positive";
+    if (msg) {
+        pd_set_error("%s: unsupported configuration: %s (d_model=%d nhead=%d ff=%d layers=%d z=%d hidden=%d flags=%d)", who, msg, d, nh, w->dim_ff,
+                     w->num_layers, w->z_dim, w->mlp_hidden, w->reserved);
+        return PD_ERR_UNSUPPORTED;
+    }
+    return PD_OK;
+}
+
+extern "C" int pd_trainer_create(const pd_weights *shape, const float *sqrt_alphas_cumprod, const float *sqrt_one_minus_alphas_cumprod,
+                                 int max_B, int max_N, pd_trainer **out) {
+    if (!shape || !out || !sqrt_alphas_cumprod || !sqrt_one_minus_alphas_cumprod || max_B < 1 || max_N < 1) {
+        pd_set_error("pd_trainer_create: invalid arguments (NULL shape / tables / out, or max_B=%d max_N=%d not positive)", max_B, max_N);
+        return PD_ERR_INVALID_ARG;
+    }
+    *out = nullptr;
+    PD_TRY(tr_shape_check(shape, "pd_trainer_create"));
+    pd_trainer *tr = new pd_trainer();
+    tr->d = shape->d_model; tr->nhead = shape->nhead; tr->hd = tr->d / tr->nhead; tr->ff = shape->dim_ff; tr->z = shape->z_dim;
+    tr->hid = shape->mlp_hidden; tr->layers = shape->num_layers; tr->timesteps = shape->timesteps;
+    tr->pivot = (shape->reserved & PD_WEIGHTS_NO_PIVOT) ? 0 : 1;
+    tr->pred_x0 = (shape->reserved & PD_WEIGHTS_PRED_X0) ? 1 : 0;
+    tr->Kf = PD_TR_FIRST_FIXED + tr->z + tr->pivot;
+    tr->max_B = max_B; tr->max_N = max_N; tr->m_cap = max_B * max_N;
+    const size_t rows = (size_t)tr->m_cap, d = tr->d, T = tr->timesteps;
+    int rc = PD_OK;
+#define TR_A(p, n) if (rc == PD_OK) rc = tr->mem.alloc(&(p), (size_t)(n), true)
+    TR_A(tr->qa, T); TR_A(tr->qb, T);
+    if (shape->sqrt_recip_alphas_cumprod && shape->sqrt_recipm1_alphas_cumprod) {
+        TR_A(tr->c_recip, T); TR_A(tr->c_recipm1, T);
+    }
+    TR_A(tr->xt, rows * 9); TR_A(tr->emb, rows * tr->Kf);
+    for (int i = 0; i <= 2 * tr->layers; ++i) TR_A(tr->hres[i], rows * d);
+    for (int l = 0; l < tr->layers; ++l) {
+        TR_A(tr->L[l].stats1, rows * 2); TR_A(tr->L[l].stats2, rows * 2);
+        TR_A(tr->L[l].qkv, rows * 3 * d); TR_A(tr->L[l].ctx, rows * d); TR_A(tr->L[l].ffa, rows * tr->ff);
+    }
+    TR_A(tr->hid_pre, rows * tr->hid); TR_A(tr->hid_post, rows * tr->hid); TR_A(tr->hid_stats, rows * 2); TR_A(tr->dl, rows * 9);
+    TR_A(tr->t_emb256, (size_t)max_B * 256); TR_A(tr->t_a0, (size_t)max_B * 128); TR_A(tr->t_sact, (size_t)max_B * 128); TR_A(tr->t_emb, (size_t)max_B * 128);
+    TR_A(tr->t_b, (size_t)max_B);
+    TR_A(tr->hn, rows * d); TR_A(tr->dres, rows * d); TR_A(tr->dhn, rows * d); TR_A(tr->dff, rows * tr->ff); TR_A(tr->dqkv, rows * 3 * d);
+    TR_A(tr->dy_hid, rows * tr->hid); TR_A(tr->dhid, rows * tr->hid); TR_A(tr->gout, rows * 9); TR_A(tr->demb_t, rows * 128);
+    TR_A(tr->dtemb, (size_t)max_B * 128); TR_A(tr->dts, (size_t)max_B * 128);
+    const size_t widest_w = std::max({(size_t)d * tr->Kf, (size_t)3 * d * d, (size_t)tr->ff * d, (size_t)tr->hid * d, (size_t)9 * tr->hid, (size_t)128 * 256});
+    tr->ws_floats = widest_w * PD_TR_MAX_CHUNKS;
+    const size_t widest_c = std::max({(size_t)3 * d, (size_t)tr->ff, (size_t)tr->hid, (size_t)256});
+    tr->ws_col_floats = 2 * widest_c * PD_TR_MAX_CHUNKS;
+    TR_A(tr->ws, tr->ws_floats); TR_A(tr->ws_col, tr->ws_col_floats);
+    TR_A(tr->d_err, 4);
+#undef TR_A
+    if (rc == PD_OK && hipMemcpy(tr->qa, sqrt_alphas_cumprod, T * sizeof(float), hipMemcpyDeviceToDevice) != hipSuccess) rc = PD_ERR_HIP;
+    if (rc == PD_OK && hipMemcpy(tr->qb, sqrt_one_minus_alphas_cumprod, T * sizeof(float), hipMemcpyDeviceToDevice) != hipSuccess) rc = PD_ERR_HIP;
+    if (rc == PD_OK && tr->c_recip) {
+        if (hipMemcpy(tr->c_recip, shape->sqrt_recip_alphas_cumprod, T * sizeof(float), hipMemcpyDeviceToDevice) != hipSuccess ||
+            hipMemcpy(tr->c_recipm1, shape->sqrt_recipm1_alphas_cumprod, T * sizeof(float), hipMemcpyDeviceToDevice) != hipSuccess)
+            rc = PD_ERR_HIP;
+    }
+    // dynamic-LDS limits are per-process attributes of the kernels: set to the family's bound (64 frames, head dim 128), never from this shape
+    if (rc == PD_OK) rc = pd_set_lds(pd_tr_attn_kernel, pd_tr_attn_lds(PD_TR_MAX_N, PD_TR_MAX_HD));
+    if (rc == PD_OK) rc = pd_set_lds(pd_tr_attn_bwd_kernel, pd_tr_attn_bwd_lds(PD_TR_MAX_N, PD_TR_MAX_HD));
+    if (rc == PD_OK && hipDeviceSynchronize() != hipSuccess) rc = PD_ERR_HIP;
+    if (rc != PD_OK) {
+        if (rc == PD_ERR_HIP) pd_set_error("pd_trainer_create: a HIP call failed: %s", hipGetErrorString(hipGetLastError()));
+        delete tr;
+        return rc;
+    }
+    *out = tr;
+    return PD_OK;
+}
+
+extern "C" void pd_trainer_destroy(pd_trainer *tr) { delete tr; }
+
+static int tr_weights_match(const pd_trainer *tr, const pd_weights *w, const char *who) {
+    if (!w) {
+        pd_set_error("%s: NULL weights", who);
+        return PD_ERR_INVALID_ARG;
+    }
+    const int pivot = (w->reserved & PD_WEIGHTS_NO_PIVOT) ? 0 : 1, px0 = (w->reserved & PD_WEIGHTS_PRED_X0) ? 1 : 0;
+    if (w->d_model != tr->d || w->nhead != tr->nhead || w->dim_ff != tr->ff || w->num_layers != tr->layers || w->z_dim != tr->z ||
+        w->mlp_hidden != tr->hid || w->timesteps != tr->timesteps || pivot != tr->pivot || px0 != tr->pred_x0 || (w->reserved & PD_WEIGHTS_POST_NORM)) {
+        pd_set_error("%s: the weights' shape fields / flags differ from the shape this trainer was created for", who);
+        return PD_ERR_INVALID_ARG;
+    }
+    bool ok = w->time_w0 && w->time_b0 && w->time_w2 && w->time_b2 && w->first_w && w->first_b && w->last0_w && w->last0_b && w->last_ln_w &&
+              w->last_ln_b && w->last3_w && w->last3_b;
+    for (int l = 0; l < tr->layers && ok; ++l) {
+        const pd_layer_weights &L = w->layers[l];
+        ok = L.norm1_w && L.norm1_b && L.in_proj_w && L.in_proj_b && L.out_proj_w && L.out_proj_b && L.norm2_w && L.norm2_b && L.linear1_w &&
+             L.linear1_b && L.linear2_w && L.linear2_b;
+    }
+    if (!ok) {
+        pd_set_error("%s: a weight pointer is NULL", who);
+        return PD_ERR_INVALID_ARG;
+    }
+    return PD_OK;
+}
+
+extern "C" int pd_train_forward(pd_trainer *tr, const pd_weights *w, const float *x_start, const float *z, const int64_t *t_seq,
+                                const float *noise, int B, int N, int loss_type, float *loss_out, float *x0_pred_out, float *xt_out,
+                                float *model_out, void *stream) {
+    if (!tr) {
+        pd_set_error("pd_train_forward: NULL trainer");
+        return PD_ERR_INVALID_ARG;
+    }
+    if (!x_start || !z || !t_seq || !noise || !loss_out || B < 1 || N < 1 || B > tr->max_B || N > tr->max_N || (loss_type != 1 && loss_type != 2)) {
+        pd_set_error("pd_train_forward: invalid arguments (B=%d N=%d loss_type=%d; max_B=%d max_N=%d; x_start, z, t_seq, noise and loss_out must not be NULL)",
+                     B, N, loss_type, tr->max_B, tr->max_N);
+        return PD_ERR_INVALID_ARG;
+    }
+    if (N > PD_TR_MAX_N) {
+        pd_set_error("pd_train_forward: N=%d exceeds the trainer's limit of %d frames per sequence (the attention backward holds a sequence in LDS)", N, PD_TR_MAX_N);
+        return PD_ERR_UNSUPPORTED;
+    }
+    PD_TRY(tr_weights_match(tr, w, "pd_train_forward"));
+    if (x0_pred_out && !tr->pred_x0 && !tr->c_recip) {
+        pd_set_error("pd_train_forward: x0_pred_out under pred_noise needs sqrt_recip / sqrt_recipm1_alphas_cumprod at pd_trainer_create");
+        return PD_ERR_STATE;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const int M = B * N, d = tr->d, rb = (M + 3) / 4;
+    tr->pend_B = tr->pend_N = 0;
+    float *xt = tr->xt;
+    hipLaunchKernelGGL(pd_tr_q_sample_kernel, dim3((M * 9 + 255) / 256), dim3(256), 0, s, x_start, noise, t_seq, tr->qa, tr->qb, M, N, tr->timesteps, xt,
+                       tr->t_b, tr->d_err);
+    hipLaunchKernelGGL(pd_tr_time_kernel, dim3(B), dim3(128), 0, s, tr->t_b, w->time_w0, w->time_b0, w->time_w2, w->time_b2, tr->t_emb256, tr->t_a0,
+                       tr->t_sact, tr->t_emb);
+    {
+        const size_t total = (size_t)M * tr->Kf;
+        hipLaunchKernelGGL(pd_tr_embed_kernel, dim3((unsigned)std::min<size_t>((total + 255) / 256, 4096)), dim3(256), 0, s, xt, z, tr->t_emb, M, N, tr->z,
+                           tr->pivot, tr->Kf, tr->emb);
+    }
+    tr_linear(tr->emb, w->first_w, w->first_b, tr->hres[0], M, d, tr->Kf, 0, nullptr, s);
+    const float scale = 1.0f / sqrtf((float)tr->hd);
+    for (int l = 0; l < tr->layers; ++l) {
+        const pd_layer_weights &W = w->layers[l];
+        const PdTrLayerStash &S = tr->L[l];
+        float *h0 = tr->hres[2 * l], *h1 = tr->hres[2 * l + 1], *h2 = tr->hres[2 * l + 2];
+        hipLaunchKernelGGL(pd_tr_ln_kernel, dim3(rb), dim3(256), 0, s, h0, tr->hn, W.norm1_w, W.norm1_b, M, d, S.stats1);
+        tr_linear(tr->hn, W.in_proj_w, W.in_proj_b, S.qkv, M, 3 * d, d, 0, nullptr, s);
+        hipLaunchKernelGGL(pd_tr_attn_kernel, dim3(B * tr->nhead), dim3(256), pd_tr_attn_lds(N, tr->hd), s, S.qkv, S.ctx, N, tr->nhead, tr->hd, d, scale);
+        tr_linear(S.ctx, W.out_proj_w, W.out_proj_b, h1, M, d, d, 0, h0, s);
+        hipLaunchKernelGGL(pd_tr_ln_kernel, dim3(rb), dim3(256), 0, s, h1, tr->hn, W.norm2_w, W.norm2_b, M, d, S.stats2);
+        tr_linear(tr->hn, W.linear1_w, W.linear1_b, S.ffa, M, tr->ff, d, 1, nullptr, s);
+        tr_linear(S.ffa, W.linear2_w, W.linear2_b, h2, M, d, tr->ff, 0, h1, s);
+    }
+    tr_linear(tr->hres[2 * tr->layers], w->last0_w, w->last0_b, tr->hid_pre, M, tr->hid, d, 0, nullptr, s);
+    PdTrTail ta;
+    memset(&ta, 0, sizeof(ta));
+    ta.hid = tr->hid_pre; ta.lnw = w->last_ln_w; ta.lnb = w->last_ln_b; ta.w3 = w->last3_w; ta.b3 = w->last3_b;
+    ta.xt = xt; ta.target = tr->pred_x0 ? x_start : noise; ta.t_b = tr->t_b; ta.c_recip = tr->c_recip; ta.c_recipm1 = tr->c_recipm1;
+    ta.loss_out = loss_out; ta.x0_out = x0_pred_out; ta.model_out = model_out;
+    ta.stats = tr->hid_stats; ta.hid_post = tr->hid_post; ta.dl = tr->dl;
+    ta.M = M; ta.H = tr->hid; ta.n_frames = N; ta.pred_x0 = tr->pred_x0; ta.loss_type = loss_type;
+    hipLaunchKernelGGL(pd_tr_tail_kernel, dim3(rb), dim3(256), 0, s, ta);
+    if (xt_out) PD_HIP_CHECK(hipMemcpyAsync(xt_out, xt, (size_t)M * 9 * sizeof(float), hipMemcpyDeviceToDevice, s));
+    PD_HIP_CHECK(hipGetLastError());
+    tr->pend_B = tr->last_B = B;
+    tr->pend_N = tr->last_N = N;
+    return PD_OK;
+}
+
+extern "C" int pd_train_backward(pd_trainer *tr, const pd_weights *w, const float *g_loss, const pd_weight_grads *grads, float *dz_out,
+                                 void *stream) {
+    if (!tr || !g_loss || !grads) {
+        pd_set_error("pd_train_backward: NULL trainer, g_loss or grads");
+        return PD_ERR_INVALID_ARG;
+    }
+    if (tr->pend_B < 1 || tr->pend_N < 1) {
+        pd_set_error("pd_train_backward: no forward is pending (pd_train_forward fills the stash that one backward consumes)");
+        return PD_ERR_STATE;
+    }
+    PD_TRY(tr_weights_match(tr, w, "pd_train_backward"));
+    hipStream_t s = (hipStream_t)stream;
+    const int B = tr->pend_B, N = tr->pend_N, M = B * N, d = tr->d, ff = tr->ff, hid = tr->hid, rb = (M + 3) / 4, Lc = tr->layers;
+    tr->pend_B = tr->pend_N = 0;
+    // tail: loss derivative -> _last.3 -> ReLU mask -> LayerNorm(hidden) backward
+    PdTrTailBwd tb;
+    memset(&tb, 0, sizeof(tb));
+    tb.g_loss = g_loss; tb.dl = tr->dl; tb.w3 = w->last3_w; tb.lnw = w->last_ln_w; tb.hid = tr->hid_pre; tb.hid_post = tr->hid_post; tb.stats = tr->hid_stats;
+    tb.gout = tr->gout; tb.dy = tr->dy_hid; tb.dhid = tr->dhid; tb.M = M; tb.H = hid;
+    hipLaunchKernelGGL(pd_tr_tail_bwd_kernel, dim3(rb), dim3(256), 0, s, tb);
+    tr_wgrad(tr, tr->gout, tr->hid_post, grads->last3_w, grads->last3_b, M, 9, hid, s);
+    tr_ln_param_grads(tr, tr->dy_hid, tr->hid_pre, tr->hid_stats, grads->last_ln_w, grads->last_ln_b, M, hid, s);
+    tr_wgrad(tr, tr->dhid, tr->hres[2 * Lc], grads->last0_w, grads->last0_b, M, hid, d, s);
+    tr_dgrad(tr->dhid, w->last0_w, d, 0, tr->dres, M, hid, d, nullptr, 0, false, s);
+    const float scale = 1.0f / sqrtf((float)tr->hd);
+    for (int l = Lc - 1; l >= 0; --l) {
+        const pd_layer_weights &W = w->layers[l];
+        const pd_layer_grads &G = grads->layers[l];
+        const PdTrLayerStash &S = tr->L[l];
+        const float *h0 = tr->hres[2 * l], *h1 = tr->hres[2 * l + 1];
+        // feed-forward sublayer: dres is the gradient of linear2's output
+        tr_wgrad(tr, tr->dres, S.ffa, G.linear2_w, G.linear2_b, M, d, ff, s);
+        tr_dgrad(tr->dres, W.linear2_w, ff, 0, tr->dff, M, d, ff, S.ffa, 1, false, s);
+        if (G.linear1_w) hipLaunchKernelGGL(pd_tr_ln_kernel, dim3(rb), dim3(256), 0, s, h1, tr->hn, W.norm2_w, W.norm2_b, M, d, S.stats2);
+        tr_wgrad(tr, tr->dff, tr->hn, G.linear1_w, G.linear1_b, M, ff, d, s);
+        tr_dgrad(tr->dff, W.linear1_w, d, 0, tr->dhn, M, ff, d, nullptr, 0, false, s);
+        tr_ln_param_grads(tr, tr->dhn, h1, S.stats2, G.norm2_w, G.norm2_b, M, d, s);
+        hipLaunchKernelGGL(pd_tr_ln_bwd_kernel, dim3(rb), dim3(256), 0, s, tr->dhn, h1, S.stats2, W.norm2_w, M, d, tr->dres);
+        // attention sublayer: dres is the gradient of out_proj's output
+        tr_wgrad(tr, tr->dres, S.ctx, G.out_proj_w, G.out_proj_b, M, d, d, s);
+        tr_dgrad(tr->dres, W.out_proj_w, d, 0, tr->dhn, M, d, d, nullptr, 0, false, s);
+        hipLaunchKernelGGL(pd_tr_attn_bwd_kernel, dim3(B * tr->nhead), dim3(256), pd_tr_attn_bwd_lds(N, tr->hd), s, S.qkv, tr->dhn, tr->dqkv, N, tr->nhead,
+                           tr->hd, d, scale);
+        if (G.in_proj_w) hipLaunchKernelGGL(pd_tr_ln_kernel, dim3(rb), dim3(256), 0, s, h0, tr->hn, W.norm1_w, W.norm1_b, M, d, S.stats1);
+        tr_wgrad(tr, tr->dqkv, tr->hn, G.in_proj_w, G.in_proj_b, M, 3 * d, d, s);
+        tr_dgrad(tr->dqkv, W.in_proj_w, d, 0, tr->dhn, M, 3 * d, d, nullptr, 0, false, s);
+        tr_ln_param_grads(tr, tr->dhn, h0, S.stats1, G.norm1_w, G.norm1_b, M, d, s);
+        hipLaunchKernelGGL(pd_tr_ln_bwd_kernel, dim3(rb), dim3(256), 0, s, tr->dhn, h0, S.stats1, W.norm1_w, M, d, tr->dres);
+    }
+    // head of the network: dres is the gradient of _first's output
+    tr_wgrad(tr, tr->dres, tr->emb, grads->first_w, grads->first_b, M, d, tr->Kf, s);
+    if (dz_out) tr_dgrad(tr->dres, w->first_w, tr->Kf, PD_TR_FIRST_FIXED, dz_out, M, d, tr->z, nullptr, 0, false, s);
+    if (grads->time_w0 || grads->time_b0 || grads->time_w2 || grads->time_b2) {
+        tr_dgrad(tr->dres, w->first_w, tr->Kf, 189, tr->demb_t, M, d, 128, nullptr, 0, false, s);
+        hipLaunchKernelGGL(pd_tr_tsum_kernel, dim3(B), dim3(128), 0, s, tr->demb_t, N, tr->dtemb);
+        tr_wgrad(tr, tr->dtemb, tr->t_sact, grads->time_w2, grads->time_b2, B, 128, 128, s);
+        if (grads->time_w0 || grads->time_b0) {
+            tr_dgrad(tr->dtemb, w->time_w2, 128, 0, tr->dts, B, 128, 128, tr->t_a0, 2, false, s);
+            tr_wgrad(tr, tr->dts, tr->t_emb256, grads->time_w0, grads->time_b0, B, 128, 256, s);
+        }
+    }
+    PD_HIP_CHECK(hipGetLastError());
+    return PD_OK;
+}
+
+extern "C" int pd_train_debug_relu(pd_trainer *tr, int layer, float *dst, long long n_floats, void *stream) {
+    if (!tr || !dst || layer < 0 || layer > tr->layers) {
+        pd_set_error("pd_train_debug_relu: NULL trainer / dst, or layer outside [0, num_layers]");
+        return PD_ERR_INVALID_ARG;
+    }
+    if (tr->last_B < 1) {
+        pd_set_error("pd_train_debug_relu: no forward has run on this trainer");
+        return PD_ERR_STATE;
+    }
+    const long long M = (long long)tr->last_B * tr->last_N;
+    const long long want = M * (layer < tr->layers ? tr->ff : tr->hid);
+    if (n_floats != want) {
+        pd_set_error("pd_train_debug_relu: n_floats=%lld, the last forward stashed %lld values there", n_floats, want);
+        return PD_ERR_INVALID_ARG;
+    }
+    const float *src = layer < tr->layers ? tr->L[layer].ffa : tr->hid_post;
+    PD_HIP_CHECK(hipMemcpyAsync(dst, src, (size_t)want * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return PD_OK;
+}
+
+extern "C" int pd_trainer_check_async(pd_trainer *tr) {
+    if (!tr) {
+        pd_set_error("pd_trainer_check_async: NULL trainer");
+        return PD_ERR_INVALID_ARG;
+    }
+    unsigned int word = 0;
+    PD_HIP_CHECK(hipDeviceSynchronize());
+    PD_HIP_CHECK(hipMemcpy(&word, tr->d_err, sizeof(word), hipMemcpyDeviceToHost));
+    if (!word) return PD_OK;
+    PD_HIP_CHECK(hipMemset(tr->d_err, 0, sizeof(word)));
+    pd_set_error("pd_trainer_check_async: a timestep outside [0, %d) was clamped by pd_train_forward (error word %u)", tr->timesteps, word);
+    return PD_ERR_STATE;
+}

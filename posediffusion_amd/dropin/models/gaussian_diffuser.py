@@ -4,10 +4,13 @@ Same constructor, same 13 persistent buffers (checkpoint keys `diffuser.betas` .
 ``sample(shape, z, cond_fn=None, cond_start_step=0) -> (pose [B,N,9], process [T+1,B,N,9])``.
 The loop itself -- 100 denoiser evaluations, posterior updates and (when cond_fn is the shipped
 GGS partial) the 7000 guided iterations -- runs as one hipGraph replay of hand-written kernels.
-The training branch (`forward` / `p_losses`, :308-332) runs its FORWARD half on the engine, one pass of the denoiser for the whole
-batch of per-sequence timesteps: the diffusion loss of a checkpoint on a batch.  The returned tensors carry no grad (backward and the
-optimiser are out of scope), and the network is evaluated as under ``model.eval()``: the reference under ``model.train()`` applies
-dropout 0.1, which the engine does not reproduce."""
+The training branch (`forward` / `p_losses`, :308-332) runs on the engine, one pass of the denoiser for the whole batch of per-sequence
+timesteps.  By default (``engine_grad = False``) it is the FORWARD half only: the diffusion loss of a checkpoint on a batch, no grad.
+With ``engine_grad = True`` and grad mode on, the loss comes from the trainer (posediffusion_amd/train.py, include/pd_engine_train.h)
+and is attached to the denoiser's parameters (and to z when it requires grad): ``loss.mean().backward()`` runs the hand-written
+backward, PyTorch keeps the optimiser.  Either way the network is evaluated as under ``model.eval()``: the reference under
+``model.train()`` applies dropout, which the engine does not reproduce -- so engine training is dropout-0 training, and the opt-in
+refuses a diffuser in ``.train()`` mode whose encoder layers have dropout p > 0."""
 import os
 from collections import namedtuple
 
@@ -46,6 +49,8 @@ class GaussianDiffusion(nn.Module):
         self.last_ggs_stats = None
         self.ggs_max_frames = host.GGS_MAX_FRAMES      # frames guided sampling admits; raise it (<= 256) to guide longer sequences: the engine
         #                                                then holds a larger exchange region (PD_OPT_GGS_MAX_FRAMES, include/pd_engine.h)
+        self.engine_grad = False                       # True: with grad mode on, p_losses / forward return a loss that is differentiable with respect to the
+        #                                                denoiser's parameters and z (the trainer's hand-written backward); the default stays forward-only
         self.ggs_long_pair_items = False               # True: above 64 frames, take frame pairs of more than 512 matches (PD_OPT_GGS_LONG_PAIR_ITEMS)
 
     # ---- schedule helpers (:190-216): elementwise on the buffers, same names and argument order; the sampler itself has these
@@ -165,10 +170,37 @@ class GaussianDiffusion(nn.Module):
         return self.p_sample_loop(shape, z=z, cond_fn=cond_fn, cond_start_step=cond_start_step, n_frames=n_frames)
 
     # ---- training branch, forward half (:308-332): q_sample, the denoiser and the loss as one pass on the engine ----------------------
-    @torch.no_grad()
+    def _check_no_dropout(self):
+        """Engine training is dropout-0 training: where the reference would apply dropout and the engine does not, refuse."""
+        if not self.training:
+            return
+        ps = [m.p for m in self.model._trunk.modules() if isinstance(m, nn.Dropout)]
+        ps += [float(getattr(l.self_attn, "dropout", 0.0)) for l in self.model._trunk.layers]
+        if any(p > 0 for p in ps):
+            raise RuntimeError(f"engine_grad: the diffuser is in .train() mode and its encoder layers have dropout p = {max(ps)}: the reference "
+                               "would apply dropout there and the engine does not (no-dropout rule). Set TRANSFORMER.dropout = 0 or call .eval()")
+
+    def _p_losses_grad(self, x_start, t, z, noise):
+        """p_losses through the trainer: ``loss`` carries grad with respect to the denoiser's parameters and z."""
+        from posediffusion_amd.train import p_losses_with_grad
+        if self.loss_type not in ("l1", "l2"):
+            raise ValueError(f"invalid loss type {self.loss_type}")
+        self._check_no_dropout()
+        noise = torch.randn_like(x_start) if noise is None else noise              # :309
+        B, N, _ = x_start.shape
+        tr = host.get_trainer(self.model, self, B, N)
+        out = p_losses_with_grad(tr, self.model, x_start, z, t, noise, self.loss_type)
+        return {"loss": out["loss"], "noise": noise, "x_0_pred": out["x_0_pred"], "x_t": out["x_t"], "t": t}
+
     def p_losses(self, x_start, t, z=None, noise=None):
         """``{"loss", "noise", "x_0_pred", "x_t", "t"}`` as the reference returns them; loss elementwise (reduction "none").
-        Eval-mode forward, no grad (see the module docstring)."""
+        Eval-mode forward; no grad unless ``engine_grad`` is set and grad mode is on (see the module docstring)."""
+        if z is not None and getattr(self, "engine_grad", False) and torch.is_grad_enabled():
+            return self._p_losses_grad(x_start, t, z, noise)
+        return self._p_losses_forward_only(x_start, t, z=z, noise=noise)
+
+    @torch.no_grad()
+    def _p_losses_forward_only(self, x_start, t, z=None, noise=None):
         if z is None:
             raise NotImplementedError("the denoiser cannot run unconditionally: p_losses needs the image features z")
         if self.loss_type not in ("l1", "l2"):

@@ -78,6 +78,30 @@ def get_engine(denoiser: torch.nn.Module, diffuser: Optional[torch.nn.Module], B
     return eng
 
 
+def get_trainer(denoiser: torch.nn.Module, diffuser: torch.nn.Module, B: int, N: int):
+    """``PoseTrainer`` (posediffusion_amd/train.py) for these live modules.  It reads the parameters where they are at every call, so it
+    is cached on shape, device, objective and capacity -- NOT on parameter versions: an optimiser step keeps it.  The capacity never
+    shrinks."""
+    from .train import PoseTrainer, shape_from_modules
+    dev = next(denoiser.parameters()).device
+    if dev.type != "cuda":
+        raise RuntimeError("the training branch of posediffusion_amd runs only on an AMD GPU "
+                           f"(model is on {dev}); move the model with .to('cuda'). There is no CPU fallback.")
+    shape = shape_from_modules(denoiser, diffuser)
+    key = (tuple(sorted(shape.items())), str(dev), int(diffuser.num_timesteps))
+    cache = denoiser.__dict__.setdefault("_pd_trainer_cache", {})
+    ent = cache.get("t")
+    if ent is not None and ent[0] == key and ent[1].max_B >= B and ent[1].max_N >= N:
+        return ent[1]
+    if ent is not None:
+        if ent[0] == key:
+            B, N = max(B, ent[1].max_B), max(N, ent[1].max_N)     # never shrink capacity
+        ent[1].close()
+    tr = PoseTrainer(shape, {n: b for n, b in diffuser.named_buffers(recurse=False)}, max_B=max(B, 1), max_N=max(N, 1), device=dev)
+    cache["t"] = (key, tr)
+    return tr
+
+
 def _raise_ggs_limit(eng: PoseEngine, ggs_max_frames: int, ggs_long_pair_items: bool = False):
     want = min(int(ggs_max_frames), eng.max_N)
     if want > GGS_MAX_FRAMES and want > eng.ggs_max_frames:
