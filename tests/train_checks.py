@@ -5,8 +5,8 @@ which every ReLU is ``a * mask`` and |d| is ``d * s`` with ``mask`` and ``s`` gi
 Why: the gradient is discontinuous at every ReLU threshold and at d = 0 under l1 -- one activation that lands on the other side of zero
 in fp32 than in fp64 changes a whole weight-gradient row (the reference's own fp32 autograd is 3e-2 from fp64 at 800 token rows through
 5 flipped activations of 6.6 million).  With the masks forced the function is smooth and a 4 x "own fp32 distance" bound is meaningful.
-Gradients come from torch.autograd.grad.  Shared by tests/test_train_checks_cpu.py, tests/test_gpu_train_grad.py and
-tools/make_p_losses_grad_golden.py."""
+Gradients come from torch.autograd.grad.  Shared by tests/test_train_checks_cpu.py, tests/test_gpu_train_grad.py,
+tests/test_gpu_train_grad_edges.py and tools/make_p_losses_grad_golden.py."""
 from __future__ import annotations
 
 import math
@@ -40,9 +40,10 @@ def _relu(a: torch.Tensor, mask: Optional[torch.Tensor], pre: List[torch.Tensor]
 
 def denoiser_forward(sd: Dict[str, torch.Tensor], net: Net, x: torch.Tensor, t: torch.Tensor, z: torch.Tensor, masks=None):
     """-> (model_out [B, N, 9], info) with info["pre"] = the L + 1 ReLU inputs ([B, N, ff] per layer, then _last's [B, N, hidden]) and
-    info["masks"] = the boolean masks used (``masks`` when given, else ``pre > 0``)."""
+    info["masks"] = the boolean masks used (``masks`` when given, else ``pre > 0``); info["pmax"] = per layer the largest probability
+    of every softmax row ([B, nhead, N]), how far from uniform (1 / N) the attention is."""
     B, N, _ = x.shape
-    pre, used = [], []
+    pre, used, pmax = [], [], []
     t_emb = O.timestep_embedding(t, sd)[:, None, :].expand(-1, N, -1)
     parts = [O.harmonic_embedding(x), t_emb, z]
     if net.pivot:
@@ -58,6 +59,7 @@ def denoiser_forward(sd: Dict[str, torch.Tensor], net: Net, x: torch.Tensor, t: 
         qkv = a @ sd[p + "self_attn.in_proj_weight"].T + sd[p + "self_attn.in_proj_bias"]
         q, k, v = (u.reshape(B, N, net.nhead, dh).transpose(1, 2) for u in qkv.split(d, dim=-1))
         att = torch.softmax((q / math.sqrt(dh)) @ k.transpose(-1, -2), dim=-1)
+        pmax.append(att.detach().max(dim=-1).values)
         ctx = (att @ v).transpose(1, 2).reshape(B, N, d)
         h = h + (ctx @ sd[p + "self_attn.out_proj.weight"].T + sd[p + "self_attn.out_proj.bias"])
         a = O._layer_norm(h, sd[p + "norm2.weight"], sd[p + "norm2.bias"])
@@ -65,7 +67,7 @@ def denoiser_forward(sd: Dict[str, torch.Tensor], net: Net, x: torch.Tensor, t: 
         h = h + (a @ sd[p + "linear2.weight"].T + sd[p + "linear2.bias"])
     a = O._layer_norm(h @ sd["_last.0.weight"].T + sd["_last.0.bias"], sd["_last.1.weight"], sd["_last.1.bias"])
     a = _relu(a, None if masks is None else masks[net.layers], pre, used)
-    return a @ sd["_last.3.weight"].T + sd["_last.3.bias"], {"pre": pre, "masks": used}
+    return a @ sd["_last.3.weight"].T + sd["_last.3.bias"], {"pre": pre, "masks": used, "pmax": pmax}
 
 
 def q_sample(x_start, noise, t, tables):
@@ -101,6 +103,17 @@ def loss_and_grads(sd: Dict[str, torch.Tensor], net: Net, inp: Dict[str, torch.T
             "masks": info["masks"], "signs": s}
 
 
+def draw_g_loss(B: int, N: int, seed: int = 0) -> torch.Tensor:
+    """A non-uniform upstream gradient [B, N, 9] (a masked, per-frame-weighted loss): randn / (B N 9), so mixed signs, times a per-frame
+    factor that spans three decades over the B N frames; sequence 0 entirely and frame 1 of every sequence are zero."""
+    g = torch.Generator().manual_seed(7700 + 100 * B + N + seed)
+    w = (10.0 ** torch.linspace(-3.0, 0.0, B * N))[torch.randperm(B * N, generator=g)].reshape(B, N, 1)
+    out = torch.randn(B, N, 9, generator=g) / (B * N * 9) * w
+    out[0] = 0.0
+    out[:, 1] = 0.0
+    return out
+
+
 def grad_dist(g, g64) -> float:
     """max|g - g64| / max|g64| of one tensor (0 when both are identically zero)."""
     g, g64 = torch.as_tensor(g).detach().cpu().double(), torch.as_tensor(g64).detach().cpu().double()
@@ -109,6 +122,49 @@ def grad_dist(g, g64) -> float:
     if den == 0.0:
         return 0.0 if num == 0.0 else float("inf")
     return num / den
+
+
+FIRST_FIXED_COLS = (("harmonic", 0, 180), ("x", 180, 189), ("t_emb", 189, 317))       # _first's columns before z (models/denoiser.py:56-68)
+
+
+def grad_blocks(name: str, g: torch.Tensor, d_model: int, z_dim: int) -> Dict[str, torch.Tensor]:
+    """The sub-blocks of the gradient ``g`` of parameter ``name`` that come from different parts of the backward and differ in
+    magnitude, so that a whole-tensor maximum norm is decided by one of them: the q, k and v row blocks of ``in_proj_weight`` /
+    ``in_proj_bias`` (q and k come from the softmax backward, v from P^T dO and usually dominates), and the column blocks of
+    ``_first.weight`` (harmonic, x, t_emb, z and, when the tensor has it, the pivot column).  {} for every other tensor."""
+    if name.endswith(("self_attn.in_proj_weight", "self_attn.in_proj_bias")):
+        assert g.shape[0] == 3 * d_model, (name, tuple(g.shape))
+        return {"q": g[:d_model], "k": g[d_model:2 * d_model], "v": g[2 * d_model:]}
+    if name == "_first.weight":
+        z0 = FIRST_FIXED_COLS[-1][2]
+        assert g.shape[1] in (z0 + z_dim, z0 + z_dim + 1), (name, tuple(g.shape))
+        out = {b: g[:, lo:hi] for b, lo, hi in FIRST_FIXED_COLS}
+        out["z"] = g[:, z0:z0 + z_dim]
+        if g.shape[1] > z0 + z_dim:
+            out["pivot"] = g[:, z0 + z_dim:]
+        return out
+    return {}
+
+
+def block_dists(name: str, g, g_own, g64, d_model: int, z_dim: int):
+    """[(block, distance of g, distance of g_own, zero)] per block of `grad_blocks`, each distance against that block's OWN float64
+    maximum (`grad_dist`); ``zero`` = the float64 block is identically zero."""
+    b, bo, b64 = (grad_blocks(name, torch.as_tensor(t).detach().cpu(), d_model, z_dim) for t in (g, g_own, g64))
+    return [(k, grad_dist(b[k], b64[k]), grad_dist(bo[k], b64[k]), b64[k].abs().max().item() == 0.0) for k in b64]
+
+
+def block_misses(name: str, g, g_own, g64, d_model: int, z_dim: int, margin: float = 4.0, margins=None):
+    """The blocks of `block_dists` whose distance exceeds ``margin`` x own (``margins``: {"name[block]": recorded margin}), or that are
+    not exactly zero where float64's is.  The k block of ``in_proj_bias`` is left out: a key bias shifts every score of a softmax row
+    equally, so its gradient is mathematically zero and float64 holds only its own rounding there (1e-17 of the tensor's maximum)."""
+    out = []
+    for k, e, own, zero in block_dists(name, g, g_own, g64, d_model, z_dim):
+        if k == "k" and name.endswith("in_proj_bias"):
+            continue
+        m = (margins or {}).get(f"{name}[{k}]", margin)
+        if (zero and e != 0.0) or (not zero and e > m * own):
+            out.append((f"{name}[{k}]", e, own))
+    return out
 
 
 # ------------------------------------------------------------------------------------------------ tests/golden/p_losses_grad.npz
