@@ -9,8 +9,9 @@
  *   - it keeps NO weight copy: every call reads the caller's LIVE tensors (DEVICE pointers, PyTorch layout [out, in]) through the
  *     pd_weights it is handed, so an optimiser step needs no rebuild and no repacking;
  *   - it owns one activation stash sized at creation for max_B x max_N token rows, and the two q_sample tables;
- *   - exact fp32 everywhere (v_mfma_f32_32x32x2_f32), eval-mode function (no dropout), pre-norm only, N <= 64 frames, head dim <= 128,
- *     pivot column on or off, both objectives, both loss types;
+ *   - exact fp32 everywhere (v_mfma_f32_32x32x2_f32), pre-norm only, N <= 64 frames, head dim <= 128, pivot column on or off, both
+ *     objectives, both loss types; pd_train_forward is the eval-mode function, pd_train_forward_dropout the .train()-mode one with the
+ *     encoder layers' dropout (masks from a counter-based generator, recomputed by the backward, never stored);
  *   - no float atomics in any reduction: gradients are bitwise reproducible and do not depend on the trainer's capacity (every
  *     reduction over token rows is chunked by a function of M = B x N alone and its partial sums are added in chunk order);
  *   - the image backbone is not differentiated: dz is handed back for whoever owns z.
@@ -62,15 +63,39 @@ int pd_train_forward(pd_trainer *tr, const pd_weights *w, const float *x_start, 
                      const float *noise, int B, int N, int loss_type,
                      float *loss_out, float *x0_pred_out, float *xt_out, float *model_out, void *stream);
 
+/* pd_train_forward with dropout of probability p at the sites in `sites` of every encoder layer -- nn.TransformerEncoderLayer's four:
+ *   PD_DROP_ATTN    the attention probabilities, after the softmax and before P V; row (b nhead + h) N + i, column = key j
+ *   PD_DROP_RESID1  dropout1, on out_proj(ctx) + bias before the residual add;       row = token row m, column < d_model
+ *   PD_DROP_FF      the feed-forward dropout, after linear1's ReLU;                   row m, column < dim_ff
+ *   PD_DROP_RESID2  dropout2, on linear2(..) + bias before the residual add;          row m, column < d_model
+ * (_last and the time embedding have none in the reference).  The element at (row r, column c) of site s (0 .. 3 in the order above) of
+ * layer l is KEPT iff word r & 3 of philox4x32_10(counter = (r >> 2, c, 4 l + s, step), key = (seed & 0xffffffff, seed >> 32)) is
+ * >= floor(p 2^32); kept values are multiplied by the fp32 value 1 / (1 - p).  The mapping depends on (B, N) and the network shape
+ * alone, never on the trainer's capacity.  The trainer remembers (p, sites, seed, step) with the pending stash: pd_train_backward
+ * differentiates THIS function, recomputing every mask.  The stashed FF activations are post-dropout (what linear2 read).
+ * p == 0 or sites == 0 is pd_train_forward itself: same launches, same bits.  p outside [0, 1) or NaN, or a bit of `sites` outside
+ * PD_DROP_ALL: PD_ERR_INVALID_ARG naming the argument, before anything is launched. */
+#define PD_DROP_ATTN 1u
+#define PD_DROP_RESID1 2u
+#define PD_DROP_FF 4u
+#define PD_DROP_RESID2 8u
+#define PD_DROP_ALL 15u
+int pd_train_forward_dropout(pd_trainer *tr, const pd_weights *w, const float *x_start, const float *z, const int64_t *t_seq,
+                             const float *noise, int B, int N, int loss_type, float p, unsigned sites, uint64_t seed, uint32_t step,
+                             float *loss_out, float *x0_pred_out, float *xt_out, float *model_out, void *stream);
+
 /* With S = sum(g_loss * loss) over the [B, N, 9] elements: writes dS/dtheta for every non-NULL member of `grads` (an overwrite, in the
  * parameter's own layout; a NULL member's weight-gradient launch is not issued) and dS/dz [B, N, z_dim] when dz_out is non-NULL.
  * Loss derivative: sign(d) with sign(0) = 0 (l1), 2 d (l2), d = model_out - target; x_0_pred carries no gradient.
+ * After pd_train_forward_dropout it differentiates that call's function (same masks).
  * Consumes the stash: PD_ERR_STATE when no forward is pending.  `w` must point to the same unmodified tensors as the forward's. */
 int pd_train_backward(pd_trainer *tr, const pd_weights *w, const float *g_loss, const pd_weight_grads *grads, float *dz_out,
                       void *stream);
 
 /* The tests' window into the stash of the pending (or last) forward: layer < num_layers -> that layer's [B x N, dim_ff] post-ReLU FF
- * activations; layer == num_layers -> _last's [B x N, mlp_hidden] post-ReLU values.  n_floats must be exactly that size. */
+ * activations; layer == num_layers -> _last's [B x N, mlp_hidden] post-ReLU values.  n_floats must be exactly that size.  The stash is
+ * returned as it is: after pd_train_forward_dropout with PD_DROP_FF an encoder layer's values are POST-dropout (0 where dropped, times
+ * 1 / (1 - p) where kept). */
 int pd_train_debug_relu(pd_trainer *tr, int layer, float *dst, long long n_floats, void *stream);
 
 /* Synchronises the device; PD_ERR_STATE if pd_train_forward met (and clamped) a timestep outside [0, timesteps) since the last check. */

@@ -82,6 +82,7 @@ PD_OPT_DENOISER_FUSED_ATTN = 5  # in_proj + attention as one kernel, Q / K / V i
 PD_OPT_DENOISER_LONG_ATTN = 6   # 1: the key-tiled attention kernel of sequences above 64 frames for every N (default 0; comparison / testing)
 PD_OPT_GGS_MAX_FRAMES = 7       # frames GGS admits: 64 (default) or a value in (64, max_N]; reallocates the exchange region, synchronous
 PD_OPT_GGS_LONG_PAIR_ITEMS = 8  # 0 (default) / 1: above 64 frames a frame pair may hold more than 512 matches (pd_ggs_longm_kernel)
+PD_DROP_ATTN, PD_DROP_RESID1, PD_DROP_FF, PD_DROP_RESID2, PD_DROP_ALL = 1, 2, 4, 8, 15   # pd_train_forward_dropout's sites (include/pd_engine_train.h)
 PD_MATCH_HINT_ONE_ORDER = 1 << 30   # pd_match_hints.max_pairs flag: every frame pair in one order only (hloc's i < j pairs)
 
 
@@ -152,6 +153,8 @@ TRAIN_SIGNATURES = {
     "pd_trainer_create": (_i, [C.POINTER(pd_weights), _vp, _vp, _i, _i, C.POINTER(_vp)]),
     "pd_trainer_destroy": (None, [_vp]),
     "pd_train_forward": (_i, [_vp, C.POINTER(pd_weights), _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "pd_train_forward_dropout": (_i, [_vp, C.POINTER(pd_weights), _vp, _vp, _vp, _vp, _i, _i, _i, C.c_float, C.c_uint, C.c_uint64, C.c_uint32,
+                                      _vp, _vp, _vp, _vp, _vp]),
     "pd_train_backward": (_i, [_vp, C.POINTER(pd_weights), _vp, C.POINTER(pd_weight_grads), _vp, _vp]),
     "pd_train_debug_relu": (_i, [_vp, _i, _vp, C.c_longlong, _vp]),
     "pd_trainer_check_async": (_i, [_vp]),

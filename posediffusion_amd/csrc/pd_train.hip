@@ -10,6 +10,9 @@
 // The residual stream is never updated in place: hres[i] is the stream at sublayer input i (2 L + 1 arrays), which IS the stash.
 // Backward: tail -> _last.0 -> per layer in reverse { linear2, ReLU mask, linear1, LN2, out_proj, attention, in_proj, LN1 } -> _first
 //   (weight gradient over all columns, data gradient for the t_emb and z columns only) -> time embedding.
+// Dropout (pd_train_forward_dropout): the four sites of an encoder layer are masked in the epilogues of out_proj / linear1 / linear2 and
+// in the attention kernel; the backward recomputes every mask from (seed, step, p) and masks the residual-stream gradient into dres_m
+// before the weight, bias and data gradients of out_proj / linear2 read it.  A call without dropout launches the DROP = false kernels.
 #include "pd_train_kernels.h"
 #include "../../include/pd_engine_train.h"
 
@@ -35,6 +38,7 @@ struct pd_trainer {
     int *t_b = nullptr;                                  // [B]
     // scratch
     float *hn = nullptr, *dres = nullptr, *dhn = nullptr, *dff = nullptr, *dqkv = nullptr;
+    float *dres_m = nullptr;                             // [M, d] dres masked at site 1 / 3 (dropout backward)
     float *dy_hid = nullptr, *dhid = nullptr, *gout = nullptr, *demb_t = nullptr, *dtemb = nullptr, *dts = nullptr;
     float *ws = nullptr;                                 // split-reduction workspaces: weight-gradient partials [chunks][Nout x K] ...
     double *ws_col = nullptr;                            // ... and column-sum partials [2][chunks][C]
@@ -42,6 +46,8 @@ struct pd_trainer {
     unsigned int *d_err = nullptr;
     int pend_B = 0, pend_N = 0;                          // B, N of the pending forward (0: none)
     int last_B = 0, last_N = 0;                          // of the last forward (pd_train_debug_relu)
+    PdTrDrop pend_drop = {};                             // dropout of the pending forward (ctr2 / philox are set per site) ...
+    unsigned pend_sites = 0;                             // ... and its sites (0: none)
     PdDevAllocs mem{"pd_trainer_create"};
 };
 
@@ -55,24 +61,36 @@ static void pd_tr_chunks(int M, int *n_chunks, int *rows) {
     *n_chunks = (M + r - 1) / r;
 }
 
-static void tr_gemm_launch(const PdTrGemm &g, int nz, hipStream_t s) {
-    hipLaunchKernelGGL(pd_tr_gemm_kernel, dim3((g.J + 63) / 64, (g.I + 63) / 64, nz), dim3(256), 0, s, g);
+static void tr_gemm_launch(const PdTrGemm &g, int nz, hipStream_t s, const PdTrDrop *dr = nullptr) {
+    const dim3 grid((g.J + 63) / 64, (g.I + 63) / 64, nz);
+    if (dr) hipLaunchKernelGGL(pd_tr_gemm_kernel<true>, grid, dim3(256), 0, s, g, *dr);
+    else hipLaunchKernelGGL(pd_tr_gemm_kernel<false>, grid, dim3(256), 0, s, g, PdTrDrop{});
 }
 
-// Y[M, Nout] = X[M, K] W[Nout, K]^T + b (+ ReLU) (+ resid)
-static void tr_linear(const float *X, const float *W, const float *b, float *Y, int M, int Nout, int K, int relu, const float *resid, hipStream_t s) {
+// the dropout of the pending / running call at `site` (0 .. 3) of `layer`, or null when that site is off
+static const PdTrDrop *tr_site(const PdTrDrop &base, unsigned sites, int layer, int site, PdTrDrop *out) {
+    if (!(sites & (1u << site))) return nullptr;
+    *out = base;
+    out->ctr2 = 4u * (unsigned)layer + (unsigned)site;
+    out->philox = 1;
+    return out;
+}
+
+// Y[M, Nout] = X[M, K] W[Nout, K]^T + b (+ ReLU) (+ dropout `dr`) (+ resid)
+static void tr_linear(const float *X, const float *W, const float *b, float *Y, int M, int Nout, int K, int relu, const float *resid, hipStream_t s,
+                      const PdTrDrop *dr = nullptr) {
     PdTrGemm g;
     memset(&g, 0, sizeof(g));
     g.A = X; g.a_rs = K; g.a_cs = 1; g.a_rfast = 1;
     g.B = W; g.b_rs = 1; g.b_cs = K; g.b_rfast = 1;
     g.C = Y; g.ldc = Nout; g.bias = b; g.relu = relu; g.resid = resid; g.ldr = Nout;
     g.I = M; g.J = Nout; g.R = K; g.r_chunk = K;
-    tr_gemm_launch(g, 1, s);
+    tr_gemm_launch(g, 1, s, dr);
 }
 
 // dX[M, Kw] = dY[M, Nout] W[:, koff : koff + Kw] (W [Nout, ldw]), masked by aux (mode 1 / 2), written or accumulated into dX
 static void tr_dgrad(const float *dY, const float *W, int ldw, int koff, float *dX, int M, int Nout, int Kw, const float *aux, int mask_mode,
-                     bool accumulate, hipStream_t s) {
+                     bool accumulate, hipStream_t s, const PdTrDrop *dr = nullptr) {
     PdTrGemm g;
     memset(&g, 0, sizeof(g));
     g.A = dY; g.a_rs = Nout; g.a_cs = 1; g.a_rfast = 1;
@@ -83,7 +101,7 @@ static void tr_dgrad(const float *dY, const float *W, int ldw, int koff, float *
         g.ldr = Kw;
     }
     g.I = M; g.J = Kw; g.R = Nout; g.r_chunk = Nout;
-    tr_gemm_launch(g, 1, s);
+    tr_gemm_launch(g, 1, s, dr);
 }
 
 // dW[Nout, K] = sum_m dY[m, :]^T X[m, :] over the chunks of M, partials added in chunk order; db[Nout] = sum_m dY[m, :] likewise
@@ -175,7 +193,7 @@ extern "C" int pd_trainer_create(const pd_weights *shape, const float *sqrt_alph
     TR_A(tr->hid_pre, rows * tr->hid); TR_A(tr->hid_post, rows * tr->hid); TR_A(tr->hid_stats, rows * 2); TR_A(tr->dl, rows * 9);
     TR_A(tr->t_emb256, (size_t)max_B * 256); TR_A(tr->t_a0, (size_t)max_B * 128); TR_A(tr->t_sact, (size_t)max_B * 128); TR_A(tr->t_emb, (size_t)max_B * 128);
     TR_A(tr->t_b, (size_t)max_B);
-    TR_A(tr->hn, rows * d); TR_A(tr->dres, rows * d); TR_A(tr->dhn, rows * d); TR_A(tr->dff, rows * tr->ff); TR_A(tr->dqkv, rows * 3 * d);
+    TR_A(tr->hn, rows * d); TR_A(tr->dres, rows * d); TR_A(tr->dres_m, rows * d); TR_A(tr->dhn, rows * d); TR_A(tr->dff, rows * tr->ff); TR_A(tr->dqkv, rows * 3 * d);
     TR_A(tr->dy_hid, rows * tr->hid); TR_A(tr->dhid, rows * tr->hid); TR_A(tr->gout, rows * 9); TR_A(tr->demb_t, rows * 128);
     TR_A(tr->dtemb, (size_t)max_B * 128); TR_A(tr->dts, (size_t)max_B * 128);
     const size_t widest_w = std::max({(size_t)d * tr->Kf, (size_t)3 * d * d, (size_t)tr->ff * d, (size_t)tr->hid * d, (size_t)9 * tr->hid, (size_t)128 * 256});
@@ -193,8 +211,10 @@ extern "C" int pd_trainer_create(const pd_weights *shape, const float *sqrt_alph
             rc = PD_ERR_HIP;
     }
     // dynamic-LDS limits are per-process attributes of the kernels: set to the family's bound (64 frames, head dim 128), never from this shape
-    if (rc == PD_OK) rc = pd_set_lds(pd_tr_attn_kernel, pd_tr_attn_lds(PD_TR_MAX_N, PD_TR_MAX_HD));
-    if (rc == PD_OK) rc = pd_set_lds(pd_tr_attn_bwd_kernel, pd_tr_attn_bwd_lds(PD_TR_MAX_N, PD_TR_MAX_HD));
+    if (rc == PD_OK) rc = pd_set_lds(pd_tr_attn_kernel<false>, pd_tr_attn_lds(PD_TR_MAX_N, PD_TR_MAX_HD));
+    if (rc == PD_OK) rc = pd_set_lds(pd_tr_attn_kernel<true>, pd_tr_attn_lds(PD_TR_MAX_N, PD_TR_MAX_HD));
+    if (rc == PD_OK) rc = pd_set_lds(pd_tr_attn_bwd_kernel<false>, pd_tr_attn_bwd_lds(PD_TR_MAX_N, PD_TR_MAX_HD));
+    if (rc == PD_OK) rc = pd_set_lds(pd_tr_attn_bwd_kernel<true>, pd_tr_attn_bwd_lds(PD_TR_MAX_N, PD_TR_MAX_HD));
     if (rc == PD_OK && hipDeviceSynchronize() != hipSuccess) rc = PD_ERR_HIP;
     if (rc != PD_OK) {
         if (rc == PD_ERR_HIP) pd_set_error("pd_trainer_create: a HIP call failed: %s", hipGetErrorString(hipGetLastError()));
@@ -232,30 +252,29 @@ static int tr_weights_match(const pd_trainer *tr, const pd_weights *w, const cha
     return PD_OK;
 }
 
-extern "C" int pd_train_forward(pd_trainer *tr, const pd_weights *w, const float *x_start, const float *z, const int64_t *t_seq,
-                                const float *noise, int B, int N, int loss_type, float *loss_out, float *x0_pred_out, float *xt_out,
-                                float *model_out, void *stream) {
-    if (!tr) {
-        pd_set_error("pd_train_forward: NULL trainer");
-        return PD_ERR_INVALID_ARG;
-    }
+// pd_train_forward (sites = 0) and pd_train_forward_dropout: `drop` holds thr / key / step / scale of the call
+static int tr_forward(pd_trainer *tr, const pd_weights *w, const float *x_start, const float *z, const int64_t *t_seq, const float *noise, int B,
+                      int N, int loss_type, const PdTrDrop &drop, unsigned sites, const char *who, float *loss_out, float *x0_pred_out, float *xt_out,
+                      float *model_out, void *stream) {
     if (!x_start || !z || !t_seq || !noise || !loss_out || B < 1 || N < 1 || B > tr->max_B || N > tr->max_N || (loss_type != 1 && loss_type != 2)) {
-        pd_set_error("pd_train_forward: invalid arguments (B=%d N=%d loss_type=%d; max_B=%d max_N=%d; x_start, z, t_seq, noise and loss_out must not be NULL)",
-                     B, N, loss_type, tr->max_B, tr->max_N);
+        pd_set_error("%s: invalid arguments (B=%d N=%d loss_type=%d; max_B=%d max_N=%d; x_start, z, t_seq, noise and loss_out must not be NULL)",
+                     who, B, N, loss_type, tr->max_B, tr->max_N);
         return PD_ERR_INVALID_ARG;
     }
     if (N > PD_TR_MAX_N) {
-        pd_set_error("pd_train_forward: N=%d exceeds the trainer's limit of %d frames per sequence (the attention backward holds a sequence in LDS)", N, PD_TR_MAX_N);
+        pd_set_error("%s: N=%d exceeds the trainer's limit of %d frames per sequence (the attention backward holds a sequence in LDS)", who, N, PD_TR_MAX_N);
         return PD_ERR_UNSUPPORTED;
     }
-    PD_TRY(tr_weights_match(tr, w, "pd_train_forward"));
+    PD_TRY(tr_weights_match(tr, w, who));
     if (x0_pred_out && !tr->pred_x0 && !tr->c_recip) {
-        pd_set_error("pd_train_forward: x0_pred_out under pred_noise needs sqrt_recip / sqrt_recipm1_alphas_cumprod at pd_trainer_create");
+        pd_set_error("%s: x0_pred_out under pred_noise needs sqrt_recip / sqrt_recipm1_alphas_cumprod at pd_trainer_create", who);
         return PD_ERR_STATE;
     }
     hipStream_t s = (hipStream_t)stream;
     const int M = B * N, d = tr->d, rb = (M + 3) / 4;
     tr->pend_B = tr->pend_N = 0;
+    tr->pend_sites = 0;
+    PdTrDrop site;
     float *xt = tr->xt;
     hipLaunchKernelGGL(pd_tr_q_sample_kernel, dim3((M * 9 + 255) / 256), dim3(256), 0, s, x_start, noise, t_seq, tr->qa, tr->qb, M, N, tr->timesteps, xt,
                        tr->t_b, tr->d_err);
@@ -274,11 +293,16 @@ extern "C" int pd_train_forward(pd_trainer *tr, const pd_weights *w, const float
         float *h0 = tr->hres[2 * l], *h1 = tr->hres[2 * l + 1], *h2 = tr->hres[2 * l + 2];
         hipLaunchKernelGGL(pd_tr_ln_kernel, dim3(rb), dim3(256), 0, s, h0, tr->hn, W.norm1_w, W.norm1_b, M, d, S.stats1);
         tr_linear(tr->hn, W.in_proj_w, W.in_proj_b, S.qkv, M, 3 * d, d, 0, nullptr, s);
-        hipLaunchKernelGGL(pd_tr_attn_kernel, dim3(B * tr->nhead), dim3(256), pd_tr_attn_lds(N, tr->hd), s, S.qkv, S.ctx, N, tr->nhead, tr->hd, d, scale);
-        tr_linear(S.ctx, W.out_proj_w, W.out_proj_b, h1, M, d, d, 0, h0, s);
+        if (const PdTrDrop *dr = tr_site(drop, sites, l, 0, &site))
+            hipLaunchKernelGGL(pd_tr_attn_kernel<true>, dim3(B * tr->nhead), dim3(256), pd_tr_attn_lds(N, tr->hd), s, S.qkv, S.ctx, N, tr->nhead, tr->hd, d,
+                               scale, *dr);
+        else
+            hipLaunchKernelGGL(pd_tr_attn_kernel<false>, dim3(B * tr->nhead), dim3(256), pd_tr_attn_lds(N, tr->hd), s, S.qkv, S.ctx, N, tr->nhead, tr->hd, d,
+                               scale, PdTrDrop{});
+        tr_linear(S.ctx, W.out_proj_w, W.out_proj_b, h1, M, d, d, 0, h0, s, tr_site(drop, sites, l, 1, &site));
         hipLaunchKernelGGL(pd_tr_ln_kernel, dim3(rb), dim3(256), 0, s, h1, tr->hn, W.norm2_w, W.norm2_b, M, d, S.stats2);
-        tr_linear(tr->hn, W.linear1_w, W.linear1_b, S.ffa, M, tr->ff, d, 1, nullptr, s);
-        tr_linear(S.ffa, W.linear2_w, W.linear2_b, h2, M, d, tr->ff, 0, h1, s);
+        tr_linear(tr->hn, W.linear1_w, W.linear1_b, S.ffa, M, tr->ff, d, 1, nullptr, s, tr_site(drop, sites, l, 2, &site));
+        tr_linear(S.ffa, W.linear2_w, W.linear2_b, h2, M, d, tr->ff, 0, h1, s, tr_site(drop, sites, l, 3, &site));
     }
     tr_linear(tr->hres[2 * tr->layers], w->last0_w, w->last0_b, tr->hid_pre, M, tr->hid, d, 0, nullptr, s);
     PdTrTail ta;
@@ -293,7 +317,46 @@ extern "C" int pd_train_forward(pd_trainer *tr, const pd_weights *w, const float
     PD_HIP_CHECK(hipGetLastError());
     tr->pend_B = tr->last_B = B;
     tr->pend_N = tr->last_N = N;
+    tr->pend_drop = drop;
+    tr->pend_sites = sites;
     return PD_OK;
+}
+
+extern "C" int pd_train_forward(pd_trainer *tr, const pd_weights *w, const float *x_start, const float *z, const int64_t *t_seq,
+                                const float *noise, int B, int N, int loss_type, float *loss_out, float *x0_pred_out, float *xt_out,
+                                float *model_out, void *stream) {
+    if (!tr) {
+        pd_set_error("pd_train_forward: NULL trainer");
+        return PD_ERR_INVALID_ARG;
+    }
+    return tr_forward(tr, w, x_start, z, t_seq, noise, B, N, loss_type, PdTrDrop{}, 0u, "pd_train_forward", loss_out, x0_pred_out, xt_out, model_out, stream);
+}
+
+extern "C" int pd_train_forward_dropout(pd_trainer *tr, const pd_weights *w, const float *x_start, const float *z, const int64_t *t_seq,
+                                        const float *noise, int B, int N, int loss_type, float p, unsigned sites, uint64_t seed, uint32_t step,
+                                        float *loss_out, float *x0_pred_out, float *xt_out, float *model_out, void *stream) {
+    if (!tr) {
+        pd_set_error("pd_train_forward_dropout: NULL trainer");
+        return PD_ERR_INVALID_ARG;
+    }
+    if (!(p >= 0.0f && p < 1.0f)) {                      // NaN fails both comparisons
+        pd_set_error("pd_train_forward_dropout: invalid argument p=%g: the dropout probability must lie in [0, 1)", (double)p);
+        return PD_ERR_INVALID_ARG;
+    }
+    if (sites & ~PD_DROP_ALL) {
+        pd_set_error("pd_train_forward_dropout: invalid argument sites=0x%x: only the bits of PD_DROP_ALL (0x%x) are defined", sites, PD_DROP_ALL);
+        return PD_ERR_INVALID_ARG;
+    }
+    PdTrDrop drop = {};
+    if (p == 0.0f) sites = 0;                            // pd_train_forward itself: same launches, same bits
+    if (sites) {
+        drop.thr = (unsigned int)floor((double)p * 4294967296.0);
+        drop.scale = 1.0f / (1.0f - p);
+        drop.key0 = (unsigned int)(seed & 0xffffffffu);
+        drop.key1 = (unsigned int)(seed >> 32);
+        drop.step = step;
+    }
+    return tr_forward(tr, w, x_start, z, t_seq, noise, B, N, loss_type, drop, sites, "pd_train_forward_dropout", loss_out, x0_pred_out, xt_out, model_out, stream);
 }
 
 extern "C" int pd_train_backward(pd_trainer *tr, const pd_weights *w, const float *g_loss, const pd_weight_grads *grads, float *dz_out,
@@ -310,6 +373,10 @@ extern "C" int pd_train_backward(pd_trainer *tr, const pd_weights *w, const floa
     hipStream_t s = (hipStream_t)stream;
     const int B = tr->pend_B, N = tr->pend_N, M = B * N, d = tr->d, ff = tr->ff, hid = tr->hid, rb = (M + 3) / 4, Lc = tr->layers;
     tr->pend_B = tr->pend_N = 0;
+    const PdTrDrop &drop = tr->pend_drop;
+    const unsigned sites = tr->pend_sites;
+    PdTrDrop site;
+    const unsigned mask_blocks = (unsigned)std::min<long long>(((long long)((M + 3) / 4) * d + 255) / 256, 4096);
     // tail: loss derivative -> _last.3 -> ReLU mask -> LayerNorm(hidden) backward
     PdTrTailBwd tb;
     memset(&tb, 0, sizeof(tb));
@@ -327,18 +394,35 @@ extern "C" int pd_train_backward(pd_trainer *tr, const pd_weights *w, const floa
         const PdTrLayerStash &S = tr->L[l];
         const float *h0 = tr->hres[2 * l], *h1 = tr->hres[2 * l + 1];
         // feed-forward sublayer: dres is the gradient of linear2's output
-        tr_wgrad(tr, tr->dres, S.ffa, G.linear2_w, G.linear2_b, M, d, ff, s);
-        tr_dgrad(tr->dres, W.linear2_w, ff, 0, tr->dff, M, d, ff, S.ffa, 1, false, s);
+        // (dropout: linear2's dY is dres masked at site 3; the stash is post-dropout, so "aux > 0" is "ReLU passed and kept", times scale)
+        const float *dy2 = tr->dres;
+        if (const PdTrDrop *dr = tr_site(drop, sites, l, 3, &site)) {
+            hipLaunchKernelGGL(pd_tr_dropmask_kernel, dim3(mask_blocks), dim3(256), 0, s, tr->dres, tr->dres_m, M, d, *dr);
+            dy2 = tr->dres_m;
+        }
+        const PdTrDrop *ffs = tr_site(drop, sites, l, 2, &site);
+        if (ffs) site.philox = 0;
+        tr_wgrad(tr, dy2, S.ffa, G.linear2_w, G.linear2_b, M, d, ff, s);
+        tr_dgrad(dy2, W.linear2_w, ff, 0, tr->dff, M, d, ff, S.ffa, 1, false, s, ffs);
         if (G.linear1_w) hipLaunchKernelGGL(pd_tr_ln_kernel, dim3(rb), dim3(256), 0, s, h1, tr->hn, W.norm2_w, W.norm2_b, M, d, S.stats2);
         tr_wgrad(tr, tr->dff, tr->hn, G.linear1_w, G.linear1_b, M, ff, d, s);
         tr_dgrad(tr->dff, W.linear1_w, d, 0, tr->dhn, M, ff, d, nullptr, 0, false, s);
         tr_ln_param_grads(tr, tr->dhn, h1, S.stats2, G.norm2_w, G.norm2_b, M, d, s);
         hipLaunchKernelGGL(pd_tr_ln_bwd_kernel, dim3(rb), dim3(256), 0, s, tr->dhn, h1, S.stats2, W.norm2_w, M, d, tr->dres);
         // attention sublayer: dres is the gradient of out_proj's output
-        tr_wgrad(tr, tr->dres, S.ctx, G.out_proj_w, G.out_proj_b, M, d, d, s);
-        tr_dgrad(tr->dres, W.out_proj_w, d, 0, tr->dhn, M, d, d, nullptr, 0, false, s);
-        hipLaunchKernelGGL(pd_tr_attn_bwd_kernel, dim3(B * tr->nhead), dim3(256), pd_tr_attn_bwd_lds(N, tr->hd), s, S.qkv, tr->dhn, tr->dqkv, N, tr->nhead,
-                           tr->hd, d, scale);
+        const float *dy1 = tr->dres;
+        if (const PdTrDrop *dr = tr_site(drop, sites, l, 1, &site)) {
+            hipLaunchKernelGGL(pd_tr_dropmask_kernel, dim3(mask_blocks), dim3(256), 0, s, tr->dres, tr->dres_m, M, d, *dr);
+            dy1 = tr->dres_m;
+        }
+        tr_wgrad(tr, dy1, S.ctx, G.out_proj_w, G.out_proj_b, M, d, d, s);
+        tr_dgrad(dy1, W.out_proj_w, d, 0, tr->dhn, M, d, d, nullptr, 0, false, s);
+        if (const PdTrDrop *dr = tr_site(drop, sites, l, 0, &site))
+            hipLaunchKernelGGL(pd_tr_attn_bwd_kernel<true>, dim3(B * tr->nhead), dim3(256), pd_tr_attn_bwd_lds(N, tr->hd), s, S.qkv, tr->dhn, tr->dqkv, N,
+                               tr->nhead, tr->hd, d, scale, *dr);
+        else
+            hipLaunchKernelGGL(pd_tr_attn_bwd_kernel<false>, dim3(B * tr->nhead), dim3(256), pd_tr_attn_bwd_lds(N, tr->hd), s, S.qkv, tr->dhn, tr->dqkv, N,
+                               tr->nhead, tr->hd, d, scale, PdTrDrop{});
         if (G.in_proj_w) hipLaunchKernelGGL(pd_tr_ln_kernel, dim3(rb), dim3(256), 0, s, h0, tr->hn, W.norm1_w, W.norm1_b, M, d, S.stats1);
         tr_wgrad(tr, tr->dqkv, tr->hn, G.in_proj_w, G.in_proj_b, M, 3 * d, d, s);
         tr_dgrad(tr->dqkv, W.in_proj_w, d, 0, tr->dhn, M, 3 * d, d, nullptr, 0, false, s);

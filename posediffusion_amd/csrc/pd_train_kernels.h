@@ -25,6 +25,47 @@
 
 #define PD_TR_ERR_T_RANGE 8u        // the trainer's error word: a timestep outside [0, timesteps) was clamped
 
+// --------------------------------------------------------------------------------------------
+// dropout masks (DESIGN 3.9 "Dropout"): Philox4x32-10, counter = (row >> 2, column, 4 layer + site, step), key = the call's 64-bit seed;
+// the element at (row, column) is kept iff word (row & 3) of the output is >= thr = floor(p 2^32).  Four consecutive rows share one call.
+// Masks are never stored: forward and backward recompute them from (seed, step, p).
+// --------------------------------------------------------------------------------------------
+struct PdTrRand {
+    unsigned int w[4];
+};
+
+__host__ __device__ __forceinline__ PdTrRand pd_tr_philox(unsigned int c0, unsigned int c1, unsigned int c2, unsigned int c3, unsigned int k0,
+                                                          unsigned int k1) {
+#pragma unroll
+    for (int round = 0; round < 10; ++round) {
+        const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0, p1 = (unsigned long long)0xCD9E8D57u * c2;
+        const unsigned int n0 = (unsigned int)(p1 >> 32) ^ c1 ^ k0, n2 = (unsigned int)(p0 >> 32) ^ c3 ^ k1;
+        c1 = (unsigned int)p1;
+        c3 = (unsigned int)p0;
+        c0 = n0;
+        c2 = n2;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    PdTrRand r;
+    r.w[0] = c0; r.w[1] = c1; r.w[2] = c2; r.w[3] = c3;
+    return r;
+}
+
+// one site of one layer in one call; philox = 0: no mask, the scale alone (the data gradient behind a masked ReLU stash)
+struct PdTrDrop {
+    unsigned int thr, key0, key1, step, ctr2;   // ctr2 = 4 layer + site
+    float scale;                                // 1 / (1 - p), fp32, from the host
+    int philox;
+};
+
+__host__ __device__ __forceinline__ bool pd_tr_keep(const PdTrDrop &dr, unsigned int row, unsigned int col) {
+    const PdTrRand r = pd_tr_philox(row >> 2, col, dr.ctr2, dr.step, dr.key0, dr.key1);
+    const unsigned int k = row & 3;                     // selected, not indexed: a run-time index would put the four words in scratch
+    const unsigned int lo = k & 1 ? r.w[1] : r.w[0], hi = k & 1 ? r.w[3] : r.w[2];
+    return (k & 2 ? hi : lo) >= dr.thr;
+}
+
 struct PdTrGemm {
     const float *A;                 // A(i, r) = A[i * a_rs + r * a_cs]
     long long a_rs, a_cs;
@@ -44,7 +85,10 @@ struct PdTrGemm {
     int a_rfast, b_rfast;           // 1: the reduction index is the contiguous one of that operand in memory (picks the coalesced staging pattern)
 };
 
-__global__ __launch_bounds__(256) void pd_tr_gemm_kernel(PdTrGemm g) {
+// DROP: the epilogue applies `dr` after the ReLU / mask and before the residual add: v = keep ? v scale : 0.  A lane's 16 accumulators are
+// four groups of four consecutive rows at one column, so a group is one Philox call.  DROP = false is the kernel as it was.
+template <bool DROP>
+__global__ __launch_bounds__(256) void pd_tr_gemm_kernel(PdTrGemm g, PdTrDrop dr) {
     __shared__ float As[PD_TR_KC * PD_TR_LD];
     __shared__ float Bs[PD_TR_KC * PD_TR_LD];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, hi = lane >> 5;
@@ -93,9 +137,13 @@ __global__ __launch_bounds__(256) void pd_tr_gemm_kernel(PdTrGemm g) {
     const int gj = j0 + wj + l31;
     if (gj >= g.J) return;
     const float bias = g.bias ? g.bias[gj] : 0.0f;
+    PdTrRand rnd = {{0u, 0u, 0u, 0u}};
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
         const int gi = i0 + wi + (q & 3) + 8 * (q >> 2) + 4 * hi;
+        if constexpr (DROP) {
+            if ((q & 3) == 0 && dr.philox) rnd = pd_tr_philox((unsigned int)gi >> 2, (unsigned int)gj, dr.ctr2, dr.step, dr.key0, dr.key1);
+        }
         if (gi >= g.I) continue;
         float v = acc[q] + bias;
         if (g.relu) v = pd_relu(v);
@@ -105,6 +153,10 @@ __global__ __launch_bounds__(256) void pd_tr_gemm_kernel(PdTrGemm g) {
             const float a = g.aux[(long long)gi * g.ldaux + gj];
             const float sg = 1.0f / (1.0f + expf(-a));
             v *= sg * (1.0f + a * (1.0f - sg));
+        }
+        if constexpr (DROP) {
+            const bool keep = dr.philox ? rnd.w[q & 3] >= dr.thr : true;
+            v = keep ? v * dr.scale : 0.0f;
         }
         if (g.resid) v += g.resid[(long long)gi * g.ldr + gj];
         C[(long long)gi * g.ldc + gj] = v;
@@ -119,6 +171,21 @@ __global__ __launch_bounds__(256) void pd_tr_reduce_kernel(const T *__restrict__
         T s = ws[e];
         for (int z = 1; z < nz; ++z) s += ws[(long long)z * total + e];
         out[e] = (float)s;
+    }
+}
+
+// out = in masked at one site (dropout backward of a residual sublayer's output): out[r][c] = keep(r, c) ? in[r][c] scale : 0 over
+// [M, D]; a thread owns four consecutive rows of one column = one Philox call
+__global__ __launch_bounds__(256) void pd_tr_dropmask_kernel(const float *__restrict__ in, float *__restrict__ out, int M, int D, PdTrDrop dr) {
+    const long long total = (long long)((M + 3) / 4) * D;
+    for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
+        const int g4 = (int)(idx / D), c = (int)(idx - (long long)g4 * D);
+        const PdTrRand rnd = pd_tr_philox((unsigned int)g4, (unsigned int)c, dr.ctr2, dr.step, dr.key0, dr.key1);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int r = 4 * g4 + k;
+            if (r < M) out[(long long)r * D + c] = rnd.w[k] >= dr.thr ? in[(long long)r * D + c] * dr.scale : 0.0f;
+        }
     }
 }
 
@@ -308,8 +375,10 @@ __device__ __forceinline__ void pd_tr_attn_stage_kv(const float *__restrict__ ba
     }
 }
 
+// DROP: site 0, the probability of (query row i, key j) is multiplied by keep scale before P V; mask row = (b nhead + h) N + i, column = j
+template <bool DROP>
 __global__ __launch_bounds__(256) void pd_tr_attn_kernel(const float *__restrict__ qkv, float *__restrict__ ctx, int N, int nhead, int hd, int d,
-                                                         float scale) {
+                                                         float scale, PdTrDrop dr) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int LD = hd + 4;
     float *Kk = lds, *V = lds + (size_t)N * LD;
@@ -321,7 +390,8 @@ __global__ __launch_bounds__(256) void pd_tr_attn_kernel(const float *__restrict
     const int jj = lane < N ? lane : N - 1;
     const float4 *kb = (const float4 *)(Kk + jj * LD);
     for (int i = wave; i < N; i += 4) {
-        const float p = pd_tr_attn_prob((const float4 *)(base + (size_t)i * ld3), kb, hd / 4, scale, lane, N);
+        float p = pd_tr_attn_prob((const float4 *)(base + (size_t)i * ld3), kb, hd / 4, scale, lane, N);
+        if constexpr (DROP) p = pd_tr_keep(dr, (unsigned int)(blockIdx.x * N + i), (unsigned int)lane) ? p * dr.scale : 0.0f;
         float o[2] = {0.0f, 0.0f};
         for (int j = 0; j < N; ++j) {
             const float pj = __shfl(p, j, 64);
@@ -345,8 +415,11 @@ static inline size_t pd_tr_attn_lds(int N, int hd) { return (size_t)2 * N * (hd 
 // Attention backward.  Phase 1, wave w owns query rows w, w + 4, ...: P row recomputed, dP_ij = dO_i . V_j, dS_ij = P_ij (dP_ij -
 // sum_j dP_ij P_ij), both rows kept in LDS, dQ_i = scale sum_j dS_ij K_j.  Phase 2, wave w owns key rows: dV_j = sum_i P_ij dO_i,
 // dK_j = scale sum_i dS_ij Q_i, the sums over the query rows in row order.  At N = 1: P = 1 and dS = 1 (dP - dP) = 0 exactly.
+// DROP (site 0), with ks = keep scale of the element and P~ = P ks what the forward multiplied into V: dP = (dO . V) ks, dS from the
+// UNMASKED P as above, and the LDS P rows that phase 2 reads hold P~ (dV = P~^T dO).  At N = 1 dS is still 1 (dP - dP) = 0.
+template <bool DROP>
 __global__ __launch_bounds__(256) void pd_tr_attn_bwd_kernel(const float *__restrict__ qkv, const float *__restrict__ dctx, float *__restrict__ dqkv,
-                                                             int N, int nhead, int hd, int d, float scale) {
+                                                             int N, int nhead, int hd, int d, float scale, PdTrDrop dr) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int LD = hd + 4, PL = N + 1;
     float *Kk = lds, *V = lds + (size_t)N * LD, *P = V + (size_t)N * LD, *dS = P + (size_t)N * PL;
@@ -371,10 +444,18 @@ __global__ __launch_bounds__(256) void pd_tr_attn_bwd_kernel(const float *__rest
             dp = fmaf(a.w, c.w, dp);
         }
         dp = lane < N ? dp : 0.0f;
+        float pt = p;
+        if constexpr (DROP) {
+            // selects, not products with (keep ? scale : 0): a product feeding dp - rs below is contracted into an fma whose result at
+            // N = 1 is the product's rounding error instead of 0
+            const bool keep = pd_tr_keep(dr, (unsigned int)(blockIdx.x * N + i), (unsigned int)lane);
+            dp = keep ? dp * dr.scale : 0.0f;
+            pt = keep ? p * dr.scale : 0.0f;
+        }
         const float rs = pd_wave_sum(dp * p);
         const float ds = p * (dp - rs);
         if (lane < N) {
-            P[i * PL + lane] = p;
+            P[i * PL + lane] = pt;
             dS[i * PL + lane] = ds;
         }
         float o[2] = {0.0f, 0.0f};

@@ -8,9 +8,12 @@ The training branch (`forward` / `p_losses`, :308-332) runs on the engine, one p
 timesteps.  By default (``engine_grad = False``) it is the FORWARD half only: the diffusion loss of a checkpoint on a batch, no grad.
 With ``engine_grad = True`` and grad mode on, the loss comes from the trainer (posediffusion_amd/train.py, include/pd_engine_train.h)
 and is attached to the denoiser's parameters (and to z when it requires grad): ``loss.mean().backward()`` runs the hand-written
-backward, PyTorch keeps the optimiser.  Either way the network is evaluated as under ``model.eval()``: the reference under
-``model.train()`` applies dropout, which the engine does not reproduce -- so engine training is dropout-0 training, and the opt-in
-refuses a diffuser in ``.train()`` mode whose encoder layers have dropout p > 0."""
+backward, PyTorch keeps the optimiser.  By default the network is evaluated as under ``model.eval()``: the reference under
+``model.train()`` applies dropout, so with ``engine_dropout = False`` engine training is dropout-0 training and the opt-in refuses a
+diffuser in ``.train()`` mode whose encoder layers have dropout p > 0.  ``engine_dropout = True`` (a second opt-in, under
+``engine_grad``) trains the model as built: in ``.train()`` mode the trainer applies the encoder layers' dropout p at their four sites
+with masks of its own counter-based generator -- one int64 seed per call from torch's default CPU generator, so ``torch.manual_seed``
+reproduces a run -- and differentiates that function.  The masks are not torch's: the distribution is the reference's, the bits are not."""
 import os
 from collections import namedtuple
 
@@ -51,6 +54,7 @@ class GaussianDiffusion(nn.Module):
         #                                                then holds a larger exchange region (PD_OPT_GGS_MAX_FRAMES, include/pd_engine.h)
         self.engine_grad = False                       # True: with grad mode on, p_losses / forward return a loss that is differentiable with respect to the
         #                                                denoiser's parameters and z (the trainer's hand-written backward); the default stays forward-only
+        self.engine_dropout = False                    # True (with engine_grad, in .train() mode): the trainer applies the encoder layers' dropout instead of refusing it
         self.ggs_long_pair_items = False               # True: above 64 frames, take frame pairs of more than 512 matches (PD_OPT_GGS_LONG_PAIR_ITEMS)
 
     # ---- schedule helpers (:190-216): elementwise on the buffers, same names and argument order; the sampler itself has these
@@ -180,16 +184,33 @@ class GaussianDiffusion(nn.Module):
             raise RuntimeError(f"engine_grad: the diffuser is in .train() mode and its encoder layers have dropout p = {max(ps)}: the reference "
                                "would apply dropout there and the engine does not (no-dropout rule). Set TRANSFORMER.dropout = 0 or call .eval()")
 
+    def _dropout_p(self):
+        """The one dropout probability of the trunk's encoder layers (all four sites of every layer), for ``engine_dropout``."""
+        ps = [float(m.p) for m in self.model._trunk.modules() if isinstance(m, nn.Dropout)]
+        ps += [float(getattr(l.self_attn, "dropout", 0.0)) for l in self.model._trunk.layers]
+        if not ps:
+            return 0.0
+        if min(ps) != max(ps):
+            raise RuntimeError(f"engine_dropout: the encoder layers' dropout sites have different probabilities ({min(ps)} and {max(ps)}): "
+                               "the trainer applies ONE p at the four sites of every layer")
+        return ps[0]
+
     def _p_losses_grad(self, x_start, t, z, noise):
         """p_losses through the trainer: ``loss`` carries grad with respect to the denoiser's parameters and z."""
         from posediffusion_amd.train import p_losses_with_grad
         if self.loss_type not in ("l1", "l2"):
             raise ValueError(f"invalid loss type {self.loss_type}")
-        self._check_no_dropout()
+        drop = {}
+        if self.training and getattr(self, "engine_dropout", False):
+            p = self._dropout_p()
+            if p > 0:                                                               # one draw per call, on the CPU: no device sync
+                drop = {"dropout_p": p, "seed": int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64)), "step": 0}
+        else:
+            self._check_no_dropout()
         noise = torch.randn_like(x_start) if noise is None else noise              # :309
         B, N, _ = x_start.shape
         tr = host.get_trainer(self.model, self, B, N)
-        out = p_losses_with_grad(tr, self.model, x_start, z, t, noise, self.loss_type)
+        out = p_losses_with_grad(tr, self.model, x_start, z, t, noise, self.loss_type, **drop)
         return {"loss": out["loss"], "noise": noise, "x_0_pred": out["x_0_pred"], "x_t": out["x_t"], "t": t}
 
     def p_losses(self, x_start, t, z=None, noise=None):

@@ -3,8 +3,10 @@ GaussianDiffusion.p_losses (models/gaussian_diffuser.py:308-327) and its gradien
 computed by hand-written gfx950 kernels from the LIVE PyTorch parameters: an optimiser step needs no rebuild and no repacking.
 
 PyTorch keeps the optimiser, the LR schedule and gradient clipping (the reference's train.py:73-77, 245-251); ``p_losses_with_grad``
-is the ``torch.autograd.Function`` that hands the engine's gradients to autograd.  Exact fp32, eval-mode function (no dropout),
-pre-norm only, N <= 64, head dim <= 128.  No CPU path: a missing library or GPU raises."""
+is the ``torch.autograd.Function`` that hands the engine's gradients to autograd.  Exact fp32, pre-norm only, N <= 64, head dim <= 128.
+Without ``dropout_p`` it is the eval-mode function; with it, the ``.train()``-mode one: dropout at the four sites of every encoder layer
+(``DROPOUT_SITES``), masks from Philox4x32-10 keyed by ``(seed, step)`` and recomputed by the backward (pd_train_forward_dropout).
+No CPU path: a missing library or GPU raises."""
 from __future__ import annotations
 
 import ctypes as C
@@ -15,6 +17,8 @@ import torch
 from . import _lib
 
 _LOSS_TYPES = {"l1": 1, "l2": 2}
+DROPOUT_SITES = {"attn": _lib.PD_DROP_ATTN, "resid1": _lib.PD_DROP_RESID1, "ff": _lib.PD_DROP_FF, "resid2": _lib.PD_DROP_RESID2}
+ALL = _lib.PD_DROP_ALL
 _TOP = (("time_embed.linear.0.weight", "time_w0"), ("time_embed.linear.0.bias", "time_b0"), ("time_embed.linear.2.weight", "time_w2"),
         ("time_embed.linear.2.bias", "time_b2"), ("_first.weight", "first_w"), ("_first.bias", "first_b"))
 _LAYER = (("norm1.weight", "norm1_w"), ("norm1.bias", "norm1_b"), ("self_attn.in_proj_weight", "in_proj_w"),
@@ -139,11 +143,15 @@ class PoseTrainer:
 
     # ---------------------------------------------------------------- forward / backward
     def forward(self, params: Dict[str, torch.Tensor], x_start: torch.Tensor, z: torch.Tensor, t: torch.Tensor, noise: torch.Tensor,
-                loss_type: str = "l1") -> Dict[str, torch.Tensor]:
+                loss_type: str = "l1", dropout_p: float = 0.0, dropout_sites: int = ALL, seed: int = 0, step: int = 0) -> Dict[str, torch.Tensor]:
         """pd_train_forward: ``{"loss", "x_0_pred", "x_t", "model_out"}`` (each [B, N, 9]) from the live ``params`` (state-dict names ->
-        tensors), with the stash one ``backward`` consumes."""
+        tensors), with the stash one ``backward`` consumes.  ``dropout_p`` > 0: pd_train_forward_dropout at the sites in ``dropout_sites``
+        (bits of ``DROPOUT_SITES``) with the masks of ``(seed, step)`` (seed: any int, taken modulo 2^64; step: uint32); ``backward`` then
+        differentiates that function.  ``dropout_p == 0`` or ``dropout_sites == 0`` is the call without dropout, bit for bit."""
         if loss_type not in _LOSS_TYPES:
             raise ValueError(f"invalid loss type {loss_type}")
+        if not 0 <= int(step) < 2 ** 32:
+            raise ValueError(f"step must fit 32 unsigned bits, got {step}")
         B, N, _ = x_start.shape
         live = self._live(params)
         x_start, z, noise = self._f32(x_start, (B, N, 9)), self._f32(z, (B, N, int(self.shape["z_dim"]))), self._f32(noise, (B, N, 9))
@@ -154,9 +162,13 @@ class PoseTrainer:
         w = self._weights_struct(live)
         self._pending = None
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.pd_train_forward(self._h, C.byref(w), x_start.data_ptr(), z.data_ptr(), t.data_ptr(), noise.data_ptr(), B, N,
-                                                 _LOSS_TYPES[loss_type], out["loss"].data_ptr(), out["x_0_pred"].data_ptr(),
-                                                 out["x_t"].data_ptr(), out["model_out"].data_ptr(), self._stream()), "pd_train_forward")
+            outs = (out["loss"].data_ptr(), out["x_0_pred"].data_ptr(), out["x_t"].data_ptr(), out["model_out"].data_ptr(), self._stream())
+            ins = (self._h, C.byref(w), x_start.data_ptr(), z.data_ptr(), t.data_ptr(), noise.data_ptr(), B, N, _LOSS_TYPES[loss_type])
+            if float(dropout_p) == 0.0 and 0 <= int(dropout_sites) <= ALL:
+                _lib.check(self.lib.pd_train_forward(*ins, *outs), "pd_train_forward")
+            else:                                # (a bad p or sites is refused by the C entry, which names the argument)
+                _lib.check(self.lib.pd_train_forward_dropout(*ins, float(dropout_p), int(dropout_sites) & 0xffffffff, int(seed) % 2 ** 64, int(step),
+                                                             *outs), "pd_train_forward_dropout")
         self._generation += 1
         self._pending = self._last_shape = (B, N)
         return out
@@ -202,12 +214,14 @@ class PoseTrainer:
 
 class _PLossesFn(torch.autograd.Function):
     """(trainer, loss_type, x_start, z, t, noise, *params) -> (loss, x_0_pred, x_t, model_out); only ``loss`` is differentiable, with
-    respect to the parameters (passed flat so that autograd routes their gradients) and z."""
+    respect to the parameters (passed flat so that autograd routes their gradients) and z.  ``loss_type`` is the string, or the tuple
+    ``(loss_type, dropout_p, dropout_sites, seed, step)`` of a forward with dropout."""
 
     @staticmethod
     def forward(ctx, trainer, loss_type, x_start, z, t, noise, *params):
         sd = dict(zip(trainer.names, params))
-        out = trainer.forward(sd, x_start, z, t, noise, loss_type)
+        loss_type, *drop = (loss_type,) if isinstance(loss_type, str) else loss_type
+        out = trainer.forward(sd, x_start, z, t, noise, loss_type, *drop)
         ctx.trainer, ctx.generation = trainer, trainer._generation
         ctx.z_shape_dtype = (z.shape, z.dtype, z.device)
         ctx.save_for_backward(*params)
@@ -231,9 +245,12 @@ class _PLossesFn(torch.autograd.Function):
         return (None, None, None, gz, None, None) + tuple(grads.get(n) for n in tr.names)
 
 
-def p_losses_with_grad(trainer: PoseTrainer, denoiser: torch.nn.Module, x_start, z, t, noise, loss_type: str = "l1") -> Dict[str, torch.Tensor]:
-    """The p_losses dict of ``trainer.forward`` with ``loss`` attached to ``denoiser``'s parameters (and to z when it requires grad)."""
+def p_losses_with_grad(trainer: PoseTrainer, denoiser: torch.nn.Module, x_start, z, t, noise, loss_type: str = "l1", dropout_p: float = 0.0,
+                       dropout_sites: int = ALL, seed: int = 0, step: int = 0) -> Dict[str, torch.Tensor]:
+    """The p_losses dict of ``trainer.forward`` (same dropout keywords) with ``loss`` attached to ``denoiser``'s parameters (and to z when
+    it requires grad)."""
     named = dict(denoiser.named_parameters())
     params = [named[n] for n in trainer.names]
-    loss, x0, xt, mo = _PLossesFn.apply(trainer, loss_type, x_start, z, t, noise, *params)
+    mode = loss_type if float(dropout_p) == 0.0 and 0 <= int(dropout_sites) <= ALL else (loss_type, dropout_p, dropout_sites, seed, step)
+    loss, x0, xt, mo = _PLossesFn.apply(trainer, mode, x_start, z, t, noise, *params)
     return {"loss": loss, "x_0_pred": x0, "x_t": xt, "model_out": mo}
