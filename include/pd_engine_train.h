@@ -9,8 +9,8 @@
  *   - it keeps NO weight copy: every call reads the caller's LIVE tensors (DEVICE pointers, PyTorch layout [out, in]) through the
  *     pd_weights it is handed, so an optimiser step needs no rebuild and no repacking;
  *   - it owns one activation stash sized at creation for max_B x max_N token rows, and the two q_sample tables;
- *   - exact fp32 everywhere (v_mfma_f32_32x32x2_f32), pre-norm only, N <= 64 frames, head dim <= 128, pivot column on or off, both
- *     objectives, both loss types; pd_train_forward is the eval-mode function, pd_train_forward_dropout the .train()-mode one with the
+ *   - exact fp32 everywhere (v_mfma_f32_32x32x2_f32), pre-norm only, N <= 64 frames by default, up to 256 with PD_TR_OPT_MAX_FRAMES,
+ *     head dim <= 128, pivot column on or off, both objectives, both loss types; pd_train_forward is the eval-mode function, pd_train_forward_dropout the .train()-mode one with the
  *     encoder layers' dropout (masks from a counter-based generator, recomputed by the backward, never stored);
  *   - no float atomics in any reduction: gradients are bitwise reproducible and do not depend on the trainer's capacity (every
  *     reduction over token rows is chunked by a function of M = B x N alone and its partial sums are added in chunk order);
@@ -54,11 +54,23 @@ int pd_trainer_create(const pd_weights *shape, const float *sqrt_alphas_cumprod,
                       int max_B, int max_N, pd_trainer **out);
 void pd_trainer_destroy(pd_trainer *tr);
 
+/* Per-trainer options.  N <= 64 runs the attention kernels that hold a (sequence, head) whole in LDS; N > 64 runs the key-tiled kernels
+ * (K and V through LDS in tiles of 64 keys; the backward in two launches with 16 nhead bytes of row statistics per token row, sized at
+ * pd_trainer_create).  At N <= 64 the key-tiled kernels perform the same operations on the same operands in the same order and give the
+ * same bits; PD_TR_OPT_LONG_ATTN = 1 runs them there.  The trainer remembers with the pending stash which family its forward ran, and the
+ * backward uses that family even if an option changed in between.  Synchronous, allocates nothing.  Any other option or value:
+ * PD_ERR_INVALID_ARG naming it, the old value stays in force. */
+#define PD_TR_OPT_MAX_FRAMES 1   /* 64 (default) .. 256 (PD_MAX_DENOISER_FRAMES): frames per sequence pd_train_forward admits        */
+#define PD_TR_OPT_LONG_ATTN  2   /* 0 (default): N <= 64 runs the short kernels, N > 64 the key-tiled ones; 1: key-tiled at every N */
+int pd_trainer_set_option(pd_trainer *tr, int option, int value);
+int pd_trainer_get_option(pd_trainer *tr, int option, int *value);
+
 /* The contract of pd_p_losses (same outputs, same t_seq clamping -- a clamped timestep raises the trainer's own error word,
  * pd_trainer_check_async) with the weights taken from `w` at the time of the call, and the stash the backward needs:
  * per layer the residual stream at both sublayer inputs, both LayerNorm (mean, rstd) pairs, qkv, ctx and the post-ReLU FF activations;
  * _first's input rows; _last's LayerNorm input, statistics and post-ReLU hidden; the time embedding's SiLU input.  Attention
- * probabilities are recomputed by the backward.  N > 64: PD_ERR_UNSUPPORTED before anything is launched.  loss_type 1 = l1, 2 = l2. */
+ * probabilities are recomputed by the backward.  N above the trainer's frame limit (64 by default, PD_TR_OPT_MAX_FRAMES):
+ * PD_ERR_UNSUPPORTED, "limit of <v> frames", before anything is launched.  loss_type 1 = l1, 2 = l2. */
 int pd_train_forward(pd_trainer *tr, const pd_weights *w, const float *x_start, const float *z, const int64_t *t_seq,
                      const float *noise, int B, int N, int loss_type,
                      float *loss_out, float *x0_pred_out, float *xt_out, float *model_out, void *stream);

@@ -83,6 +83,7 @@ PD_OPT_DENOISER_LONG_ATTN = 6   # 1: the key-tiled attention kernel of sequences
 PD_OPT_GGS_MAX_FRAMES = 7       # frames GGS admits: 64 (default) or a value in (64, max_N]; reallocates the exchange region, synchronous
 PD_OPT_GGS_LONG_PAIR_ITEMS = 8  # 0 (default) / 1: above 64 frames a frame pair may hold more than 512 matches (pd_ggs_longm_kernel)
 PD_DROP_ATTN, PD_DROP_RESID1, PD_DROP_FF, PD_DROP_RESID2, PD_DROP_ALL = 1, 2, 4, 8, 15   # pd_train_forward_dropout's sites (include/pd_engine_train.h)
+PD_TR_OPT_MAX_FRAMES, PD_TR_OPT_LONG_ATTN = 1, 2   # pd_trainer_set_option (include/pd_engine_train.h): frame limit 64 .. 256; key-tiled attention at every N
 PD_MATCH_HINT_ONE_ORDER = 1 << 30   # pd_match_hints.max_pairs flag: every frame pair in one order only (hloc's i < j pairs)
 
 
@@ -152,6 +153,8 @@ EXT_SIGNATURES = {
 TRAIN_SIGNATURES = {
     "pd_trainer_create": (_i, [C.POINTER(pd_weights), _vp, _vp, _i, _i, C.POINTER(_vp)]),
     "pd_trainer_destroy": (None, [_vp]),
+    "pd_trainer_set_option": (_i, [_vp, _i, _i]),
+    "pd_trainer_get_option": (_i, [_vp, _i, C.POINTER(_i)]),
     "pd_train_forward": (_i, [_vp, C.POINTER(pd_weights), _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "pd_train_forward_dropout": (_i, [_vp, C.POINTER(pd_weights), _vp, _vp, _vp, _vp, _i, _i, _i, C.c_float, C.c_uint, C.c_uint64, C.c_uint32,
                                       _vp, _vp, _vp, _vp, _vp]),

@@ -13,6 +13,8 @@
 // Dropout (pd_train_forward_dropout): the four sites of an encoder layer are masked in the epilogues of out_proj / linear1 / linear2 and
 // in the attention kernel; the backward recomputes every mask from (seed, step, p) and masks the residual-stream gradient into dres_m
 // before the weight, bias and data gradients of out_proj / linear2 read it.  A call without dropout launches the DROP = false kernels.
+// Attention: N <= 64 runs pd_tr_attn_kernel / pd_tr_attn_bwd_kernel (a sequence whole in LDS), N > 64 -- admitted once PD_TR_OPT_MAX_FRAMES
+// raises the limit -- the key-tiled pd_tr_lattn_* kernels (pd_train_lattn.h); the family a forward ran is remembered with its stash.
 #include "pd_train_kernels.h"
 #include "../../include/pd_engine_train.h"
 
@@ -39,6 +41,7 @@ struct pd_trainer {
     // scratch
     float *hn = nullptr, *dres = nullptr, *dhn = nullptr, *dff = nullptr, *dqkv = nullptr;
     float *dres_m = nullptr;                             // [M, d] dres masked at site 1 / 3 (dropout backward)
+    float *la_stats = nullptr;                           // [M nhead, 4] (row maximum, 1 / sum, rs x 2) between the two phases of the key-tiled backward
     float *dy_hid = nullptr, *dhid = nullptr, *gout = nullptr, *demb_t = nullptr, *dtemb = nullptr, *dts = nullptr;
     float *ws = nullptr;                                 // split-reduction workspaces: weight-gradient partials [chunks][Nout x K] ...
     double *ws_col = nullptr;                            // ... and column-sum partials [2][chunks][C]
@@ -48,6 +51,9 @@ struct pd_trainer {
     int last_B = 0, last_N = 0;                          // of the last forward (pd_train_debug_relu)
     PdTrDrop pend_drop = {};                             // dropout of the pending forward (ctr2 / philox are set per site) ...
     unsigned pend_sites = 0;                             // ... and its sites (0: none)
+    int max_frames = PD_TR_MAX_N;                        // PD_TR_OPT_MAX_FRAMES
+    int long_attn = 0;                                   // PD_TR_OPT_LONG_ATTN
+    int pend_long = 0;                                   // the pending forward ran the key-tiled attention: so does its backward
     PdDevAllocs mem{"pd_trainer_create"};
 };
 
@@ -139,6 +145,41 @@ static void tr_ln_param_grads(pd_trainer *tr, const float *dy, const float *x, c
     if (dbeta) hipLaunchKernelGGL(pd_tr_reduce_kernel<double>, dim3((D + 255) / 256), dim3(256), 0, s, pb, (long long)D, nch, dbeta);
 }
 
+// attention forward of one layer: the short kernel (a sequence whole in LDS) or the key-tiled one
+static void tr_attn_launch(const pd_trainer *tr, bool tiled, const float *qkv, float *ctx, int B, int N, float scale, const PdTrDrop *dr, hipStream_t s) {
+    const int nh = tr->nhead, hd = tr->hd, d = tr->d;
+    if (tiled) {
+        const dim3 grid(B * nh, (N + PD_TR_LA_ROWS - 1) / PD_TR_LA_ROWS);
+        if (dr) hipLaunchKernelGGL(pd_tr_lattn_kernel<true>, grid, dim3(256), pd_tr_lattn_lds(N, hd), s, qkv, ctx, N, nh, hd, d, scale, *dr);
+        else hipLaunchKernelGGL(pd_tr_lattn_kernel<false>, grid, dim3(256), pd_tr_lattn_lds(N, hd), s, qkv, ctx, N, nh, hd, d, scale, PdTrDrop{});
+    } else if (dr) {
+        hipLaunchKernelGGL(pd_tr_attn_kernel<true>, dim3(B * nh), dim3(256), pd_tr_attn_lds(N, hd), s, qkv, ctx, N, nh, hd, d, scale, *dr);
+    } else {
+        hipLaunchKernelGGL(pd_tr_attn_kernel<false>, dim3(B * nh), dim3(256), pd_tr_attn_lds(N, hd), s, qkv, ctx, N, nh, hd, d, scale, PdTrDrop{});
+    }
+}
+
+// attention backward of one layer: dqkv from qkv and dctx; tiled = phase A (dQ, row statistics) then phase B (dK, dV)
+static void tr_attn_bwd_launch(const pd_trainer *tr, bool tiled, const float *qkv, const float *dctx, float *dqkv, int B, int N, float scale,
+                               const PdTrDrop *dr, hipStream_t s) {
+    const int nh = tr->nhead, hd = tr->hd, d = tr->d;
+    if (tiled) {
+        const dim3 rows(B * nh, (N + PD_TR_LA_ROWS - 1) / PD_TR_LA_ROWS), keys(B * nh, pd_tr_la_tiles(N));
+        const size_t la = pd_tr_lattn_bwd_rows_lds(N, hd), lb = pd_tr_lattn_bwd_keys_lds(N, hd);
+        if (dr) {
+            hipLaunchKernelGGL(pd_tr_lattn_bwd_rows_kernel<true>, rows, dim3(256), la, s, qkv, dctx, dqkv, tr->la_stats, N, nh, hd, d, scale, *dr);
+            hipLaunchKernelGGL(pd_tr_lattn_bwd_keys_kernel<true>, keys, dim3(256), lb, s, qkv, dctx, dqkv, tr->la_stats, N, nh, hd, d, scale, *dr);
+        } else {
+            hipLaunchKernelGGL(pd_tr_lattn_bwd_rows_kernel<false>, rows, dim3(256), la, s, qkv, dctx, dqkv, tr->la_stats, N, nh, hd, d, scale, PdTrDrop{});
+            hipLaunchKernelGGL(pd_tr_lattn_bwd_keys_kernel<false>, keys, dim3(256), lb, s, qkv, dctx, dqkv, tr->la_stats, N, nh, hd, d, scale, PdTrDrop{});
+        }
+    } else if (dr) {
+        hipLaunchKernelGGL(pd_tr_attn_bwd_kernel<true>, dim3(B * nh), dim3(256), pd_tr_attn_bwd_lds(N, hd), s, qkv, dctx, dqkv, N, nh, hd, d, scale, *dr);
+    } else {
+        hipLaunchKernelGGL(pd_tr_attn_bwd_kernel<false>, dim3(B * nh), dim3(256), pd_tr_attn_bwd_lds(N, hd), s, qkv, dctx, dqkv, N, nh, hd, d, scale, PdTrDrop{});
+    }
+}
+
 // ---- shape checks ----------------------------------------------------------------------------
 static int tr_shape_check(const pd_weights *w, const char *who) {
     const int d = w->d_model, nh = w->nhead;
@@ -196,6 +237,7 @@ extern "C" int pd_trainer_create(const pd_weights *shape, const float *sqrt_alph
     TR_A(tr->hn, rows * d); TR_A(tr->dres, rows * d); TR_A(tr->dres_m, rows * d); TR_A(tr->dhn, rows * d); TR_A(tr->dff, rows * tr->ff); TR_A(tr->dqkv, rows * 3 * d);
     TR_A(tr->dy_hid, rows * tr->hid); TR_A(tr->dhid, rows * tr->hid); TR_A(tr->gout, rows * 9); TR_A(tr->demb_t, rows * 128);
     TR_A(tr->dtemb, (size_t)max_B * 128); TR_A(tr->dts, (size_t)max_B * 128);
+    TR_A(tr->la_stats, rows * tr->nhead * PD_TR_LA_STATS);
     const size_t widest_w = std::max({(size_t)d * tr->Kf, (size_t)3 * d * d, (size_t)tr->ff * d, (size_t)tr->hid * d, (size_t)9 * tr->hid, (size_t)128 * 256});
     tr->ws_floats = widest_w * PD_TR_MAX_CHUNKS;
     const size_t widest_c = std::max({(size_t)3 * d, (size_t)tr->ff, (size_t)tr->hid, (size_t)256});
@@ -215,6 +257,13 @@ extern "C" int pd_trainer_create(const pd_weights *shape, const float *sqrt_alph
     if (rc == PD_OK) rc = pd_set_lds(pd_tr_attn_kernel<true>, pd_tr_attn_lds(PD_TR_MAX_N, PD_TR_MAX_HD));
     if (rc == PD_OK) rc = pd_set_lds(pd_tr_attn_bwd_kernel<false>, pd_tr_attn_bwd_lds(PD_TR_MAX_N, PD_TR_MAX_HD));
     if (rc == PD_OK) rc = pd_set_lds(pd_tr_attn_bwd_kernel<true>, pd_tr_attn_bwd_lds(PD_TR_MAX_N, PD_TR_MAX_HD));
+    // the key-tiled kernels likewise: 256 frames, head dim 128
+    if (rc == PD_OK) rc = pd_set_lds(pd_tr_lattn_kernel<false>, pd_tr_lattn_lds(PD_TR_LA_MAX_N, PD_TR_MAX_HD));
+    if (rc == PD_OK) rc = pd_set_lds(pd_tr_lattn_kernel<true>, pd_tr_lattn_lds(PD_TR_LA_MAX_N, PD_TR_MAX_HD));
+    if (rc == PD_OK) rc = pd_set_lds(pd_tr_lattn_bwd_rows_kernel<false>, pd_tr_lattn_bwd_rows_lds(PD_TR_LA_MAX_N, PD_TR_MAX_HD));
+    if (rc == PD_OK) rc = pd_set_lds(pd_tr_lattn_bwd_rows_kernel<true>, pd_tr_lattn_bwd_rows_lds(PD_TR_LA_MAX_N, PD_TR_MAX_HD));
+    if (rc == PD_OK) rc = pd_set_lds(pd_tr_lattn_bwd_keys_kernel<false>, pd_tr_lattn_bwd_keys_lds(PD_TR_LA_MAX_N, PD_TR_MAX_HD));
+    if (rc == PD_OK) rc = pd_set_lds(pd_tr_lattn_bwd_keys_kernel<true>, pd_tr_lattn_bwd_keys_lds(PD_TR_LA_MAX_N, PD_TR_MAX_HD));
     if (rc == PD_OK && hipDeviceSynchronize() != hipSuccess) rc = PD_ERR_HIP;
     if (rc != PD_OK) {
         if (rc == PD_ERR_HIP) pd_set_error("pd_trainer_create: a HIP call failed: %s", hipGetErrorString(hipGetLastError()));
@@ -226,6 +275,44 @@ extern "C" int pd_trainer_create(const pd_weights *shape, const float *sqrt_alph
 }
 
 extern "C" void pd_trainer_destroy(pd_trainer *tr) { delete tr; }
+
+extern "C" int pd_trainer_set_option(pd_trainer *tr, int option, int value) {
+    if (!tr) {
+        pd_set_error("pd_trainer_set_option: NULL trainer");
+        return PD_ERR_INVALID_ARG;
+    }
+    if (option == PD_TR_OPT_MAX_FRAMES) {
+        if (value < PD_TR_MAX_N || value > PD_TR_LA_MAX_N) {
+            pd_set_error("pd_trainer_set_option: PD_TR_OPT_MAX_FRAMES=%d is outside [%d, %d]", value, PD_TR_MAX_N, PD_TR_LA_MAX_N);
+            return PD_ERR_INVALID_ARG;
+        }
+        tr->max_frames = value;
+    } else if (option == PD_TR_OPT_LONG_ATTN) {
+        if (value != 0 && value != 1) {
+            pd_set_error("pd_trainer_set_option: PD_TR_OPT_LONG_ATTN=%d must be 0 or 1", value);
+            return PD_ERR_INVALID_ARG;
+        }
+        tr->long_attn = value;
+    } else {
+        pd_set_error("pd_trainer_set_option: unknown option %d (value %d)", option, value);
+        return PD_ERR_INVALID_ARG;
+    }
+    return PD_OK;
+}
+
+extern "C" int pd_trainer_get_option(pd_trainer *tr, int option, int *value) {
+    if (!tr || !value) {
+        pd_set_error("pd_trainer_get_option: NULL trainer or value");
+        return PD_ERR_INVALID_ARG;
+    }
+    if (option == PD_TR_OPT_MAX_FRAMES) *value = tr->max_frames;
+    else if (option == PD_TR_OPT_LONG_ATTN) *value = tr->long_attn;
+    else {
+        pd_set_error("pd_trainer_get_option: unknown option %d", option);
+        return PD_ERR_INVALID_ARG;
+    }
+    return PD_OK;
+}
 
 static int tr_weights_match(const pd_trainer *tr, const pd_weights *w, const char *who) {
     if (!w) {
@@ -261,8 +348,11 @@ static int tr_forward(pd_trainer *tr, const pd_weights *w, const float *x_start,
                      who, B, N, loss_type, tr->max_B, tr->max_N);
         return PD_ERR_INVALID_ARG;
     }
-    if (N > PD_TR_MAX_N) {
-        pd_set_error("%s: N=%d exceeds the trainer's limit of %d frames per sequence (the attention backward holds a sequence in LDS)", who, N, PD_TR_MAX_N);
+    if (N > tr->max_frames) {
+        if (tr->max_frames == PD_TR_MAX_N)
+            pd_set_error("%s: N=%d exceeds the trainer's limit of %d frames per sequence (the attention backward holds a sequence in LDS)", who, N, PD_TR_MAX_N);
+        else
+            pd_set_error("%s: N=%d exceeds the trainer's limit of %d frames per sequence (PD_TR_OPT_MAX_FRAMES)", who, N, tr->max_frames);
         return PD_ERR_UNSUPPORTED;
     }
     PD_TRY(tr_weights_match(tr, w, who));
@@ -274,6 +364,7 @@ static int tr_forward(pd_trainer *tr, const pd_weights *w, const float *x_start,
     const int M = B * N, d = tr->d, rb = (M + 3) / 4;
     tr->pend_B = tr->pend_N = 0;
     tr->pend_sites = 0;
+    const bool tiled = tr->long_attn || N > PD_TR_MAX_N;
     PdTrDrop site;
     float *xt = tr->xt;
     hipLaunchKernelGGL(pd_tr_q_sample_kernel, dim3((M * 9 + 255) / 256), dim3(256), 0, s, x_start, noise, t_seq, tr->qa, tr->qb, M, N, tr->timesteps, xt,
@@ -293,12 +384,7 @@ static int tr_forward(pd_trainer *tr, const pd_weights *w, const float *x_start,
         float *h0 = tr->hres[2 * l], *h1 = tr->hres[2 * l + 1], *h2 = tr->hres[2 * l + 2];
         hipLaunchKernelGGL(pd_tr_ln_kernel, dim3(rb), dim3(256), 0, s, h0, tr->hn, W.norm1_w, W.norm1_b, M, d, S.stats1);
         tr_linear(tr->hn, W.in_proj_w, W.in_proj_b, S.qkv, M, 3 * d, d, 0, nullptr, s);
-        if (const PdTrDrop *dr = tr_site(drop, sites, l, 0, &site))
-            hipLaunchKernelGGL(pd_tr_attn_kernel<true>, dim3(B * tr->nhead), dim3(256), pd_tr_attn_lds(N, tr->hd), s, S.qkv, S.ctx, N, tr->nhead, tr->hd, d,
-                               scale, *dr);
-        else
-            hipLaunchKernelGGL(pd_tr_attn_kernel<false>, dim3(B * tr->nhead), dim3(256), pd_tr_attn_lds(N, tr->hd), s, S.qkv, S.ctx, N, tr->nhead, tr->hd, d,
-                               scale, PdTrDrop{});
+        tr_attn_launch(tr, tiled, S.qkv, S.ctx, B, N, scale, tr_site(drop, sites, l, 0, &site), s);
         tr_linear(S.ctx, W.out_proj_w, W.out_proj_b, h1, M, d, d, 0, h0, s, tr_site(drop, sites, l, 1, &site));
         hipLaunchKernelGGL(pd_tr_ln_kernel, dim3(rb), dim3(256), 0, s, h1, tr->hn, W.norm2_w, W.norm2_b, M, d, S.stats2);
         tr_linear(tr->hn, W.linear1_w, W.linear1_b, S.ffa, M, tr->ff, d, 1, nullptr, s, tr_site(drop, sites, l, 2, &site));
@@ -319,6 +405,7 @@ static int tr_forward(pd_trainer *tr, const pd_weights *w, const float *x_start,
     tr->pend_N = tr->last_N = N;
     tr->pend_drop = drop;
     tr->pend_sites = sites;
+    tr->pend_long = tiled ? 1 : 0;
     return PD_OK;
 }
 
@@ -417,12 +504,7 @@ extern "C" int pd_train_backward(pd_trainer *tr, const pd_weights *w, const floa
         }
         tr_wgrad(tr, dy1, S.ctx, G.out_proj_w, G.out_proj_b, M, d, d, s);
         tr_dgrad(dy1, W.out_proj_w, d, 0, tr->dhn, M, d, d, nullptr, 0, false, s);
-        if (const PdTrDrop *dr = tr_site(drop, sites, l, 0, &site))
-            hipLaunchKernelGGL(pd_tr_attn_bwd_kernel<true>, dim3(B * tr->nhead), dim3(256), pd_tr_attn_bwd_lds(N, tr->hd), s, S.qkv, tr->dhn, tr->dqkv, N,
-                               tr->nhead, tr->hd, d, scale, *dr);
-        else
-            hipLaunchKernelGGL(pd_tr_attn_bwd_kernel<false>, dim3(B * tr->nhead), dim3(256), pd_tr_attn_bwd_lds(N, tr->hd), s, S.qkv, tr->dhn, tr->dqkv, N,
-                               tr->nhead, tr->hd, d, scale, PdTrDrop{});
+        tr_attn_bwd_launch(tr, tr->pend_long != 0, S.qkv, tr->dhn, tr->dqkv, B, N, scale, tr_site(drop, sites, l, 0, &site), s);
         if (G.in_proj_w) hipLaunchKernelGGL(pd_tr_ln_kernel, dim3(rb), dim3(256), 0, s, h0, tr->hn, W.norm1_w, W.norm1_b, M, d, S.stats1);
         tr_wgrad(tr, tr->dqkv, tr->hn, G.in_proj_w, G.in_proj_b, M, 3 * d, d, s);
         tr_dgrad(tr->dqkv, W.in_proj_w, d, 0, tr->dhn, M, 3 * d, d, nullptr, 0, false, s);

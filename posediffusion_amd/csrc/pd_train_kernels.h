@@ -500,6 +500,9 @@ __global__ __launch_bounds__(256) void pd_tr_attn_bwd_kernel(const float *__rest
 }
 static inline size_t pd_tr_attn_bwd_lds(int N, int hd) { return ((size_t)2 * N * (hd + 4) + (size_t)2 * N * (N + 1)) * sizeof(float); }
 
+// the same attention for up to 256 frames, K and V through LDS in tiles of 64 keys (PD_TR_OPT_MAX_FRAMES): pd_tr_lattn_* kernels
+#include "pd_train_lattn.h"
+
 // --------------------------------------------------------------------------------------------
 // tail: LayerNorm(hidden) -> ReLU -> Linear(hidden, 9) (_last.1 .. 3) and the outputs of p_losses (gaussian_diffuser.py:312-327), one
 // wave per token row, lane l holds hidden values l, l + 64, ... (hidden <= 1024).  Stash: stats (mean, rstd), the post-ReLU hidden row,

@@ -13,7 +13,9 @@ backward, PyTorch keeps the optimiser.  By default the network is evaluated as u
 diffuser in ``.train()`` mode whose encoder layers have dropout p > 0.  ``engine_dropout = True`` (a second opt-in, under
 ``engine_grad``) trains the model as built: in ``.train()`` mode the trainer applies the encoder layers' dropout p at their four sites
 with masks of its own counter-based generator -- one int64 seed per call from torch's default CPU generator, so ``torch.manual_seed``
-reproduces a run -- and differentiates that function.  The masks are not torch's: the distribution is the reference's, the bits are not."""
+reproduces a run -- and differentiates that function.  The masks are not torch's: the distribution is the reference's, the bits are not.
+The trainer takes sequences of up to 64 frames by default; ``engine_grad_max_frames`` (64 .. 256) raises that (PD_TR_OPT_MAX_FRAMES:
+above 64 frames the attention and its backward run key-tiled kernels)."""
 import os
 from collections import namedtuple
 
@@ -54,6 +56,7 @@ class GaussianDiffusion(nn.Module):
         #                                                then holds a larger exchange region (PD_OPT_GGS_MAX_FRAMES, include/pd_engine.h)
         self.engine_grad = False                       # True: with grad mode on, p_losses / forward return a loss that is differentiable with respect to the
         #                                                denoiser's parameters and z (the trainer's hand-written backward); the default stays forward-only
+        self.engine_grad_max_frames = 64               # frames per sequence engine_grad admits; raise it (<= 256) to train on longer sequences (PD_TR_OPT_MAX_FRAMES)
         self.engine_dropout = False                    # True (with engine_grad, in .train() mode): the trainer applies the encoder layers' dropout instead of refusing it
         self.ggs_long_pair_items = False               # True: above 64 frames, take frame pairs of more than 512 matches (PD_OPT_GGS_LONG_PAIR_ITEMS)
 
@@ -200,6 +203,7 @@ class GaussianDiffusion(nn.Module):
         from posediffusion_amd.train import p_losses_with_grad
         if self.loss_type not in ("l1", "l2"):
             raise ValueError(f"invalid loss type {self.loss_type}")
+        limit = int(getattr(self, "engine_grad_max_frames", 64))
         drop = {}
         if self.training and getattr(self, "engine_dropout", False):
             p = self._dropout_p()
@@ -209,13 +213,19 @@ class GaussianDiffusion(nn.Module):
             self._check_no_dropout()
         noise = torch.randn_like(x_start) if noise is None else noise              # :309
         B, N, _ = x_start.shape
-        tr = host.get_trainer(self.model, self, B, N)
+        if N > limit:
+            raise RuntimeError(f"engine_grad: N={N} exceeds the trainer's limit of {limit} frames per sequence; set engine_grad_max_frames = {N} "
+                               "(at most 256) to train on sequences of this length")
+        tr = host.get_trainer(self.model, self, B, N, max_frames=limit)
         out = p_losses_with_grad(tr, self.model, x_start, z, t, noise, self.loss_type, **drop)
         return {"loss": out["loss"], "noise": noise, "x_0_pred": out["x_0_pred"], "x_t": out["x_t"], "t": t}
 
     def p_losses(self, x_start, t, z=None, noise=None):
         """``{"loss", "noise", "x_0_pred", "x_t", "t"}`` as the reference returns them; loss elementwise (reduction "none").
         Eval-mode forward; no grad unless ``engine_grad`` is set and grad mode is on (see the module docstring)."""
+        limit = int(getattr(self, "engine_grad_max_frames", 64))
+        if not 64 <= limit <= 256:
+            raise ValueError(f"engine_grad_max_frames = {limit} is outside [64, 256]")
         if z is not None and getattr(self, "engine_grad", False) and torch.is_grad_enabled():
             return self._p_losses_grad(x_start, t, z, noise)
         return self._p_losses_forward_only(x_start, t, z=z, noise=noise)

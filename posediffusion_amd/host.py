@@ -78,10 +78,11 @@ def get_engine(denoiser: torch.nn.Module, diffuser: Optional[torch.nn.Module], B
     return eng
 
 
-def get_trainer(denoiser: torch.nn.Module, diffuser: torch.nn.Module, B: int, N: int):
+def get_trainer(denoiser: torch.nn.Module, diffuser: torch.nn.Module, B: int, N: int, max_frames: int = 64):
     """``PoseTrainer`` (posediffusion_amd/train.py) for these live modules.  It reads the parameters where they are at every call, so it
     is cached on shape, device, objective and capacity -- NOT on parameter versions: an optimiser step keeps it.  The capacity never
-    shrinks."""
+    shrinks.  ``max_frames`` above 64 RAISES the frames per sequence the trainer admits (PD_TR_OPT_MAX_FRAMES), never lowers them on a
+    cached one."""
     from .train import PoseTrainer, shape_from_modules
     dev = next(denoiser.parameters()).device
     if dev.type != "cuda":
@@ -92,14 +93,23 @@ def get_trainer(denoiser: torch.nn.Module, diffuser: torch.nn.Module, B: int, N:
     cache = denoiser.__dict__.setdefault("_pd_trainer_cache", {})
     ent = cache.get("t")
     if ent is not None and ent[0] == key and ent[1].max_B >= B and ent[1].max_N >= N:
+        _raise_trainer_limit(ent[1], max_frames)
         return ent[1]
     if ent is not None:
         if ent[0] == key:
             B, N = max(B, ent[1].max_B), max(N, ent[1].max_N)     # never shrink capacity
+            if hasattr(ent[1].lib, "pd_trainer_get_option"):
+                max_frames = max(int(max_frames), ent[1].max_frames)
         ent[1].close()
     tr = PoseTrainer(shape, {n: b for n, b in diffuser.named_buffers(recurse=False)}, max_B=max(B, 1), max_N=max(N, 1), device=dev)
+    _raise_trainer_limit(tr, max_frames)
     cache["t"] = (key, tr)
     return tr
+
+
+def _raise_trainer_limit(tr, max_frames: int):
+    if int(max_frames) > 64 and int(max_frames) > tr.max_frames:     # (the default asks the library nothing: today's calls, also under A / B with an older build)
+        tr.set_max_frames(int(max_frames))
 
 
 def _raise_ggs_limit(eng: PoseEngine, ggs_max_frames: int, ggs_long_pair_items: bool = False):

@@ -3,7 +3,9 @@ GaussianDiffusion.p_losses (models/gaussian_diffuser.py:308-327) and its gradien
 computed by hand-written gfx950 kernels from the LIVE PyTorch parameters: an optimiser step needs no rebuild and no repacking.
 
 PyTorch keeps the optimiser, the LR schedule and gradient clipping (the reference's train.py:73-77, 245-251); ``p_losses_with_grad``
-is the ``torch.autograd.Function`` that hands the engine's gradients to autograd.  Exact fp32, pre-norm only, N <= 64, head dim <= 128.
+is the ``torch.autograd.Function`` that hands the engine's gradients to autograd.  Exact fp32, pre-norm only, head dim <= 128, N <= 64
+frames by default and up to 256 with ``max_frames`` / ``set_max_frames`` (PD_TR_OPT_MAX_FRAMES): above 64 frames the attention runs
+key-tiled kernels, which at N <= 64 give the bits of the default ones (``set_long_attn``, for the tests).
 Without ``dropout_p`` it is the eval-mode function; with it, the ``.train()``-mode one: dropout at the four sites of every encoder layer
 (``DROPOUT_SITES``), masks from Philox4x32-10 keyed by ``(seed, step)`` and recomputed by the backward (pd_train_forward_dropout).
 No CPU path: a missing library or GPU raises."""
@@ -29,6 +31,7 @@ _BOTTOM = (("_last.0.weight", "last0_w"), ("_last.0.bias", "last0_b"), ("_last.1
            ("_last.3.weight", "last3_w"), ("_last.3.bias", "last3_b"))
 _R_TABLES = ("sqrt_recip_alphas_cumprod", "sqrt_recipm1_alphas_cumprod")
 _Q_TABLES = ("sqrt_alphas_cumprod", "sqrt_one_minus_alphas_cumprod")
+DEFAULT_MAX_FRAMES, MAX_FRAMES = 64, 256     # PD_TR_OPT_MAX_FRAMES: its default and its ceiling (PD_MAX_DENOISER_FRAMES)
 
 
 def param_names(num_layers: int) -> List[str]:
@@ -65,9 +68,10 @@ def _fill(struct, num_layers: int, ptr_of) -> None:
 
 
 class PoseTrainer:
-    """``shape``: ``shape_from_modules(...)``; ``tables``: the GaussianDiffusion buffers (the two q_sample tables are required)."""
+    """``shape``: ``shape_from_modules(...)``; ``tables``: the GaussianDiffusion buffers (the two q_sample tables are required).
+    ``max_frames``: frames per sequence ``forward`` admits, 64 (default) .. 256 -- independent of the capacity ``max_N``."""
 
-    def __init__(self, shape: Dict, tables: Dict[str, torch.Tensor], max_B: int, max_N: int, device=None):
+    def __init__(self, shape: Dict, tables: Dict[str, torch.Tensor], max_B: int, max_N: int, device=None, max_frames: int = DEFAULT_MAX_FRAMES):
         if not torch.cuda.is_available():
             raise RuntimeError("posediffusion_amd.PoseTrainer needs an AMD GPU (torch.cuda unavailable); there is no CPU fallback")
         if shape["objective"] not in ("pred_noise", "pred_x0"):
@@ -93,6 +97,12 @@ class PoseTrainer:
             _lib.check(self.lib.pd_trainer_create(C.byref(w), ptrs[_Q_TABLES[0]], ptrs[_Q_TABLES[1]], self.max_B, self.max_N, C.byref(self._h)),
                        "pd_trainer_create")
         del keep
+        if int(max_frames) != DEFAULT_MAX_FRAMES:
+            try:
+                self.set_max_frames(max_frames)
+            except Exception:
+                self.close()
+                raise
 
     def _weights_struct(self, params: Optional[Dict[str, torch.Tensor]]) -> _lib.pd_weights:
         s = self.shape
@@ -137,6 +147,28 @@ class PoseTrainer:
         if tuple(t.shape) != tuple(shape):
             raise ValueError(f"expected shape {tuple(shape)}, got {tuple(t.shape)}")
         return t
+
+    # ---------------------------------------------------------------- options
+    def set_option(self, option: int, value: int) -> None:
+        """pd_trainer_set_option; a refused option or value raises and leaves the old value in force."""
+        _lib.check(self.lib.pd_trainer_set_option(self._h, int(option), int(value)), "pd_trainer_set_option")
+
+    def get_option(self, option: int) -> int:
+        v = C.c_int(0)
+        _lib.check(self.lib.pd_trainer_get_option(self._h, int(option), C.byref(v)), "pd_trainer_get_option")
+        return int(v.value)
+
+    def set_max_frames(self, n: int) -> None:
+        """Frames per sequence ``forward`` admits from now on: 64 .. 256 (PD_TR_OPT_MAX_FRAMES)."""
+        self.set_option(_lib.PD_TR_OPT_MAX_FRAMES, n)
+
+    @property
+    def max_frames(self) -> int:
+        return self.get_option(_lib.PD_TR_OPT_MAX_FRAMES)
+
+    def set_long_attn(self, on: bool) -> None:
+        """True: the key-tiled attention kernels at every N (PD_TR_OPT_LONG_ATTN); at N <= 64 they give the default kernels' bits."""
+        self.set_option(_lib.PD_TR_OPT_LONG_ATTN, 1 if on else 0)
 
     def check_async(self):
         _lib.check(self.lib.pd_trainer_check_async(self._h), "pd_trainer_check_async")
