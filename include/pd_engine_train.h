@@ -14,7 +14,8 @@
  *     encoder layers' dropout (masks from a counter-based generator, recomputed by the backward, never stored);
  *   - no float atomics in any reduction: gradients are bitwise reproducible and do not depend on the trainer's capacity (every
  *     reduction over token rows is chunked by a function of M = B x N alone and its partial sums are added in chunk order);
- *   - the image backbone is not differentiated: dz is handed back for whoever owns z.
+ *   - the image backbone is not this object's: dz is handed back for whoever owns z -- pd_vit_trainer (pd_engine_vit_train.h) takes it on
+ *     to the backbone's parameters.
  * Conventions are those of pd_engine.h (return codes, pd_last_error, `stream` = hipStream_t as void *).  Both calls are asynchronous on
  * `stream`; after pd_trainer_create nothing synchronises with the host and nothing is allocated.
  */

@@ -64,6 +64,19 @@ class pd_vit_weights(C.Structure):
                 + [("layers", pd_vit_layer_weights * 16)])
 
 
+class pd_vit_layer_grads(C.Structure):
+    """include/pd_engine_vit_train.h: where each tensor's gradient goes (mirrors pd_vit_layer_weights; None = not wanted)"""
+    _fields_ = list(pd_vit_layer_weights._fields_)
+
+
+class pd_vit_weight_grads(C.Structure):
+    """include/pd_engine_vit_train.h: mirrors the pointer members of pd_vit_weights"""
+    _fields_ = ([(n, C.c_void_p) for n in ("patch_w", "patch_b", "cls_token", "pos_embed", "norm_w", "norm_b")]
+                + [("layers", pd_vit_layer_grads * 16)])
+
+
+PD_VIT_TRAIN_MAX_TOKENS, PD_VIT_TRAIN_MAX_SCALES = 256, 8   # include/pd_engine_vit_train.h: tokens per image and scale; scales per call
+
 # pd_ggs_cfg.reserved flags and pd_engine_set_option ids (include/pd_engine.h; tests/test_host_cpu.py checks them against the header)
 PD_GGS_CFG_FORCE_ONE_HOP = 1
 PD_GGS_CFG_NO_LDS_STAGING = 2
@@ -162,6 +175,13 @@ TRAIN_SIGNATURES = {
     "pd_train_debug_relu": (_i, [_vp, _i, _vp, C.c_longlong, _vp]),
     "pd_trainer_check_async": (_i, [_vp]),
 }
+# the exports of include/pd_engine_vit_train.h: the image backbone with gradients (again a table of its own)
+VIT_TRAIN_SIGNATURES = {
+    "pd_vit_trainer_create": (_i, [C.POINTER(pd_vit_weights), _i, _i, _i, C.POINTER(_vp)]),
+    "pd_vit_trainer_destroy": (None, [_vp]),
+    "pd_vit_train_forward": (_i, [_vp, C.POINTER(pd_vit_weights), _vp, _i, _i, _i, C.POINTER(C.c_double), _i, C.POINTER(_vp), _vp, _vp]),
+    "pd_vit_train_backward": (_i, [_vp, C.POINTER(pd_vit_weights), _vp, C.POINTER(pd_vit_weight_grads), _vp]),
+}
 
 _lib = None
 
@@ -191,7 +211,7 @@ def load():
             "There is no CPU fallback.")
     import torch  # noqa: F401  (loads the HIP runtime first)
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-    for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **TRAIN_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **TRAIN_SIGNATURES, **VIT_TRAIN_SIGNATURES}.items():
         if os.environ.get("PD_ENGINE_LIB") and not hasattr(lib, name):
             continue              # an older build under A / B lacks the newest debug exports
         fn = getattr(lib, name)   # AttributeError here = library does not match the header

@@ -1,0 +1,421 @@
+// pd_vit_train.hip -- the image backbone with gradients (include/pd_engine_vit_train.h): the multi-scale DINO ViT-S/16
+// forward with an activation stash, and its backward from dS/dz to every backbone parameter.  Kernels: pd_train_kernels.h (every matrix
+// product, LayerNorm backward, column sums, split reductions, key-tiled attention -- launched unchanged) and pd_vit_train_kernels.h.
+//
+// Replaces (paths relative to the reference's pose_diffusion/): the autograd graph of models/image_feature_extractor.py:57-87 over the
+// torch.hub dino_vits16 backbone (:40-42) that train.py back-propagates when IMAGE_FEATURE_EXTRACTOR.freeze is False (all three configs).
+//
+// Forward, per scale in call order, on the caller's live weights:
+//   im2col of the prepared images -> patch GEMM -> token assembly (+ cls, + pos) -> per block { LN1 (+stats) -> qkv GEMM -> attention ->
+//   proj GEMM + residual -> LN2 (+stats) -> fc1 GEMM (pre-activation stashed) -> GELU -> fc2 GEMM + residual } -> final LayerNorm of the CLS
+//   rows, added into z; the last scale divides by n_scales.
+// The residual stream is never updated in place: hres[i] is the stream at sublayer input i (2 L + 1 arrays per scale), which IS the stash.
+// Backward, per scale in REVERSE call order: final LayerNorm -> per block in reverse { GELU recomputed, fc2, GELU', fc1, LN2, proj,
+//   attention (two launches), qkv, LN1 } -> token assembly adjoint -> patch GEMM's weight gradient.  The first scale it runs writes every
+//   gradient, the later ones add to it (the GEMM's resid = C path, pd_vt_reduce_acc_kernel).  Then cls_token / pos_embed from the
+//   scales' per-token position gradients in call order (pd_vt_posgrid_kernel).
+#include "pd_vit_train_kernels.h"
+#include "../../include/pd_engine_vit_train.h"
+
+#include <algorithm>
+#include <string.h>
+
+#define VT_EPS 1e-6f                // DINO's partial(nn.LayerNorm, eps=1e-6)
+
+struct PdVtLayerStash {
+    float *stats1, *stats2;         // [rows, 2] (mean, rstd)
+    float *qkv, *ctx, *pre;         // [rows, 3 d], [rows, d], [rows, ff] (fc1 output before the GELU)
+};
+
+struct PdVtScale {                  // one scale of the pending forward
+    int gh, gw, P, T, M;            // token grid, patches and tokens per image, token rows of the scale
+    size_t row0;                    // its first row in every stash array
+    int resampled;                  // its position table came from the caller (bicubic resampling of the trained grid)
+};
+
+struct pd_vit_trainer {
+    int d = 0, nhead = 0, hd = 0, ff = 0, layers = 0, grid0 = 0;
+    int max_images = 0, max_rows = 0, max_scales = 0;
+    // stash
+    float *cols = nullptr;                               // [rows, 768] im2col rows (a scale's n P rows at its row0)
+    float *hres[2 * 16 + 1] = {};                        // [rows, d] each
+    PdVtLayerStash L[16] = {};
+    float *fstats = nullptr;                             // [max_scales][max_images][2] final LayerNorm statistics
+    // scratch
+    float *hn = nullptr, *dres = nullptr, *dhn = nullptr, *act = nullptr, *dff = nullptr, *dqkv = nullptr;
+    float *la_stats = nullptr;                           // [rows nhead, 4] between the two phases of the attention backward
+    float *dpos = nullptr;                               // [max_scales][PD_VT_MAX_TOKENS][d] per-token position gradients
+    float *ws = nullptr;                                 // split-reduction workspaces, as in pd_trainer
+    double *ws_col = nullptr;
+    float *ws_d = nullptr;                               // [VT_DGRAD_MAX_CHUNKS][rows, d] partial data gradients of a long reduction
+    int pend_n = 0, pend_scales = 0;                     // images / scales of the pending forward (0: none)
+    PdVtScale pend[PD_VIT_TRAIN_MAX_SCALES] = {};
+    PdDevAllocs mem{"pd_vit_trainer_create"};
+};
+
+// ---- launch helpers: pd_train.hip's, with the accumulate switch of a gradient summed over scales -------------------------------------
+// the chunks of a reduction over M token rows: a function of M alone (pd_trainer's rule)
+static void vt_chunks(int M, int *n_chunks, int *rows) {
+    int n = std::min(PD_TR_MAX_CHUNKS, (M + 255) / 256);
+    int r = (M + n - 1) / n;
+    r = (r + 31) / 32 * 32;
+    *rows = r;
+    *n_chunks = (M + r - 1) / r;
+}
+
+static void vt_gemm_launch(const PdTrGemm &g, int nz, hipStream_t s) {
+    hipLaunchKernelGGL(pd_tr_gemm_kernel<false>, dim3((g.J + 63) / 64, (g.I + 63) / 64, nz), dim3(256), 0, s, g, PdTrDrop{});
+}
+
+// Y[M, Nout] = X[M, K] W[Nout, K]^T + b (+ resid)
+static void vt_linear(const float *X, const float *W, const float *b, float *Y, int M, int Nout, int K, const float *resid, hipStream_t s) {
+    PdTrGemm g;
+    memset(&g, 0, sizeof(g));
+    g.A = X; g.a_rs = K; g.a_cs = 1; g.a_rfast = 1;
+    g.B = W; g.b_rs = 1; g.b_cs = K; g.b_rfast = 1;
+    g.C = Y; g.ldc = Nout; g.bias = b; g.resid = resid; g.ldr = Nout;
+    g.I = M; g.J = Nout; g.R = K; g.r_chunk = K;
+    vt_gemm_launch(g, 1, s);
+}
+
+// dX[M, K] = dY[M, Nout] W (W [Nout, K]).  A reduction of more than VT_DGRAD_SPLIT terms (qkv's 1152, fc1's 1536) is cut into chunks of
+// VT_DGRAD_CHUNK whose partial sums are added in chunk order: one fmaf chain over 1536 terms left norm2 / proj gradients 3.4 x further from
+// float64 than torch's blocked sums are (profiles/vit_train_parity.txt).  The cut depends on the layer's width alone.
+#define VT_DGRAD_SPLIT 512
+#define VT_DGRAD_CHUNK 384
+#define VT_DGRAD_MAX_CHUNKS 4
+static void vt_dgrad(pd_vit_trainer *tr, const float *dY, const float *W, float *dX, int M, int Nout, int K, hipStream_t s) {
+    const int nch = Nout > VT_DGRAD_SPLIT ? (Nout + VT_DGRAD_CHUNK - 1) / VT_DGRAD_CHUNK : 1;
+    PdTrGemm g;
+    memset(&g, 0, sizeof(g));
+    g.A = dY; g.a_rs = Nout; g.a_cs = 1; g.a_rfast = 1;
+    g.B = W; g.b_rs = K; g.b_cs = 1; g.b_rfast = 0;
+    g.C = nch > 1 ? tr->ws_d : dX; g.ldc = K;
+    g.I = M; g.J = K; g.R = Nout; g.r_chunk = nch > 1 ? VT_DGRAD_CHUNK : Nout;
+    vt_gemm_launch(g, nch, s);
+    if (nch > 1) {
+        const long long total = (long long)M * K;
+        hipLaunchKernelGGL(pd_tr_reduce_kernel<float>, dim3((unsigned)std::min<long long>((total + 255) / 256, 2048)), dim3(256), 0, s, tr->ws_d, total, nch, dX);
+    }
+}
+
+// dW[Nout, K] (+)= sum_m dY[m, :]^T X[m, :] over the chunks of M, partials added in chunk order; db[Nout] (+)= sum_m dY[m, :] likewise
+static void vt_wgrad(pd_vit_trainer *tr, const float *dY, const float *X, float *dW, float *db, int M, int Nout, int K, bool acc, hipStream_t s) {
+    int nch, rows;
+    vt_chunks(M, &nch, &rows);
+    if (dW) {
+        PdTrGemm g;
+        memset(&g, 0, sizeof(g));
+        g.A = dY; g.a_rs = 1; g.a_cs = Nout; g.a_rfast = 0;
+        g.B = X; g.b_rs = K; g.b_cs = 1; g.b_rfast = 0;
+        g.C = nch > 1 ? tr->ws : dW; g.ldc = K;
+        if (nch == 1 && acc) {
+            g.resid = dW;
+            g.ldr = K;
+        }
+        g.I = Nout; g.J = K; g.R = M; g.r_chunk = rows;
+        vt_gemm_launch(g, nch, s);
+        if (nch > 1) {
+            const long long total = (long long)Nout * K;
+            const dim3 grid((unsigned)std::min<long long>((total + 255) / 256, 2048));
+            if (acc) hipLaunchKernelGGL(pd_vt_reduce_acc_kernel<float>, grid, dim3(256), 0, s, tr->ws, total, nch, dW);
+            else hipLaunchKernelGGL(pd_tr_reduce_kernel<float>, grid, dim3(256), 0, s, tr->ws, total, nch, dW);
+        }
+    }
+    if (db) {
+        hipLaunchKernelGGL(pd_tr_colsum_kernel<false>, dim3((Nout + 63) / 64, nch), dim3(256), 0, s, dY, (long long)Nout, nullptr, 0LL, nullptr, M, Nout, rows,
+                           nullptr, tr->ws_col);
+        if (acc) hipLaunchKernelGGL(pd_vt_reduce_acc_kernel<double>, dim3((Nout + 255) / 256), dim3(256), 0, s, tr->ws_col, (long long)Nout, nch, db);
+        else hipLaunchKernelGGL(pd_tr_reduce_kernel<double>, dim3((Nout + 255) / 256), dim3(256), 0, s, tr->ws_col, (long long)Nout, nch, db);
+    }
+}
+
+// LayerNorm's dgamma (+)= sum_m dy xhat, dbeta (+)= sum_m dy
+static void vt_ln_param_grads(pd_vit_trainer *tr, const float *dy, const float *x, const float *stats, float *dgamma, float *dbeta, int M, int D, bool acc,
+                              hipStream_t s) {
+    if (!dgamma && !dbeta) return;
+    int nch, rows;
+    vt_chunks(M, &nch, &rows);
+    double *pa = tr->ws_col, *pb = tr->ws_col + (size_t)PD_TR_MAX_CHUNKS * D;     // [chunks][D] each
+    hipLaunchKernelGGL(pd_tr_colsum_kernel<true>, dim3((D + 63) / 64, nch), dim3(256), 0, s, dy, (long long)D, x, (long long)D, stats, M, D, rows, pa, pb);
+    const dim3 grid((D + 255) / 256);
+    if (acc) {
+        if (dgamma) hipLaunchKernelGGL(pd_vt_reduce_acc_kernel<double>, grid, dim3(256), 0, s, pa, (long long)D, nch, dgamma);
+        if (dbeta) hipLaunchKernelGGL(pd_vt_reduce_acc_kernel<double>, grid, dim3(256), 0, s, pb, (long long)D, nch, dbeta);
+    } else {
+        if (dgamma) hipLaunchKernelGGL(pd_tr_reduce_kernel<double>, grid, dim3(256), 0, s, pa, (long long)D, nch, dgamma);
+        if (dbeta) hipLaunchKernelGGL(pd_tr_reduce_kernel<double>, grid, dim3(256), 0, s, pb, (long long)D, nch, dbeta);
+    }
+}
+
+static unsigned vt_blocks(size_t total, unsigned cap) { return (unsigned)std::min<size_t>((total + 255) / 256, cap); }
+
+// ---- shape checks ----------------------------------------------------------------------------
+static int vt_shape_check(const pd_vit_weights *w, const char *who) {
+    const char *msg = nullptr;
+    if (w->dim != 384) msg = "dim must be 384";
+    else if (w->num_heads != 6) msg = "num_heads must be 6 (head dim 64)";
+    else if (w->mlp_hidden != 1536) msg = "mlp_hidden must be 1536";
+    else if (w->patch_size != PD_VT_PATCH) msg = "patch_size must be 16";
+    else if (w->depth < 1 || w->depth > 16) msg = "depth must be in [1, 16]";
+    else if (w->pos_grid < 1 || w->pos_grid > 15) msg = "pos_grid must be in [1, 15]";
+    if (msg) {
+        pd_set_error("%s: unsupported ViT shape: %s (dim=%d heads=%d mlp=%d patch=%d depth=%d pos_grid=%d)", who, msg, w->dim, w->num_heads, w->mlp_hidden,
+                     w->patch_size, w->depth, w->pos_grid);
+        return PD_ERR_UNSUPPORTED;
+    }
+    return PD_OK;
+}
+
+extern "C" int pd_vit_trainer_create(const pd_vit_weights *shape, int max_images, int max_rows, int max_scales, pd_vit_trainer **out) {
+    if (!shape || !out) {
+        pd_set_error("pd_vit_trainer_create: invalid argument: NULL shape or out");
+        return PD_ERR_INVALID_ARG;
+    }
+    *out = nullptr;
+    if (max_images < 1 || max_rows < 2 || max_scales < 1 || max_scales > PD_VIT_TRAIN_MAX_SCALES) {
+        pd_set_error("pd_vit_trainer_create: invalid argument: max_images=%d (>= 1), max_rows=%d (>= 2), max_scales=%d (1 .. %d)", max_images, max_rows,
+                     max_scales, PD_VIT_TRAIN_MAX_SCALES);
+        return PD_ERR_INVALID_ARG;
+    }
+    PD_TRY(vt_shape_check(shape, "pd_vit_trainer_create"));
+    pd_vit_trainer *tr = new pd_vit_trainer();
+    tr->d = shape->dim; tr->nhead = shape->num_heads; tr->hd = tr->d / tr->nhead; tr->ff = shape->mlp_hidden; tr->layers = shape->depth;
+    tr->grid0 = shape->pos_grid;
+    tr->max_images = max_images; tr->max_rows = max_rows; tr->max_scales = max_scales;
+    const size_t rows = (size_t)max_rows, d = tr->d, ff = tr->ff;
+    int rc = PD_OK;
+#define VT_A(p, n) if (rc == PD_OK) rc = tr->mem.alloc(&(p), (size_t)(n), true)
+    VT_A(tr->cols, rows * PD_VT_KP);
+    for (int i = 0; i <= 2 * tr->layers; ++i) VT_A(tr->hres[i], rows * d);
+    for (int l = 0; l < tr->layers; ++l) {
+        VT_A(tr->L[l].stats1, rows * 2); VT_A(tr->L[l].stats2, rows * 2);
+        VT_A(tr->L[l].qkv, rows * 3 * d); VT_A(tr->L[l].ctx, rows * d); VT_A(tr->L[l].pre, rows * ff);
+    }
+    VT_A(tr->fstats, (size_t)max_scales * max_images * 2);
+    VT_A(tr->hn, rows * d); VT_A(tr->dres, rows * d); VT_A(tr->dhn, rows * d); VT_A(tr->act, rows * ff); VT_A(tr->dff, rows * ff); VT_A(tr->dqkv, rows * 3 * d);
+    VT_A(tr->la_stats, rows * tr->nhead * PD_TR_LA_STATS);
+    VT_A(tr->dpos, (size_t)max_scales * PD_VT_MAX_TOKENS * d);
+    VT_A(tr->ws, std::max(ff * d, d * (size_t)PD_VT_KP) * PD_TR_MAX_CHUNKS);
+    VT_A(tr->ws_col, 2 * std::max(ff, 3 * d) * PD_TR_MAX_CHUNKS);
+    VT_A(tr->ws_d, (size_t)VT_DGRAD_MAX_CHUNKS * rows * d);
+#undef VT_A
+    // dynamic-LDS limits are per-process attributes of the kernels: the family's bound (256 keys, head dim 128), as pd_trainer_create sets them
+    if (rc == PD_OK) rc = pd_set_lds(pd_tr_lattn_kernel<false>, pd_tr_lattn_lds(PD_TR_LA_MAX_N, PD_TR_MAX_HD));
+    if (rc == PD_OK) rc = pd_set_lds(pd_tr_lattn_bwd_rows_kernel<false>, pd_tr_lattn_bwd_rows_lds(PD_TR_LA_MAX_N, PD_TR_MAX_HD));
+    if (rc == PD_OK) rc = pd_set_lds(pd_tr_lattn_bwd_keys_kernel<false>, pd_tr_lattn_bwd_keys_lds(PD_TR_LA_MAX_N, PD_TR_MAX_HD));
+    if (rc == PD_OK && hipDeviceSynchronize() != hipSuccess) rc = PD_ERR_HIP;
+    if (rc != PD_OK) {
+        if (rc == PD_ERR_HIP) pd_set_error("pd_vit_trainer_create: a HIP call failed: %s", hipGetErrorString(hipGetLastError()));
+        delete tr;
+        return rc;
+    }
+    *out = tr;
+    return PD_OK;
+}
+
+extern "C" void pd_vit_trainer_destroy(pd_vit_trainer *tr) { delete tr; }
+
+static int vt_weights_match(const pd_vit_trainer *tr, const pd_vit_weights *w, const char *who) {
+    if (!w) {
+        pd_set_error("%s: invalid argument: NULL weights", who);
+        return PD_ERR_INVALID_ARG;
+    }
+    if (w->dim != tr->d || w->num_heads != tr->nhead || w->mlp_hidden != tr->ff || w->depth != tr->layers || w->patch_size != PD_VT_PATCH ||
+        w->pos_grid != tr->grid0) {
+        pd_set_error("%s: invalid argument w: its shape fields differ from the shape this trainer was created for", who);
+        return PD_ERR_INVALID_ARG;
+    }
+    bool ok = w->patch_w && w->patch_b && w->cls_token && w->pos_embed && w->norm_w && w->norm_b;
+    for (int l = 0; l < tr->layers && ok; ++l) {
+        const pd_vit_layer_weights &L = w->layers[l];
+        ok = L.norm1_w && L.norm1_b && L.qkv_w && L.qkv_b && L.proj_w && L.proj_b && L.norm2_w && L.norm2_b && L.fc1_w && L.fc1_b && L.fc2_w && L.fc2_b;
+    }
+    if (!ok) {
+        pd_set_error("%s: invalid argument w: a weight pointer is NULL", who);
+        return PD_ERR_INVALID_ARG;
+    }
+    return PD_OK;
+}
+
+extern "C" int pd_vit_train_forward(pd_vit_trainer *tr, const pd_vit_weights *w, const float *images, int n, int H, int W,
+                                    const double *scale_factors, int n_scales, const float *const *pos, float *z_out, void *stream) {
+    const char *who = "pd_vit_train_forward";
+    if (!tr) {
+        pd_set_error("%s: invalid argument: NULL trainer", who);
+        return PD_ERR_INVALID_ARG;
+    }
+    if (!images || !z_out || !scale_factors) {
+        pd_set_error("%s: invalid argument: images, scale_factors and z_out must not be NULL", who);
+        return PD_ERR_INVALID_ARG;
+    }
+    if (n < 1 || H < 1 || W < 1 || n_scales < 1) {
+        pd_set_error("%s: invalid argument: n=%d, H=%d, W=%d and n_scales=%d must be positive", who, n, H, W, n_scales);
+        return PD_ERR_INVALID_ARG;
+    }
+    PD_TRY(vt_weights_match(tr, w, who));
+    if (n_scales > tr->max_scales) {
+        pd_set_error("%s: n_scales=%d exceeds the limit of %d scales this trainer was created for", who, n_scales, tr->max_scales);
+        return PD_ERR_UNSUPPORTED;
+    }
+    if (n > tr->max_images) {
+        pd_set_error("%s: n=%d exceeds the capacity of %d images this trainer was created for", who, n, tr->max_images);
+        return PD_ERR_UNSUPPORTED;
+    }
+    PdVtScale sc[PD_VIT_TRAIN_MAX_SCALES];
+    float inv_sf[PD_VIT_TRAIN_MAX_SCALES];
+    int same_size[PD_VIT_TRAIN_MAX_SCALES];
+    size_t rows = 0;
+    for (int i = 0; i < n_scales; ++i) {
+        const double sf = scale_factors[i];
+        if (!(sf > 0.0)) {
+            pd_set_error("%s: invalid argument scale_factors[%d]=%g: a scale factor must be positive", who, i, sf);
+            return PD_ERR_INVALID_ARG;
+        }
+        const bool identity = sf == 1.0;
+        const int hs = identity ? H : (int)floor((double)H * sf), wsz = identity ? W : (int)floor((double)W * sf);   // torch: floor(size * scale) in double
+        PdVtScale &S = sc[i];
+        S.gh = hs / PD_VT_PATCH; S.gw = wsz / PD_VT_PATCH; S.P = S.gh * S.gw; S.T = S.P + 1;
+        if (S.gh < 1 || S.gw < 1) {
+            pd_set_error("%s: scale %d (%g) leaves %d x %d pixels: below the limit of one whole 16 x 16 patch", who, i, sf, hs, wsz);
+            return PD_ERR_UNSUPPORTED;
+        }
+        if ((long long)S.gh * S.gw + 1 > PD_VT_MAX_TOKENS) {
+            pd_set_error("%s: scale %d (%g) gives %lld tokens per image (%d x %d pixels): the limit is %d tokens per image", who, i, sf,
+                         (long long)S.gh * S.gw + 1, hs, wsz, PD_VT_MAX_TOKENS);
+            return PD_ERR_UNSUPPORTED;
+        }
+        const bool trained = S.gh == tr->grid0 && S.gw == tr->grid0;
+        S.resampled = (pos && pos[i] && !trained) ? 1 : 0;      // (torch's resampling of a grid onto its own size is a copy: such a table IS pos_embed)
+        if (!S.resampled && !trained) {
+            pd_set_error("%s: invalid argument pos[%d]: NULL, but the scale's %d x %d token grid is not the trained %d x %d one and needs the "
+                         "resampled position table", who, i, S.gh, S.gw, tr->grid0, tr->grid0);
+            return PD_ERR_INVALID_ARG;
+        }
+        S.M = n * S.T;
+        S.row0 = rows;
+        rows += (size_t)S.M;
+        inv_sf[i] = (float)(1.0 / sf);          // torch: float(1 / scale_factor) as the coordinate scale
+        same_size[i] = identity ? 1 : 0;
+    }
+    if (rows > (size_t)tr->max_rows) {
+        pd_set_error("%s: %d images give %zu token rows over the %d scales: beyond the capacity of %d token rows this trainer was created for", who, n,
+                     rows, n_scales, tr->max_rows);
+        return PD_ERR_UNSUPPORTED;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    tr->pend_n = tr->pend_scales = 0;
+    const int d = tr->d, ff = tr->ff, Lc = tr->layers;
+    const float scale = 1.0f / sqrtf((float)tr->hd);
+    for (int i = 0; i < n_scales; ++i) {
+        const PdVtScale &S = sc[i];
+        const int M = S.M, rb = (M + 3) / 4;
+        const size_t r0 = S.row0;
+        float *cols = tr->cols + r0 * PD_VT_KP;
+        hipLaunchKernelGGL(pd_vt_im2col_kernel, dim3(vt_blocks((size_t)n * S.P * PD_VT_KP, 8192)), dim3(256), 0, s, images, n, H, W, S.gh, S.gw, inv_sf[i], same_size[i],
+                           cols);
+        vt_linear(cols, w->patch_w, w->patch_b, tr->hn, n * S.P, d, PD_VT_KP, nullptr, s);
+        hipLaunchKernelGGL(pd_vt_assemble_kernel, dim3(vt_blocks((size_t)M * d, 4096)), dim3(256), 0, s, tr->hn, w->cls_token,
+                           S.resampled ? pos[i] : w->pos_embed, n, S.T, d, tr->hres[0] + r0 * d);
+        for (int l = 0; l < Lc; ++l) {
+            const pd_vit_layer_weights &Wl = w->layers[l];
+            const PdVtLayerStash &St = tr->L[l];
+            float *h0 = tr->hres[2 * l] + r0 * d, *h1 = tr->hres[2 * l + 1] + r0 * d, *h2 = tr->hres[2 * l + 2] + r0 * d;
+            float *qkv = St.qkv + r0 * 3 * d, *ctx = St.ctx + r0 * d, *pre = St.pre + r0 * ff;
+            hipLaunchKernelGGL(pd_vt_ln_kernel, dim3(rb), dim3(256), 0, s, h0, tr->hn, Wl.norm1_w, Wl.norm1_b, M, d, VT_EPS, St.stats1 + r0 * 2);
+            vt_linear(tr->hn, Wl.qkv_w, Wl.qkv_b, qkv, M, 3 * d, d, nullptr, s);
+            hipLaunchKernelGGL(pd_tr_lattn_kernel<false>, dim3(n * tr->nhead, (S.T + PD_TR_LA_ROWS - 1) / PD_TR_LA_ROWS), dim3(256), pd_tr_lattn_lds(S.T, tr->hd),
+                               s, qkv, ctx, S.T, tr->nhead, tr->hd, d, scale, PdTrDrop{});
+            vt_linear(ctx, Wl.proj_w, Wl.proj_b, h1, M, d, d, h0, s);
+            hipLaunchKernelGGL(pd_vt_ln_kernel, dim3(rb), dim3(256), 0, s, h1, tr->hn, Wl.norm2_w, Wl.norm2_b, M, d, VT_EPS, St.stats2 + r0 * 2);
+            vt_linear(tr->hn, Wl.fc1_w, Wl.fc1_b, pre, M, ff, d, nullptr, s);
+            hipLaunchKernelGGL(pd_vt_gelu_kernel, dim3(vt_blocks((size_t)M * ff / 4, 4096)), dim3(256), 0, s, (const float4 *)pre, (float4 *)tr->act,
+                               (size_t)M * ff / 4);
+            vt_linear(tr->act, Wl.fc2_w, Wl.fc2_b, h2, M, d, ff, h1, s);
+        }
+        hipLaunchKernelGGL(pd_vt_final_kernel, dim3((n + 3) / 4), dim3(256), 0, s, tr->hres[2 * Lc] + r0 * d, n, S.T, d, w->norm_w, w->norm_b, VT_EPS,
+                           i == 0 ? 1 : 0, i == n_scales - 1 ? 1 : 0, n_scales, z_out, tr->fstats + (size_t)i * tr->max_images * 2);
+    }
+    PD_HIP_CHECK(hipGetLastError());
+    memcpy(tr->pend, sc, sizeof(sc[0]) * n_scales);
+    tr->pend_n = n;
+    tr->pend_scales = n_scales;
+    return PD_OK;
+}
+
+extern "C" int pd_vit_train_backward(pd_vit_trainer *tr, const pd_vit_weights *w, const float *g_z, const pd_vit_weight_grads *grads, void *stream) {
+    const char *who = "pd_vit_train_backward";
+    if (!tr || !g_z || !grads) {
+        pd_set_error("%s: invalid argument: NULL trainer, g_z or grads", who);
+        return PD_ERR_INVALID_ARG;
+    }
+    if (tr->pend_n < 1 || tr->pend_scales < 1) {
+        pd_set_error("%s: no forward is pending (pd_vit_train_forward fills the stash that one backward consumes)", who);
+        return PD_ERR_STATE;
+    }
+    PD_TRY(vt_weights_match(tr, w, who));
+    hipStream_t s = (hipStream_t)stream;
+    const int n = tr->pend_n, ns = tr->pend_scales, d = tr->d, ff = tr->ff, Lc = tr->layers;
+    tr->pend_n = tr->pend_scales = 0;
+    const float scale = 1.0f / sqrtf((float)tr->hd);
+    for (int i = ns - 1; i >= 0; --i) {
+        const PdVtScale &S = tr->pend[i];
+        const bool acc = i != ns - 1;                      // the first scale that runs writes, the others add
+        const int M = S.M, rb = (M + 3) / 4, T = S.T;
+        const size_t r0 = S.row0;
+        const float *hl = tr->hres[2 * Lc] + r0 * d, *fst = tr->fstats + (size_t)i * tr->max_images * 2;
+        if (grads->norm_w || grads->norm_b)
+            hipLaunchKernelGGL(pd_vt_final_param_kernel, dim3((d + 255) / 256), dim3(256), 0, s, g_z, hl, fst, n, T, d, ns, acc ? 1 : 0, grads->norm_w,
+                               grads->norm_b);
+        hipLaunchKernelGGL(pd_vt_final_bwd_kernel, dim3(rb), dim3(256), 0, s, g_z, hl, fst, w->norm_w, n, T, d, ns, tr->dres);
+        for (int l = Lc - 1; l >= 0; --l) {
+            const pd_vit_layer_weights &Wl = w->layers[l];
+            const pd_vit_layer_grads &G = grads->layers[l];
+            const PdVtLayerStash &St = tr->L[l];
+            const float *h0 = tr->hres[2 * l] + r0 * d, *h1 = tr->hres[2 * l + 1] + r0 * d;
+            const float *qkv = St.qkv + r0 * 3 * d, *ctx = St.ctx + r0 * d, *pre = St.pre + r0 * ff;
+            const float *st1 = St.stats1 + r0 * 2, *st2 = St.stats2 + r0 * 2;
+            const size_t n4 = (size_t)M * ff / 4;
+            // MLP sublayer: dres is the gradient of fc2's output
+            if (G.fc2_w) hipLaunchKernelGGL(pd_vt_gelu_kernel, dim3(vt_blocks(n4, 4096)), dim3(256), 0, s, (const float4 *)pre, (float4 *)tr->act, n4);
+            vt_wgrad(tr, tr->dres, tr->act, G.fc2_w, G.fc2_b, M, d, ff, acc, s);
+            vt_dgrad(tr, tr->dres, Wl.fc2_w, tr->dff, M, d, ff, s);
+            hipLaunchKernelGGL(pd_vt_gelu_bwd_kernel, dim3(vt_blocks(n4, 4096)), dim3(256), 0, s, (const float4 *)pre, (float4 *)tr->dff, n4);
+            if (G.fc1_w) hipLaunchKernelGGL(pd_vt_ln_kernel, dim3(rb), dim3(256), 0, s, h1, tr->hn, Wl.norm2_w, Wl.norm2_b, M, d, VT_EPS, (float *)nullptr);
+            vt_wgrad(tr, tr->dff, tr->hn, G.fc1_w, G.fc1_b, M, ff, d, acc, s);
+            vt_dgrad(tr, tr->dff, Wl.fc1_w, tr->dhn, M, ff, d, s);
+            vt_ln_param_grads(tr, tr->dhn, h1, st2, G.norm2_w, G.norm2_b, M, d, acc, s);
+            hipLaunchKernelGGL(pd_tr_ln_bwd_kernel, dim3(rb), dim3(256), 0, s, tr->dhn, h1, st2, Wl.norm2_w, M, d, tr->dres);
+            // attention sublayer: dres is the gradient of proj's output
+            vt_wgrad(tr, tr->dres, ctx, G.proj_w, G.proj_b, M, d, d, acc, s);
+            vt_dgrad(tr, tr->dres, Wl.proj_w, tr->dhn, M, d, d, s);
+            {
+                const dim3 rows(n * tr->nhead, (T + PD_TR_LA_ROWS - 1) / PD_TR_LA_ROWS), keys(n * tr->nhead, pd_tr_la_tiles(T));
+                hipLaunchKernelGGL(pd_tr_lattn_bwd_rows_kernel<false>, rows, dim3(256), pd_tr_lattn_bwd_rows_lds(T, tr->hd), s, qkv, tr->dhn, tr->dqkv,
+                                   tr->la_stats, T, tr->nhead, tr->hd, d, scale, PdTrDrop{});
+                hipLaunchKernelGGL(pd_tr_lattn_bwd_keys_kernel<false>, keys, dim3(256), pd_tr_lattn_bwd_keys_lds(T, tr->hd), s, qkv, tr->dhn, tr->dqkv,
+                                   tr->la_stats, T, tr->nhead, tr->hd, d, scale, PdTrDrop{});
+            }
+            if (G.qkv_w) hipLaunchKernelGGL(pd_vt_ln_kernel, dim3(rb), dim3(256), 0, s, h0, tr->hn, Wl.norm1_w, Wl.norm1_b, M, d, VT_EPS, (float *)nullptr);
+            vt_wgrad(tr, tr->dqkv, tr->hn, G.qkv_w, G.qkv_b, M, 3 * d, d, acc, s);
+            vt_dgrad(tr, tr->dqkv, Wl.qkv_w, tr->dhn, M, 3 * d, d, s);
+            vt_ln_param_grads(tr, tr->dhn, h0, st1, G.norm1_w, G.norm1_b, M, d, acc, s);
+            hipLaunchKernelGGL(pd_tr_ln_bwd_kernel, dim3(rb), dim3(256), 0, s, tr->dhn, h0, st1, Wl.norm1_w, M, d, tr->dres);
+        }
+        // token assembly adjoint: dres is the gradient of x0.  dhn receives the patch GEMM's output gradient in compact rows
+        hipLaunchKernelGGL(pd_vt_assemble_bwd_kernel, dim3((T * d + 255) / 256), dim3(256), 0, s, tr->dres, n, T, d, tr->dhn,
+                           tr->dpos + (size_t)i * PD_VT_MAX_TOKENS * d);
+        vt_wgrad(tr, tr->dhn, tr->cols + r0 * PD_VT_KP, grads->patch_w, grads->patch_b, n * S.P, d, PD_VT_KP, acc, s);
+    }
+    if (grads->cls_token || grads->pos_embed) {
+        const int g = tr->grid0;
+        for (int i = 0; i < ns; ++i) {                     // call order
+            const PdVtScale &S = tr->pend[i];
+            const float ry = (float)(1.0 / (((double)S.gh + 0.1) / (double)g)), rx = (float)(1.0 / (((double)S.gw + 0.1) / (double)g));
+            hipLaunchKernelGGL(pd_vt_posgrid_kernel, dim3(((1 + g * g) * d + 255) / 256), dim3(256), 0, s, tr->dpos + (size_t)i * PD_VT_MAX_TOKENS * d, S.gh,
+                               S.gw, g, d, S.resampled, i > 0 ? 1 : 0, ry, rx, grads->pos_embed, grads->cls_token);
+        }
+    }
+    PD_HIP_CHECK(hipGetLastError());
+    return PD_OK;
+}

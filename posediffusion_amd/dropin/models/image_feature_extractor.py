@@ -6,6 +6,10 @@ no network here, and the hub code is third-party.  This module therefore owns a 
 names (``_net.patch_embed.proj``, ``_net.cls_token``, ``_net.pos_embed``, ``_net.blocks.N.{norm1, attn.qkv, attn.proj,
 norm2, mlp.fc1, mlp.fc2}``, ``_net.norm``), so a PoseDiffusion checkpoint (or a plain ``dino_vits16`` checkpoint loaded
 into ``._net``) loads with ``strict=True``; the arithmetic runs in the engine (`posediffusion_amd.vit.VitEngine`).
+By default the features carry no grad.  With ``engine_grad = True``, ``freeze`` False and grad mode on, ``forward`` returns a z that is
+differentiable with respect to ``_net``'s parameters (`posediffusion_amd.vit_train.VitTrainer`, include/pd_engine_vit_train.h: exact
+fp32 from the live parameters, at most 256 tokens per image and scale); together with ``GaussianDiffusion.engine_grad`` the training
+branch of ``PoseDiffusionModel`` then fills ``.grad`` on the denoiser AND the backbone, as the reference's train.py does.
 Other backbones of the reference (``resnet*``, ``dinov2*``) are not implemented: inject a callable as ``.backbone``."""
 import torch
 import torch.nn as nn
@@ -48,6 +52,8 @@ class MultiScaleImageFeatureExtractor(nn.Module):
         super().__init__()
         self.freeze, self.scale_factors, self.modelname = freeze, scale_factors, modelname
         self.backbone = None                       # optional injected callable images[BN,3,H,W] -> [BN,C]
+        self.engine_grad = False                   # True (with freeze False and grad mode on): forward returns a z that is differentiable with respect
+                                                   # to _net's parameters, computed by the backbone trainer; False: the no_grad inference path
         if modelname == "dino_vits16":
             self._net = _dino_vits16_parameters()
             self._output_dim = self._net.norm.weight.shape[0]                   # :42
@@ -78,8 +84,30 @@ class MultiScaleImageFeatureExtractor(nn.Module):
             self.__dict__["_pd_vit_cache"] = ent
         return ent[1]
 
-    @torch.no_grad()
+    def _wants_engine_grad(self) -> bool:
+        """Both opt-ins and something to differentiate: ``engine_grad`` set, not frozen, grad mode on, a ``_net`` parameter that requires grad."""
+        return (bool(getattr(self, "engine_grad", False)) and not self.freeze and torch.is_grad_enabled() and self.backbone is None
+                and self._net is not None and any(p.requires_grad for p in self._net.parameters()))
+
     def forward(self, image_rgb: torch.Tensor) -> torch.Tensor:
+        if self._wants_engine_grad():
+            return self._forward_grad(image_rgb)
+        return self._forward_no_grad(image_rgb)
+
+    def _forward_grad(self, image_rgb: torch.Tensor) -> torch.Tensor:
+        """z that carries grad with respect to ``_net``'s parameters, from the backbone trainer (posediffusion_amd/vit_train.py)."""
+        from posediffusion_amd import host
+        from posediffusion_amd.vit_train import multiscale_with_grad, token_rows
+        if self._net.norm.weight.device.type != "cuda":
+            raise RuntimeError("posediffusion_amd image features run only on an AMD GPU; move the model with .to('cuda')")
+        if len(self.scale_factors) <= 0:
+            raise ValueError(f"Wrong format of self.scale_factors: {self.scale_factors}")                 # :68-69
+        n, _, H, W = image_rgb.shape
+        tr = host.get_vit_trainer(self._net, n, n * token_rows(H, W, self.scale_factors), len(self.scale_factors))
+        return multiscale_with_grad(tr, self._net, image_rgb, self.scale_factors)
+
+    @torch.no_grad()
+    def _forward_no_grad(self, image_rgb: torch.Tensor) -> torch.Tensor:
         if self.backbone is not None:
             return self.backbone(image_rgb)
         if self._net is None:

@@ -107,6 +107,30 @@ def get_trainer(denoiser: torch.nn.Module, diffuser: torch.nn.Module, B: int, N:
     return tr
 
 
+def get_vit_trainer(net: torch.nn.Module, n_images: int, rows: int, n_scales: int = 3):
+    """``VitTrainer`` (posediffusion_amd/vit_train.py) for this live DINO parameter tree.  Like ``get_trainer`` it is cached on shape,
+    device and capacity -- NOT on parameter versions: it reads the parameters where they are at every call, so an optimiser step keeps
+    it.  ``rows``: token rows of one call summed over its scales (``n_images * vit_train.token_rows(H, W, scale_factors)``).  The
+    capacity never shrinks."""
+    from .vit_train import VitTrainer, shape_from_module
+    dev = net.pos_embed.device
+    if dev.type != "cuda":
+        raise RuntimeError("the backbone training branch of posediffusion_amd runs only on an AMD GPU "
+                           f"(model is on {dev}); move the model with .to('cuda'). There is no CPU fallback.")
+    key = (tuple(sorted(shape_from_module(net).items())), str(dev))
+    cache = net.__dict__.setdefault("_pd_vit_trainer_cache", {})
+    ent = cache.get("t")
+    if ent is not None and ent[0] == key and ent[1].max_images >= n_images and ent[1].max_rows >= rows and ent[1].max_scales >= n_scales:
+        return ent[1]
+    if ent is not None:
+        if ent[0] == key:                                         # never shrink capacity
+            n_images, rows, n_scales = max(n_images, ent[1].max_images), max(rows, ent[1].max_rows), max(n_scales, ent[1].max_scales)
+        ent[1].close()
+    tr = VitTrainer(shape_from_module(net), max_images=max(n_images, 1), max_rows=max(rows, 2), max_scales=max(n_scales, 1), device=dev)
+    cache["t"] = (key, tr)
+    return tr
+
+
 def _raise_trainer_limit(tr, max_frames: int):
     if int(max_frames) > 64 and int(max_frames) > tr.max_frames:     # (the default asks the library nothing: today's calls, also under A / B with an older build)
         tr.set_max_frames(int(max_frames))
