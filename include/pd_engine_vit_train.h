@@ -59,8 +59,10 @@ void pd_vit_trainer_destroy(pd_vit_trainer *tr);
  * scale_factors: HOST array [n_scales]; a scale of 1 keeps the pixels, another one resizes to floor(H s) x floor(W s) bilinearly
  * (align_corners=False), as pd_vit_forward_scale does.  pos: HOST array [n_scales] of DEVICE pointers: pos[s] = DINO's
  * interpolate_pos_encoding table [1 + gh gw, dim] of scale s's token grid, resampled by the caller from the live pos_embed; NULL = the
- * scale runs on the trained pos_grid x pos_grid grid and reads w->pos_embed itself (so does a scale whose grid is the trained one although
- * a table was given: resampling a grid onto its own size is a copy).
+ * scale runs on the trained table and reads w->pos_embed itself.  A scale is on the trained table only when its token grid is pos_grid x
+ * pos_grid AND its pixel height equals its width (DINO's rule; a table given for such a scale is ignored, it IS pos_embed).  A 224 x 232
+ * input has the trained 14 x 14 grid but is resampled by DINO with scale factor 14.1 / 14, which is not a copy: it needs its table, and
+ * NULL there is PD_ERR_INVALID_ARG like for any other resampled scale.
  * PD_ERR_UNSUPPORTED, naming the limit, before anything is launched: a scale of more than PD_VIT_TRAIN_MAX_TOKENS tokens per image or of
  * no whole patch, n_scales above the trainer's max_scales, n above max_images, more token rows than max_rows.  Bad arguments:
  * PD_ERR_INVALID_ARG naming the argument.  A refused call leaves a pending stash as it was. */

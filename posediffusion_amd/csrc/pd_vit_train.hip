@@ -78,12 +78,13 @@ static void vt_linear(const float *X, const float *W, const float *b, float *Y, 
     vt_gemm_launch(g, 1, s);
 }
 
-// dX[M, K] = dY[M, Nout] W (W [Nout, K]).  A reduction of more than VT_DGRAD_SPLIT terms (qkv's 1152, fc1's 1536) is cut into chunks of
-// VT_DGRAD_CHUNK whose partial sums are added in chunk order: one fmaf chain over 1536 terms left norm2 / proj gradients 3.4 x further from
-// float64 than torch's blocked sums are (profiles/vit_train_parity.txt).  The cut depends on the layer's width alone.
-#define VT_DGRAD_SPLIT 512
-#define VT_DGRAD_CHUNK 384
-#define VT_DGRAD_MAX_CHUNKS 4
+// dX[M, K] = dY[M, Nout] W (W [Nout, K]).  A reduction of more than VT_DGRAD_SPLIT terms (every layer: 384, qkv's 1152, fc1's 1536) is cut
+// into chunks of VT_DGRAD_CHUNK whose partial sums are added in chunk order: one fmaf chain over 1536 terms left norm2 / proj gradients
+// 3.4 x further from float64 than torch's blocked sums are, and chains of 384 still left a cancelling column sum behind qkv's data
+// gradient twice as far as chains of 96 do (profiles/vit_train_parity.txt sections 1 and 5).  The cut depends on the layer's width alone.
+#define VT_DGRAD_SPLIT 128
+#define VT_DGRAD_CHUNK 96
+#define VT_DGRAD_MAX_CHUNKS 16
 static void vt_dgrad(pd_vit_trainer *tr, const float *dY, const float *W, float *dX, int M, int Nout, int K, hipStream_t s) {
     const int nch = Nout > VT_DGRAD_SPLIT ? (Nout + VT_DGRAD_CHUNK - 1) / VT_DGRAD_CHUNK : 1;
     PdTrGemm g;
@@ -285,8 +286,10 @@ extern "C" int pd_vit_train_forward(pd_vit_trainer *tr, const pd_vit_weights *w,
                          (long long)S.gh * S.gw + 1, hs, wsz, PD_VT_MAX_TOKENS);
             return PD_ERR_UNSUPPORTED;
         }
-        const bool trained = S.gh == tr->grid0 && S.gw == tr->grid0;
-        S.resampled = (pos && pos[i] && !trained) ? 1 : 0;      // (torch's resampling of a grid onto its own size is a copy: such a table IS pos_embed)
+        // DINO's interpolate_pos_encoding returns pos_embed only for the trained grid AND hs == wsz.  Unequal pixel sizes on the trained grid
+        // (224 x 232) are resampled with scale factor (g + 0.1) / g per axis, which is no copy: source coordinates move by up to 0.1 cell
+        const bool trained = S.gh == tr->grid0 && S.gw == tr->grid0 && hs == wsz;
+        S.resampled = (pos && pos[i] && !trained) ? 1 : 0;
         if (!S.resampled && !trained) {
             pd_set_error("%s: invalid argument pos[%d]: NULL, but the scale's %d x %d token grid is not the trained %d x %d one and needs the "
                          "resampled position table", who, i, S.gh, S.gw, tr->grid0, tr->grid0);

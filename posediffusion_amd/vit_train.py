@@ -5,7 +5,8 @@ no LayerNorm folding and no repacking (``VitEngine``, the inference path, keeps 
 
 ``multiscale_with_grad`` is the ``torch.autograd.Function`` that hands the engine's gradients to autograd; PyTorch keeps the optimiser.
 DINO's ``interpolate_pos_encoding`` (bicubic resampling of the trained position grid) is evaluated with torch at every call from the
-live ``pos_embed`` -- nothing is cached, so nothing can go stale; its adjoint runs on the engine.  Exact fp32, at most 256 tokens per
+live ``pos_embed`` -- nothing is cached, so nothing can go stale; its adjoint runs on the engine.  (One geometry is written out instead:
+the trained grid under unequal pixel sizes, where torch's GPU kernel copies -- ``_pos_for``.)  Exact fp32, at most 256 tokens per
 image and scale (240 x 272 pixels).  Images are data: no image gradient.  No CPU path: a missing library or GPU raises."""
 from __future__ import annotations
 
@@ -50,6 +51,26 @@ def scaled_size(H: int, W: int, sf: float):
 def token_rows(H: int, W: int, scale_factors: Sequence[float]) -> int:
     """Token rows one image takes over the scales of a call (the unit of ``VitTrainer``'s capacity)."""
     return sum(1 + (hs // PATCH) * (ws // PATCH) for hs, ws in (scaled_size(H, W, sf) for sf in scale_factors))
+
+
+def _bicubic_matrix(g_out: int, g: int) -> torch.Tensor:
+    """[g_out, g] float32 on the CPU: one axis of torch's bicubic upsample (A = -0.75, align_corners=False) of a g-long grid onto g_out cells
+    under DINO's scale factor (g_out + 0.1) / g -- source coordinate float(1 / scale_factor) (o + 0.5) - 0.5, not clamped, the four taps
+    clamped to [0, g - 1] (pd_vt_cubic_taps' arithmetic)."""
+    rscale = torch.tensor(1.0 / ((g_out + 0.1) / g), dtype=torch.float32)
+    src = rscale * (torch.arange(g_out, dtype=torch.float32) + 0.5) - 0.5
+    fl = torch.floor(src)
+    t = src - fl
+
+    def near(x):                    # |x| <= 1
+        return ((1.25 * x - 2.25) * x) * x + 1.0
+
+    def far(x):                     # 1 < |x| < 2
+        return ((-0.75 * x + 3.75) * x - 6.0) * x + 3.0
+    m = torch.zeros(g_out, g)
+    for k, w in enumerate((far(t + 1.0), near(t), near(1.0 - t), far(2.0 - t))):
+        m.index_put_((torch.arange(g_out), (fl.long() - 1 + k).clamp(0, g - 1)), w, accumulate=True)
+    return m
 
 
 def _fill(struct, depth: int, ptr_of) -> None:
@@ -125,6 +146,14 @@ class VitTrainer:
         if (gh == g and gw == g and hs == ws) or gh < 1 or gw < 1:       # (no whole patch: pd_vit_train_forward refuses the scale and names the limit)
             return None
         pe = pos_embed.detach().reshape(1, 1 + g * g, self.dim)
+        if gh == g and gw == g:
+            # The trained grid under unequal pixel sizes (224 x 232).  DINO resamples it with scale factor (g + 0.1) / g per axis, and the
+            # reference's float64 CPU kernel evaluates that: source coordinates move by up to 0.1 cell.  torch's GPU bicubic kernel COPIES
+            # whenever input and output sizes are equal, whatever the scale factor, so here the resampling is written out as its two tap
+            # matrices (the taps pd_vt_posgrid_kernel's adjoint uses).
+            m = _bicubic_matrix(g, g).to(pe.device)
+            pp = torch.einsum("yi,xj,ijc->yxc", m, m, pe[0, 1:].reshape(g, g, self.dim))
+            return torch.cat((pe[0, :1], pp.reshape(-1, self.dim)), dim=0).contiguous()
         # (DINO names the first spatial size w; it passes (w0 / g, h0 / g) for the (rows, cols) of the grid)
         w0, h0 = gh + 0.1, gw + 0.1
         pp = F.interpolate(pe[:, 1:].reshape(1, g, g, self.dim).permute(0, 3, 1, 2), scale_factor=(w0 / g, h0 / g), mode="bicubic")

@@ -167,6 +167,19 @@ def grid15(seed, depth, dtype):
     return net.to(dtype).eval()
 
 
+def grid1(seed, depth, dtype):
+    """a network trained on a 1 x 1 position grid (DinoViT(img_size=16)): make_vit's parameters, its own 2-row position table -- every
+    other grid is a resampling of ONE cell, whose four taps per axis all clamp to it"""
+    src = _base(seed, depth)
+    net = VO.DinoViT(img_size=16, depth=depth)
+    with torch.no_grad():
+        own = net.state_dict()
+        for k, v in src.state_dict().items():
+            if k != "pos_embed":
+                own[k].copy_(v)
+    return net.to(dtype).eval()
+
+
 def _peaked(seed, depth, dtype, factor):
     net = _base(seed, depth)
     with torch.no_grad():
