@@ -96,4 +96,18 @@ __device__ __forceinline__ float pd_wave_sum(float v) {
     for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
     return v;
 }
+// LayerNorm statistics of one row of D floats held by one wave, as the trainers' forward kernels compute them: lane-strided sum -> mean,
+// fmaf sum of squared deviations -> rstd = 1 / sqrt(var + eps)
+__device__ __forceinline__ void pd_wave_row_stats(const float *__restrict__ src, int D, int lane, float eps, float *mean_out, float *rstd_out) {
+    float s = 0.0f;
+    for (int c = lane; c < D; c += 64) s += src[c];
+    const float mean = pd_wave_sum(s) / (float)D;
+    float q = 0.0f;
+    for (int c = lane; c < D; c += 64) {
+        const float e = src[c] - mean;
+        q = fmaf(e, e, q);
+    }
+    *mean_out = mean;
+    *rstd_out = 1.0f / sqrtf(pd_wave_sum(q) / (float)D + eps);
+}
 

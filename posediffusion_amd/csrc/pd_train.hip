@@ -15,7 +15,10 @@
 // before the weight, bias and data gradients of out_proj / linear2 read it.  A call without dropout launches the DROP = false kernels.
 // Attention: N <= 64 runs pd_tr_attn_kernel / pd_tr_attn_bwd_kernel (a sequence whole in LDS), N > 64 -- admitted once PD_TR_OPT_MAX_FRAMES
 // raises the limit -- the key-tiled pd_tr_lattn_* kernels (pd_train_lattn.h); the family a forward ran is remembered with its stash.
+// This file is the only one that compiles pd_train_kernels.h: the launch helpers below (pd_train_launch.h) are the backbone trainer's way
+// to the same kernels (pd_vit_train.hip), with acc = false here and its per-scale accumulate switch there.
 #include "pd_train_kernels.h"
+#include "pd_train_launch.h"
 #include "../../include/pd_engine_train.h"
 
 #include <algorithm>
@@ -41,10 +44,8 @@ struct pd_trainer {
     // scratch
     float *hn = nullptr, *dres = nullptr, *dhn = nullptr, *dff = nullptr, *dqkv = nullptr;
     float *dres_m = nullptr;                             // [M, d] dres masked at site 1 / 3 (dropout backward)
-    float *la_stats = nullptr;                           // [M nhead, 4] (row maximum, 1 / sum, rs x 2) between the two phases of the key-tiled backward
     float *dy_hid = nullptr, *dhid = nullptr, *gout = nullptr, *demb_t = nullptr, *dtemb = nullptr, *dts = nullptr;
-    float *ws = nullptr;                                 // split-reduction workspaces: weight-gradient partials [chunks][Nout x K] ...
-    double *ws_col = nullptr;                            // ... and column-sum partials [2][chunks][C]
+    PdTrWork wk = {};                                    // split-reduction workspaces; la_stats [M nhead, 4] (row maximum, 1 / sum, rs x 2)
     size_t ws_floats = 0, ws_col_floats = 0;
     unsigned int *d_err = nullptr;
     int pend_B = 0, pend_N = 0;                          // B, N of the pending forward (0: none)
@@ -57,17 +58,22 @@ struct pd_trainer {
     PdDevAllocs mem{"pd_trainer_create"};
 };
 
-// ---- launch helpers ------------------------------------------------------------------------
-// the chunks of a reduction over M token rows: a function of M alone
-static void pd_tr_chunks(int M, int *n_chunks, int *rows) {
-    int n = std::min(PD_TR_MAX_CHUNKS, (M + 255) / 256);
-    int r = (M + n - 1) / n;
-    r = (r + 31) / 32 * 32;
-    *rows = r;
-    *n_chunks = (M + r - 1) / r;
+// ---- launch helpers shared with pd_vit_train.hip (pd_train_launch.h) --------------------------
+int pd_tr_set_attention_lds() {
+    const size_t sf = pd_tr_attn_lds(PD_TR_MAX_N, PD_TR_MAX_HD), sb = pd_tr_attn_bwd_lds(PD_TR_MAX_N, PD_TR_MAX_HD);
+    const size_t lf = pd_tr_lattn_lds(PD_TR_LA_MAX_N, PD_TR_MAX_HD), la = pd_tr_lattn_bwd_rows_lds(PD_TR_LA_MAX_N, PD_TR_MAX_HD),
+                 lb = pd_tr_lattn_bwd_keys_lds(PD_TR_LA_MAX_N, PD_TR_MAX_HD);
+    const struct { const void *kernel; size_t bytes; } bounds[] = {
+        {(const void *)pd_tr_attn_kernel<false>, sf}, {(const void *)pd_tr_attn_kernel<true>, sf},
+        {(const void *)pd_tr_attn_bwd_kernel<false>, sb}, {(const void *)pd_tr_attn_bwd_kernel<true>, sb},
+        {(const void *)pd_tr_lattn_kernel<false>, lf}, {(const void *)pd_tr_lattn_kernel<true>, lf},
+        {(const void *)pd_tr_lattn_bwd_rows_kernel<false>, la}, {(const void *)pd_tr_lattn_bwd_rows_kernel<true>, la},
+        {(const void *)pd_tr_lattn_bwd_keys_kernel<false>, lb}, {(const void *)pd_tr_lattn_bwd_keys_kernel<true>, lb}};
+    for (const auto &b : bounds) PD_HIP_CHECK(hipFuncSetAttribute(b.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b.bytes));
+    return PD_OK;
 }
 
-static void tr_gemm_launch(const PdTrGemm &g, int nz, hipStream_t s, const PdTrDrop *dr = nullptr) {
+void pd_tr_gemm_launch(const PdTrGemm &g, int nz, hipStream_t s, const PdTrDrop *dr) {
     const dim3 grid((g.J + 63) / 64, (g.I + 63) / 64, nz);
     if (dr) hipLaunchKernelGGL(pd_tr_gemm_kernel<true>, grid, dim3(256), 0, s, g, *dr);
     else hipLaunchKernelGGL(pd_tr_gemm_kernel<false>, grid, dim3(256), 0, s, g, PdTrDrop{});
@@ -83,15 +89,15 @@ static const PdTrDrop *tr_site(const PdTrDrop &base, unsigned sites, int layer, 
 }
 
 // Y[M, Nout] = X[M, K] W[Nout, K]^T + b (+ ReLU) (+ dropout `dr`) (+ resid)
-static void tr_linear(const float *X, const float *W, const float *b, float *Y, int M, int Nout, int K, int relu, const float *resid, hipStream_t s,
-                      const PdTrDrop *dr = nullptr) {
+void pd_tr_linear(const float *X, const float *W, const float *b, float *Y, int M, int Nout, int K, int relu, const float *resid, hipStream_t s,
+                  const PdTrDrop *dr) {
     PdTrGemm g;
     memset(&g, 0, sizeof(g));
     g.A = X; g.a_rs = K; g.a_cs = 1; g.a_rfast = 1;
     g.B = W; g.b_rs = 1; g.b_cs = K; g.b_rfast = 1;
     g.C = Y; g.ldc = Nout; g.bias = b; g.relu = relu; g.resid = resid; g.ldr = Nout;
     g.I = M; g.J = Nout; g.R = K; g.r_chunk = K;
-    tr_gemm_launch(g, 1, s, dr);
+    pd_tr_gemm_launch(g, 1, s, dr);
 }
 
 // dX[M, Kw] = dY[M, Nout] W[:, koff : koff + Kw] (W [Nout, ldw]), masked by aux (mode 1 / 2), written or accumulated into dX
@@ -107,11 +113,21 @@ static void tr_dgrad(const float *dY, const float *W, int ldw, int koff, float *
         g.ldr = Kw;
     }
     g.I = M; g.J = Kw; g.R = Nout; g.r_chunk = Nout;
-    tr_gemm_launch(g, 1, s, dr);
+    pd_tr_gemm_launch(g, 1, s, dr);
 }
 
-// dW[Nout, K] = sum_m dY[m, :]^T X[m, :] over the chunks of M, partials added in chunk order; db[Nout] = sum_m dY[m, :] likewise
-static void tr_wgrad(pd_trainer *tr, const float *dY, const float *X, float *dW, float *db, int M, int Nout, int K, hipStream_t s) {
+// out[e] (+)= ws[0][e] + ... + ws[nz - 1][e]
+template <typename T>
+static void tr_reduce(const T *ws, long long total, int nz, float *out, bool acc, hipStream_t s) {
+    const dim3 grid((unsigned)std::min<long long>((total + 255) / 256, 2048));      // (a column sum's total, at most 8192, never meets the cap)
+    if (acc) hipLaunchKernelGGL((pd_tr_reduce_kernel<T, true>), grid, dim3(256), 0, s, ws, total, nz, out);
+    else hipLaunchKernelGGL((pd_tr_reduce_kernel<T, false>), grid, dim3(256), 0, s, ws, total, nz, out);
+}
+
+void pd_tr_reduce_launch(const float *ws, long long total, int nz, float *out, hipStream_t s) { tr_reduce(ws, total, nz, out, false, s); }
+
+// dW[Nout, K] (+)= sum_m dY[m, :]^T X[m, :] over the chunks of M, partials added in chunk order; db[Nout] (+)= sum_m dY[m, :] likewise
+void pd_tr_wgrad(const PdTrWork &wk, const float *dY, const float *X, float *dW, float *db, int M, int Nout, int K, bool acc, hipStream_t s) {
     int nch, rows;
     pd_tr_chunks(M, &nch, &rows);
     if (dW) {
@@ -119,35 +135,44 @@ static void tr_wgrad(pd_trainer *tr, const float *dY, const float *X, float *dW,
         memset(&g, 0, sizeof(g));
         g.A = dY; g.a_rs = 1; g.a_cs = Nout; g.a_rfast = 0;
         g.B = X; g.b_rs = K; g.b_cs = 1; g.b_rfast = 0;
-        g.C = nch > 1 ? tr->ws : dW; g.ldc = K;
-        g.I = Nout; g.J = K; g.R = M; g.r_chunk = rows;
-        tr_gemm_launch(g, nch, s);
-        if (nch > 1) {
-            const long long total = (long long)Nout * K;
-            hipLaunchKernelGGL(pd_tr_reduce_kernel<float>, dim3((unsigned)std::min<long long>((total + 255) / 256, 2048)), dim3(256), 0, s, tr->ws, total, nch, dW);
+        g.C = nch > 1 ? wk.ws : dW; g.ldc = K;
+        if (nch == 1 && acc) {
+            g.resid = dW;
+            g.ldr = K;
         }
+        g.I = Nout; g.J = K; g.R = M; g.r_chunk = rows;
+        pd_tr_gemm_launch(g, nch, s);
+        if (nch > 1) tr_reduce(wk.ws, (long long)Nout * K, nch, dW, acc, s);
     }
     if (db) {
         hipLaunchKernelGGL(pd_tr_colsum_kernel<false>, dim3((Nout + 63) / 64, nch), dim3(256), 0, s, dY, (long long)Nout, nullptr, 0LL, nullptr, M, Nout, rows,
-                           nullptr, tr->ws_col);
-        hipLaunchKernelGGL(pd_tr_reduce_kernel<double>, dim3((Nout + 255) / 256), dim3(256), 0, s, tr->ws_col, (long long)Nout, nch, db);
+                           nullptr, wk.ws_col);
+        tr_reduce(wk.ws_col, (long long)Nout, nch, db, acc, s);
     }
 }
 
-// LayerNorm's dgamma = sum_m dy xhat, dbeta = sum_m dy
-static void tr_ln_param_grads(pd_trainer *tr, const float *dy, const float *x, const float *stats, float *dgamma, float *dbeta, int M, int D, hipStream_t s) {
+// LayerNorm's dgamma (+)= sum_m dy xhat, dbeta (+)= sum_m dy
+void pd_tr_ln_param_grads(const PdTrWork &wk, const float *dy, const float *x, const float *stats, float *dgamma, float *dbeta, int M, int D, bool acc,
+                          hipStream_t s) {
     if (!dgamma && !dbeta) return;
     int nch, rows;
     pd_tr_chunks(M, &nch, &rows);
-    double *pa = tr->ws_col, *pb = tr->ws_col + (size_t)PD_TR_MAX_CHUNKS * D;     // [chunks][D] each
+    double *pa = wk.ws_col, *pb = wk.ws_col + (size_t)PD_TR_MAX_CHUNKS * D;       // [chunks][D] each
     hipLaunchKernelGGL(pd_tr_colsum_kernel<true>, dim3((D + 63) / 64, nch), dim3(256), 0, s, dy, (long long)D, x, (long long)D, stats, M, D, rows, pa, pb);
-    if (dgamma) hipLaunchKernelGGL(pd_tr_reduce_kernel<double>, dim3((D + 255) / 256), dim3(256), 0, s, pa, (long long)D, nch, dgamma);
-    if (dbeta) hipLaunchKernelGGL(pd_tr_reduce_kernel<double>, dim3((D + 255) / 256), dim3(256), 0, s, pb, (long long)D, nch, dbeta);
+    if (dgamma) tr_reduce(pa, (long long)D, nch, dgamma, acc, s);
+    if (dbeta) tr_reduce(pb, (long long)D, nch, dbeta, acc, s);
+}
+
+void pd_tr_ln_launch(const float *in, float *out, const float *gamma, const float *beta, int M, int D, float eps, float *stats, hipStream_t s) {
+    hipLaunchKernelGGL(pd_tr_ln_kernel, dim3((M + 3) / 4), dim3(256), 0, s, in, out, gamma, beta, M, D, eps, stats);
+}
+
+void pd_tr_ln_bwd_launch(const float *dy, const float *x, const float *stats, const float *gamma, int M, int D, float *dres, hipStream_t s) {
+    hipLaunchKernelGGL(pd_tr_ln_bwd_kernel, dim3((M + 3) / 4), dim3(256), 0, s, dy, x, stats, gamma, M, D, dres);
 }
 
 // attention forward of one layer: the short kernel (a sequence whole in LDS) or the key-tiled one
-static void tr_attn_launch(const pd_trainer *tr, bool tiled, const float *qkv, float *ctx, int B, int N, float scale, const PdTrDrop *dr, hipStream_t s) {
-    const int nh = tr->nhead, hd = tr->hd, d = tr->d;
+void pd_tr_attn_launch(bool tiled, const float *qkv, float *ctx, int B, int N, int nh, int hd, int d, float scale, const PdTrDrop *dr, hipStream_t s) {
     if (tiled) {
         const dim3 grid(B * nh, (N + PD_TR_LA_ROWS - 1) / PD_TR_LA_ROWS);
         if (dr) hipLaunchKernelGGL(pd_tr_lattn_kernel<true>, grid, dim3(256), pd_tr_lattn_lds(N, hd), s, qkv, ctx, N, nh, hd, d, scale, *dr);
@@ -160,18 +185,17 @@ static void tr_attn_launch(const pd_trainer *tr, bool tiled, const float *qkv, f
 }
 
 // attention backward of one layer: dqkv from qkv and dctx; tiled = phase A (dQ, row statistics) then phase B (dK, dV)
-static void tr_attn_bwd_launch(const pd_trainer *tr, bool tiled, const float *qkv, const float *dctx, float *dqkv, int B, int N, float scale,
-                               const PdTrDrop *dr, hipStream_t s) {
-    const int nh = tr->nhead, hd = tr->hd, d = tr->d;
+void pd_tr_attn_bwd_launch(bool tiled, const float *qkv, const float *dctx, float *dqkv, float *la_stats, int B, int N, int nh, int hd, int d,
+                           float scale, const PdTrDrop *dr, hipStream_t s) {
     if (tiled) {
         const dim3 rows(B * nh, (N + PD_TR_LA_ROWS - 1) / PD_TR_LA_ROWS), keys(B * nh, pd_tr_la_tiles(N));
         const size_t la = pd_tr_lattn_bwd_rows_lds(N, hd), lb = pd_tr_lattn_bwd_keys_lds(N, hd);
         if (dr) {
-            hipLaunchKernelGGL(pd_tr_lattn_bwd_rows_kernel<true>, rows, dim3(256), la, s, qkv, dctx, dqkv, tr->la_stats, N, nh, hd, d, scale, *dr);
-            hipLaunchKernelGGL(pd_tr_lattn_bwd_keys_kernel<true>, keys, dim3(256), lb, s, qkv, dctx, dqkv, tr->la_stats, N, nh, hd, d, scale, *dr);
+            hipLaunchKernelGGL(pd_tr_lattn_bwd_rows_kernel<true>, rows, dim3(256), la, s, qkv, dctx, dqkv, la_stats, N, nh, hd, d, scale, *dr);
+            hipLaunchKernelGGL(pd_tr_lattn_bwd_keys_kernel<true>, keys, dim3(256), lb, s, qkv, dctx, dqkv, la_stats, N, nh, hd, d, scale, *dr);
         } else {
-            hipLaunchKernelGGL(pd_tr_lattn_bwd_rows_kernel<false>, rows, dim3(256), la, s, qkv, dctx, dqkv, tr->la_stats, N, nh, hd, d, scale, PdTrDrop{});
-            hipLaunchKernelGGL(pd_tr_lattn_bwd_keys_kernel<false>, keys, dim3(256), lb, s, qkv, dctx, dqkv, tr->la_stats, N, nh, hd, d, scale, PdTrDrop{});
+            hipLaunchKernelGGL(pd_tr_lattn_bwd_rows_kernel<false>, rows, dim3(256), la, s, qkv, dctx, dqkv, la_stats, N, nh, hd, d, scale, PdTrDrop{});
+            hipLaunchKernelGGL(pd_tr_lattn_bwd_keys_kernel<false>, keys, dim3(256), lb, s, qkv, dctx, dqkv, la_stats, N, nh, hd, d, scale, PdTrDrop{});
         }
     } else if (dr) {
         hipLaunchKernelGGL(pd_tr_attn_bwd_kernel<true>, dim3(B * nh), dim3(256), pd_tr_attn_bwd_lds(N, hd), s, qkv, dctx, dqkv, N, nh, hd, d, scale, *dr);
@@ -237,12 +261,12 @@ extern "C" int pd_trainer_create(const pd_weights *shape, const float *sqrt_alph
     TR_A(tr->hn, rows * d); TR_A(tr->dres, rows * d); TR_A(tr->dres_m, rows * d); TR_A(tr->dhn, rows * d); TR_A(tr->dff, rows * tr->ff); TR_A(tr->dqkv, rows * 3 * d);
     TR_A(tr->dy_hid, rows * tr->hid); TR_A(tr->dhid, rows * tr->hid); TR_A(tr->gout, rows * 9); TR_A(tr->demb_t, rows * 128);
     TR_A(tr->dtemb, (size_t)max_B * 128); TR_A(tr->dts, (size_t)max_B * 128);
-    TR_A(tr->la_stats, rows * tr->nhead * PD_TR_LA_STATS);
+    TR_A(tr->wk.la_stats, rows * tr->nhead * PD_TR_LA_STATS);
     const size_t widest_w = std::max({(size_t)d * tr->Kf, (size_t)3 * d * d, (size_t)tr->ff * d, (size_t)tr->hid * d, (size_t)9 * tr->hid, (size_t)128 * 256});
     tr->ws_floats = widest_w * PD_TR_MAX_CHUNKS;
     const size_t widest_c = std::max({(size_t)3 * d, (size_t)tr->ff, (size_t)tr->hid, (size_t)256});
     tr->ws_col_floats = 2 * widest_c * PD_TR_MAX_CHUNKS;
-    TR_A(tr->ws, tr->ws_floats); TR_A(tr->ws_col, tr->ws_col_floats);
+    TR_A(tr->wk.ws, tr->ws_floats); TR_A(tr->wk.ws_col, tr->ws_col_floats);
     TR_A(tr->d_err, 4);
 #undef TR_A
     if (rc == PD_OK && hipMemcpy(tr->qa, sqrt_alphas_cumprod, T * sizeof(float), hipMemcpyDeviceToDevice) != hipSuccess) rc = PD_ERR_HIP;
@@ -252,18 +276,7 @@ extern "C" int pd_trainer_create(const pd_weights *shape, const float *sqrt_alph
             hipMemcpy(tr->c_recipm1, shape->sqrt_recipm1_alphas_cumprod, T * sizeof(float), hipMemcpyDeviceToDevice) != hipSuccess)
             rc = PD_ERR_HIP;
     }
-    // dynamic-LDS limits are per-process attributes of the kernels: set to the family's bound (64 frames, head dim 128), never from this shape
-    if (rc == PD_OK) rc = pd_set_lds(pd_tr_attn_kernel<false>, pd_tr_attn_lds(PD_TR_MAX_N, PD_TR_MAX_HD));
-    if (rc == PD_OK) rc = pd_set_lds(pd_tr_attn_kernel<true>, pd_tr_attn_lds(PD_TR_MAX_N, PD_TR_MAX_HD));
-    if (rc == PD_OK) rc = pd_set_lds(pd_tr_attn_bwd_kernel<false>, pd_tr_attn_bwd_lds(PD_TR_MAX_N, PD_TR_MAX_HD));
-    if (rc == PD_OK) rc = pd_set_lds(pd_tr_attn_bwd_kernel<true>, pd_tr_attn_bwd_lds(PD_TR_MAX_N, PD_TR_MAX_HD));
-    // the key-tiled kernels likewise: 256 frames, head dim 128
-    if (rc == PD_OK) rc = pd_set_lds(pd_tr_lattn_kernel<false>, pd_tr_lattn_lds(PD_TR_LA_MAX_N, PD_TR_MAX_HD));
-    if (rc == PD_OK) rc = pd_set_lds(pd_tr_lattn_kernel<true>, pd_tr_lattn_lds(PD_TR_LA_MAX_N, PD_TR_MAX_HD));
-    if (rc == PD_OK) rc = pd_set_lds(pd_tr_lattn_bwd_rows_kernel<false>, pd_tr_lattn_bwd_rows_lds(PD_TR_LA_MAX_N, PD_TR_MAX_HD));
-    if (rc == PD_OK) rc = pd_set_lds(pd_tr_lattn_bwd_rows_kernel<true>, pd_tr_lattn_bwd_rows_lds(PD_TR_LA_MAX_N, PD_TR_MAX_HD));
-    if (rc == PD_OK) rc = pd_set_lds(pd_tr_lattn_bwd_keys_kernel<false>, pd_tr_lattn_bwd_keys_lds(PD_TR_LA_MAX_N, PD_TR_MAX_HD));
-    if (rc == PD_OK) rc = pd_set_lds(pd_tr_lattn_bwd_keys_kernel<true>, pd_tr_lattn_bwd_keys_lds(PD_TR_LA_MAX_N, PD_TR_MAX_HD));
+    if (rc == PD_OK) rc = pd_tr_set_attention_lds();
     if (rc == PD_OK && hipDeviceSynchronize() != hipSuccess) rc = PD_ERR_HIP;
     if (rc != PD_OK) {
         if (rc == PD_ERR_HIP) pd_set_error("pd_trainer_create: a HIP call failed: %s", hipGetErrorString(hipGetLastError()));
@@ -376,21 +389,21 @@ static int tr_forward(pd_trainer *tr, const pd_weights *w, const float *x_start,
         hipLaunchKernelGGL(pd_tr_embed_kernel, dim3((unsigned)std::min<size_t>((total + 255) / 256, 4096)), dim3(256), 0, s, xt, z, tr->t_emb, M, N, tr->z,
                            tr->pivot, tr->Kf, tr->emb);
     }
-    tr_linear(tr->emb, w->first_w, w->first_b, tr->hres[0], M, d, tr->Kf, 0, nullptr, s);
+    pd_tr_linear(tr->emb, w->first_w, w->first_b, tr->hres[0], M, d, tr->Kf, 0, nullptr, s);
     const float scale = 1.0f / sqrtf((float)tr->hd);
     for (int l = 0; l < tr->layers; ++l) {
         const pd_layer_weights &W = w->layers[l];
         const PdTrLayerStash &S = tr->L[l];
         float *h0 = tr->hres[2 * l], *h1 = tr->hres[2 * l + 1], *h2 = tr->hres[2 * l + 2];
-        hipLaunchKernelGGL(pd_tr_ln_kernel, dim3(rb), dim3(256), 0, s, h0, tr->hn, W.norm1_w, W.norm1_b, M, d, S.stats1);
-        tr_linear(tr->hn, W.in_proj_w, W.in_proj_b, S.qkv, M, 3 * d, d, 0, nullptr, s);
-        tr_attn_launch(tr, tiled, S.qkv, S.ctx, B, N, scale, tr_site(drop, sites, l, 0, &site), s);
-        tr_linear(S.ctx, W.out_proj_w, W.out_proj_b, h1, M, d, d, 0, h0, s, tr_site(drop, sites, l, 1, &site));
-        hipLaunchKernelGGL(pd_tr_ln_kernel, dim3(rb), dim3(256), 0, s, h1, tr->hn, W.norm2_w, W.norm2_b, M, d, S.stats2);
-        tr_linear(tr->hn, W.linear1_w, W.linear1_b, S.ffa, M, tr->ff, d, 1, nullptr, s, tr_site(drop, sites, l, 2, &site));
-        tr_linear(S.ffa, W.linear2_w, W.linear2_b, h2, M, d, tr->ff, 0, h1, s, tr_site(drop, sites, l, 3, &site));
+        pd_tr_ln_launch(h0, tr->hn, W.norm1_w, W.norm1_b, M, d, 1e-5f, S.stats1, s);
+        pd_tr_linear(tr->hn, W.in_proj_w, W.in_proj_b, S.qkv, M, 3 * d, d, 0, nullptr, s);
+        pd_tr_attn_launch(tiled, S.qkv, S.ctx, B, N, tr->nhead, tr->hd, d, scale, tr_site(drop, sites, l, 0, &site), s);
+        pd_tr_linear(S.ctx, W.out_proj_w, W.out_proj_b, h1, M, d, d, 0, h0, s, tr_site(drop, sites, l, 1, &site));
+        pd_tr_ln_launch(h1, tr->hn, W.norm2_w, W.norm2_b, M, d, 1e-5f, S.stats2, s);
+        pd_tr_linear(tr->hn, W.linear1_w, W.linear1_b, S.ffa, M, tr->ff, d, 1, nullptr, s, tr_site(drop, sites, l, 2, &site));
+        pd_tr_linear(S.ffa, W.linear2_w, W.linear2_b, h2, M, d, tr->ff, 0, h1, s, tr_site(drop, sites, l, 3, &site));
     }
-    tr_linear(tr->hres[2 * tr->layers], w->last0_w, w->last0_b, tr->hid_pre, M, tr->hid, d, 0, nullptr, s);
+    pd_tr_linear(tr->hres[2 * tr->layers], w->last0_w, w->last0_b, tr->hid_pre, M, tr->hid, d, 0, nullptr, s);
     PdTrTail ta;
     memset(&ta, 0, sizeof(ta));
     ta.hid = tr->hid_pre; ta.lnw = w->last_ln_w; ta.lnb = w->last_ln_b; ta.w3 = w->last3_w; ta.b3 = w->last3_b;
@@ -470,9 +483,9 @@ extern "C" int pd_train_backward(pd_trainer *tr, const pd_weights *w, const floa
     tb.g_loss = g_loss; tb.dl = tr->dl; tb.w3 = w->last3_w; tb.lnw = w->last_ln_w; tb.hid = tr->hid_pre; tb.hid_post = tr->hid_post; tb.stats = tr->hid_stats;
     tb.gout = tr->gout; tb.dy = tr->dy_hid; tb.dhid = tr->dhid; tb.M = M; tb.H = hid;
     hipLaunchKernelGGL(pd_tr_tail_bwd_kernel, dim3(rb), dim3(256), 0, s, tb);
-    tr_wgrad(tr, tr->gout, tr->hid_post, grads->last3_w, grads->last3_b, M, 9, hid, s);
-    tr_ln_param_grads(tr, tr->dy_hid, tr->hid_pre, tr->hid_stats, grads->last_ln_w, grads->last_ln_b, M, hid, s);
-    tr_wgrad(tr, tr->dhid, tr->hres[2 * Lc], grads->last0_w, grads->last0_b, M, hid, d, s);
+    pd_tr_wgrad(tr->wk, tr->gout, tr->hid_post, grads->last3_w, grads->last3_b, M, 9, hid, false, s);
+    pd_tr_ln_param_grads(tr->wk, tr->dy_hid, tr->hid_pre, tr->hid_stats, grads->last_ln_w, grads->last_ln_b, M, hid, false, s);
+    pd_tr_wgrad(tr->wk, tr->dhid, tr->hres[2 * Lc], grads->last0_w, grads->last0_b, M, hid, d, false, s);
     tr_dgrad(tr->dhid, w->last0_w, d, 0, tr->dres, M, hid, d, nullptr, 0, false, s);
     const float scale = 1.0f / sqrtf((float)tr->hd);
     for (int l = Lc - 1; l >= 0; --l) {
@@ -489,38 +502,38 @@ extern "C" int pd_train_backward(pd_trainer *tr, const pd_weights *w, const floa
         }
         const PdTrDrop *ffs = tr_site(drop, sites, l, 2, &site);
         if (ffs) site.philox = 0;
-        tr_wgrad(tr, dy2, S.ffa, G.linear2_w, G.linear2_b, M, d, ff, s);
+        pd_tr_wgrad(tr->wk, dy2, S.ffa, G.linear2_w, G.linear2_b, M, d, ff, false, s);
         tr_dgrad(dy2, W.linear2_w, ff, 0, tr->dff, M, d, ff, S.ffa, 1, false, s, ffs);
-        if (G.linear1_w) hipLaunchKernelGGL(pd_tr_ln_kernel, dim3(rb), dim3(256), 0, s, h1, tr->hn, W.norm2_w, W.norm2_b, M, d, S.stats2);
-        tr_wgrad(tr, tr->dff, tr->hn, G.linear1_w, G.linear1_b, M, ff, d, s);
+        if (G.linear1_w) pd_tr_ln_launch(h1, tr->hn, W.norm2_w, W.norm2_b, M, d, 1e-5f, S.stats2, s);
+        pd_tr_wgrad(tr->wk, tr->dff, tr->hn, G.linear1_w, G.linear1_b, M, ff, d, false, s);
         tr_dgrad(tr->dff, W.linear1_w, d, 0, tr->dhn, M, ff, d, nullptr, 0, false, s);
-        tr_ln_param_grads(tr, tr->dhn, h1, S.stats2, G.norm2_w, G.norm2_b, M, d, s);
-        hipLaunchKernelGGL(pd_tr_ln_bwd_kernel, dim3(rb), dim3(256), 0, s, tr->dhn, h1, S.stats2, W.norm2_w, M, d, tr->dres);
+        pd_tr_ln_param_grads(tr->wk, tr->dhn, h1, S.stats2, G.norm2_w, G.norm2_b, M, d, false, s);
+        pd_tr_ln_bwd_launch(tr->dhn, h1, S.stats2, W.norm2_w, M, d, tr->dres, s);
         // attention sublayer: dres is the gradient of out_proj's output
         const float *dy1 = tr->dres;
         if (const PdTrDrop *dr = tr_site(drop, sites, l, 1, &site)) {
             hipLaunchKernelGGL(pd_tr_dropmask_kernel, dim3(mask_blocks), dim3(256), 0, s, tr->dres, tr->dres_m, M, d, *dr);
             dy1 = tr->dres_m;
         }
-        tr_wgrad(tr, dy1, S.ctx, G.out_proj_w, G.out_proj_b, M, d, d, s);
+        pd_tr_wgrad(tr->wk, dy1, S.ctx, G.out_proj_w, G.out_proj_b, M, d, d, false, s);
         tr_dgrad(dy1, W.out_proj_w, d, 0, tr->dhn, M, d, d, nullptr, 0, false, s);
-        tr_attn_bwd_launch(tr, tr->pend_long != 0, S.qkv, tr->dhn, tr->dqkv, B, N, scale, tr_site(drop, sites, l, 0, &site), s);
-        if (G.in_proj_w) hipLaunchKernelGGL(pd_tr_ln_kernel, dim3(rb), dim3(256), 0, s, h0, tr->hn, W.norm1_w, W.norm1_b, M, d, S.stats1);
-        tr_wgrad(tr, tr->dqkv, tr->hn, G.in_proj_w, G.in_proj_b, M, 3 * d, d, s);
+        pd_tr_attn_bwd_launch(tr->pend_long != 0, S.qkv, tr->dhn, tr->dqkv, tr->wk.la_stats, B, N, tr->nhead, tr->hd, d, scale, tr_site(drop, sites, l, 0, &site), s);
+        if (G.in_proj_w) pd_tr_ln_launch(h0, tr->hn, W.norm1_w, W.norm1_b, M, d, 1e-5f, S.stats1, s);
+        pd_tr_wgrad(tr->wk, tr->dqkv, tr->hn, G.in_proj_w, G.in_proj_b, M, 3 * d, d, false, s);
         tr_dgrad(tr->dqkv, W.in_proj_w, d, 0, tr->dhn, M, 3 * d, d, nullptr, 0, false, s);
-        tr_ln_param_grads(tr, tr->dhn, h0, S.stats1, G.norm1_w, G.norm1_b, M, d, s);
-        hipLaunchKernelGGL(pd_tr_ln_bwd_kernel, dim3(rb), dim3(256), 0, s, tr->dhn, h0, S.stats1, W.norm1_w, M, d, tr->dres);
+        pd_tr_ln_param_grads(tr->wk, tr->dhn, h0, S.stats1, G.norm1_w, G.norm1_b, M, d, false, s);
+        pd_tr_ln_bwd_launch(tr->dhn, h0, S.stats1, W.norm1_w, M, d, tr->dres, s);
     }
     // head of the network: dres is the gradient of _first's output
-    tr_wgrad(tr, tr->dres, tr->emb, grads->first_w, grads->first_b, M, d, tr->Kf, s);
+    pd_tr_wgrad(tr->wk, tr->dres, tr->emb, grads->first_w, grads->first_b, M, d, tr->Kf, false, s);
     if (dz_out) tr_dgrad(tr->dres, w->first_w, tr->Kf, PD_TR_FIRST_FIXED, dz_out, M, d, tr->z, nullptr, 0, false, s);
     if (grads->time_w0 || grads->time_b0 || grads->time_w2 || grads->time_b2) {
         tr_dgrad(tr->dres, w->first_w, tr->Kf, 189, tr->demb_t, M, d, 128, nullptr, 0, false, s);
         hipLaunchKernelGGL(pd_tr_tsum_kernel, dim3(B), dim3(128), 0, s, tr->demb_t, N, tr->dtemb);
-        tr_wgrad(tr, tr->dtemb, tr->t_sact, grads->time_w2, grads->time_b2, B, 128, 128, s);
+        pd_tr_wgrad(tr->wk, tr->dtemb, tr->t_sact, grads->time_w2, grads->time_b2, B, 128, 128, false, s);
         if (grads->time_w0 || grads->time_b0) {
             tr_dgrad(tr->dtemb, w->time_w2, 128, 0, tr->dts, B, 128, 128, tr->t_a0, 2, false, s);
-            tr_wgrad(tr, tr->dts, tr->t_emb256, grads->time_w0, grads->time_b0, B, 128, 256, s);
+            pd_tr_wgrad(tr->wk, tr->dts, tr->t_emb256, grads->time_w0, grads->time_b0, B, 128, 256, false, s);
         }
     }
     PD_HIP_CHECK(hipGetLastError());

@@ -9,17 +9,19 @@
 // Determinism: no float atomics anywhere.  A reduction over the token rows (weight gradients, bias gradients, LayerNorm gamma / beta) is
 // cut into chunks whose size depends on M = B x N alone (pd_tr_chunks); every chunk writes its partial sum to a workspace slice and
 // pd_tr_reduce_kernel adds the slices in chunk order.
+//
+// pd_train.hip is the ONE translation unit that includes this file.  The backbone trainer (pd_vit_train.hip) runs the GEMM, the reductions,
+// the column sums, LayerNorm and the key-tiled attention through the launch helpers of pd_train_launch.h, which pd_train.hip defines.
 #pragma once
 #include "pd_denoiser_dev.h"
+#include "pd_train_launch.h"        // PD_TR_MAX_CHUNKS, PD_TR_MAX_HD, PdTrDrop, PdTrGemm
 
 #include <math.h>
 
 #define PD_TR_TILE 64
 #define PD_TR_KC 32
 #define PD_TR_LD 65                 // LDS row stride of a staged tile [KC][64]: both staging patterns and the MFMA reads stay spread over the banks
-#define PD_TR_MAX_CHUNKS 16
 #define PD_TR_FIRST_FIXED 317       // harmonic (180) + x (9) + t_emb (128): the columns of _first before z
-#define PD_TR_MAX_HD 128
 #define PD_TR_MAX_N 64
 #define PD_TR_TAIL_PER 16           // hidden <= 1024 = 16 values per lane
 
@@ -52,38 +54,12 @@ __host__ __device__ __forceinline__ PdTrRand pd_tr_philox(unsigned int c0, unsig
     return r;
 }
 
-// one site of one layer in one call; philox = 0: no mask, the scale alone (the data gradient behind a masked ReLU stash)
-struct PdTrDrop {
-    unsigned int thr, key0, key1, step, ctr2;   // ctr2 = 4 layer + site
-    float scale;                                // 1 / (1 - p), fp32, from the host
-    int philox;
-};
-
 __host__ __device__ __forceinline__ bool pd_tr_keep(const PdTrDrop &dr, unsigned int row, unsigned int col) {
     const PdTrRand r = pd_tr_philox(row >> 2, col, dr.ctr2, dr.step, dr.key0, dr.key1);
     const unsigned int k = row & 3;                     // selected, not indexed: a run-time index would put the four words in scratch
     const unsigned int lo = k & 1 ? r.w[1] : r.w[0], hi = k & 1 ? r.w[3] : r.w[2];
     return (k & 2 ? hi : lo) >= dr.thr;
 }
-
-struct PdTrGemm {
-    const float *A;                 // A(i, r) = A[i * a_rs + r * a_cs]
-    long long a_rs, a_cs;
-    const float *B;                 // B(r, j) = B[r * b_rs + j * b_cs]
-    long long b_rs, b_cs;
-    float *C;                       // C(i, j) = C[i * ldc + j]; slice z of a split reduction starts at C + z * I * ldc
-    long long ldc;
-    const float *bias;              // [J] added per column, or null
-    const float *resid;             // [I, ldr] added last (a residual stream, or C itself to accumulate), or null
-    long long ldr;
-    const float *aux;               // [I, ldaux] the mask operand, or null
-    long long ldaux;
-    int mask_mode;                  // 1: result kept where aux > 0 (ReLU backward from the stashed post-ReLU values); 2: times SiLU'(aux)
-    int relu;                       // ReLU after the bias
-    int I, J, R;
-    int r_chunk;                    // reduction indices per blockIdx.z
-    int a_rfast, b_rfast;           // 1: the reduction index is the contiguous one of that operand in memory (picks the coalesced staging pattern)
-};
 
 // DROP: the epilogue applies `dr` after the ReLU / mask and before the residual add: v = keep ? v scale : 0.  A lane's 16 accumulators are
 // four groups of four consecutive rows at one column, so a group is one Philox call.  DROP = false is the kernel as it was.
@@ -164,13 +140,14 @@ __global__ __launch_bounds__(256) void pd_tr_gemm_kernel(PdTrGemm g, PdTrDrop dr
 }
 
 // out[e] = ws[0][e] + ws[1][e] + ... in slice order (the fixed order of every split reduction); T = float (weight-gradient partials) or
-// double (column-sum partials)
-template <typename T>
+// double (column-sum partials).  ACC: the sum is ADDED to out (the backbone's gradients, accumulated over the scales of a call)
+template <typename T, bool ACC>
 __global__ __launch_bounds__(256) void pd_tr_reduce_kernel(const T *__restrict__ ws, long long total, int nz, float *__restrict__ out) {
     for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long long)gridDim.x * blockDim.x) {
         T s = ws[e];
         for (int z = 1; z < nz; ++z) s += ws[(long long)z * total + e];
-        out[e] = (float)s;
+        if constexpr (ACC) out[e] += (float)s;
+        else out[e] = (float)s;
     }
 }
 
@@ -299,24 +276,18 @@ __global__ __launch_bounds__(256) void pd_tr_embed_kernel(const float *__restric
     }
 }
 
-// LayerNorm over rows [M, D] with its affine, eps 1e-5: one wave per row (the generic path's kernel), also writing stats[m] = (mean, rstd)
+// LayerNorm over rows [M, D] with its affine (eps: the denoiser's 1e-5, DINO's 1e-6): one wave per row (the generic path's kernel), also
+// writing stats[m] = (mean, rstd) when stats is not null
 __global__ __launch_bounds__(256) void pd_tr_ln_kernel(const float *__restrict__ in, float *__restrict__ out, const float *__restrict__ gamma,
-                                                       const float *__restrict__ beta, int M, int D, float *__restrict__ stats) {
+                                                       const float *__restrict__ beta, int M, int D, float eps, float *__restrict__ stats) {
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= M) return;
     const float *src = in + (size_t)row * D;
-    float s = 0.0f;
-    for (int c = lane; c < D; c += 64) s += src[c];
-    const float mean = pd_wave_sum(s) / (float)D;
-    float q = 0.0f;
-    for (int c = lane; c < D; c += 64) {
-        const float e = src[c] - mean;
-        q = fmaf(e, e, q);
-    }
-    const float rstd = 1.0f / sqrtf(pd_wave_sum(q) / (float)D + 1e-5f);
+    float mean, rstd;
+    pd_wave_row_stats(src, D, lane, eps, &mean, &rstd);
     float *dst = out + (size_t)row * D;
     for (int c = lane; c < D; c += 64) dst[c] = (src[c] - mean) * rstd * gamma[c] + beta[c];
-    if (lane == 0) {
+    if (stats && lane == 0) {
         stats[2 * (size_t)row] = mean;
         stats[2 * (size_t)row + 1] = rstd;
     }

@@ -28,9 +28,7 @@
 #define PD_TR_LA_RPW 4              // query rows per wave
 #define PD_TR_LA_ROWS (4 * PD_TR_LA_RPW)   // query rows per workgroup (forward, phase A) and per block of phase B
 #define PD_TR_LA_MAX_TILES 4
-#define PD_TR_LA_MAX_N (PD_TR_LA_TILE * PD_TR_LA_MAX_TILES)
 #define PD_TR_LA_PL (PD_TR_LA_TILE + 1)    // row stride of phase B's P~ / dS blocks
-#define PD_TR_LA_STATS 4            // floats per (b, h, i) between the phases: row maximum, 1 / sum, rs of lanes 0 .. 31, rs of lanes 32 .. 63
 
 constexpr int pd_tr_la_tiles(int N) { return (N + PD_TR_LA_TILE - 1) / PD_TR_LA_TILE; }   // (constexpr: callable from host and device code)
 // dynamic LDS in bytes.  Forward: one K / V tile, the scaled query rows, their probabilities over the tiles
@@ -48,6 +46,9 @@ static inline size_t pd_tr_lattn_bwd_keys_lds(int N, int hd) {
 }
 
 #ifndef PD_TR_LATTN_HOST_ONLY       // (a plain C++ translation unit may include this file for the functions above)
+
+// PD_TR_LA_MAX_N and PD_TR_LA_STATS size both trainers' allocations: pd_train_launch.h holds them (pd_train_kernels.h has included it)
+static_assert(PD_TR_LA_MAX_N == PD_TR_LA_TILE * PD_TR_LA_MAX_TILES, "PD_TR_LA_MAX_N is the keys of PD_TR_LA_MAX_TILES tiles");
 
 // rows i0 .. i0 + 15 of `src` (row stride ld, clamped to row N - 1) times `mul` into dst [16][hd + 4]
 __device__ __forceinline__ void pd_tr_la_stage_rows(const float *__restrict__ src, size_t ld, int i0, int N, int hd, float mul, float *dst) {

@@ -1,6 +1,7 @@
 // pd_vit_train.hip -- the image backbone with gradients (include/pd_engine_vit_train.h): the multi-scale DINO ViT-S/16
-// forward with an activation stash, and its backward from dS/dz to every backbone parameter.  Kernels: pd_train_kernels.h (every matrix
-// product, LayerNorm backward, column sums, split reductions, key-tiled attention -- launched unchanged) and pd_vit_train_kernels.h.
+// forward with an activation stash, and its backward from dS/dz to every backbone parameter.  Kernels: pd_vit_train_kernels.h (the ViT's own,
+// the only device code of this file) and the denoiser trainer's -- every matrix product, LayerNorm forward and backward, column sums, split
+// reductions, key-tiled attention -- through the launch helpers of pd_train_launch.h, which pd_train.hip defines next to the kernels.
 //
 // Replaces (paths relative to the reference's pose_diffusion/): the autograd graph of models/image_feature_extractor.py:57-87 over the
 // torch.hub dino_vits16 backbone (:40-42) that train.py back-propagates when IMAGE_FEATURE_EXTRACTOR.freeze is False (all three configs).
@@ -12,7 +13,7 @@
 // The residual stream is never updated in place: hres[i] is the stream at sublayer input i (2 L + 1 arrays per scale), which IS the stash.
 // Backward, per scale in REVERSE call order: final LayerNorm -> per block in reverse { GELU recomputed, fc2, GELU', fc1, LN2, proj,
 //   attention (two launches), qkv, LN1 } -> token assembly adjoint -> patch GEMM's weight gradient.  The first scale it runs writes every
-//   gradient, the later ones add to it (the GEMM's resid = C path, pd_vt_reduce_acc_kernel).  Then cls_token / pos_embed from the
+//   gradient, the later ones add to it (the helpers' acc: the GEMM's resid = C path, the accumulating reduce).  Then cls_token / pos_embed from the
 //   scales' per-token position gradients in call order (pd_vt_posgrid_kernel).
 #include "pd_vit_train_kernels.h"
 #include "../../include/pd_engine_vit_train.h"
@@ -43,41 +44,15 @@ struct pd_vit_trainer {
     float *fstats = nullptr;                             // [max_scales][max_images][2] final LayerNorm statistics
     // scratch
     float *hn = nullptr, *dres = nullptr, *dhn = nullptr, *act = nullptr, *dff = nullptr, *dqkv = nullptr;
-    float *la_stats = nullptr;                           // [rows nhead, 4] between the two phases of the attention backward
     float *dpos = nullptr;                               // [max_scales][PD_VT_MAX_TOKENS][d] per-token position gradients
-    float *ws = nullptr;                                 // split-reduction workspaces, as in pd_trainer
-    double *ws_col = nullptr;
+    PdTrWork wk = {};                                    // split-reduction workspaces and la_stats [rows nhead, 4], as in pd_trainer
     float *ws_d = nullptr;                               // [VT_DGRAD_MAX_CHUNKS][rows, d] partial data gradients of a long reduction
     int pend_n = 0, pend_scales = 0;                     // images / scales of the pending forward (0: none)
     PdVtScale pend[PD_VIT_TRAIN_MAX_SCALES] = {};
     PdDevAllocs mem{"pd_vit_trainer_create"};
 };
 
-// ---- launch helpers: pd_train.hip's, with the accumulate switch of a gradient summed over scales -------------------------------------
-// the chunks of a reduction over M token rows: a function of M alone (pd_trainer's rule)
-static void vt_chunks(int M, int *n_chunks, int *rows) {
-    int n = std::min(PD_TR_MAX_CHUNKS, (M + 255) / 256);
-    int r = (M + n - 1) / n;
-    r = (r + 31) / 32 * 32;
-    *rows = r;
-    *n_chunks = (M + r - 1) / r;
-}
-
-static void vt_gemm_launch(const PdTrGemm &g, int nz, hipStream_t s) {
-    hipLaunchKernelGGL(pd_tr_gemm_kernel<false>, dim3((g.J + 63) / 64, (g.I + 63) / 64, nz), dim3(256), 0, s, g, PdTrDrop{});
-}
-
-// Y[M, Nout] = X[M, K] W[Nout, K]^T + b (+ resid)
-static void vt_linear(const float *X, const float *W, const float *b, float *Y, int M, int Nout, int K, const float *resid, hipStream_t s) {
-    PdTrGemm g;
-    memset(&g, 0, sizeof(g));
-    g.A = X; g.a_rs = K; g.a_cs = 1; g.a_rfast = 1;
-    g.B = W; g.b_rs = 1; g.b_cs = K; g.b_rfast = 1;
-    g.C = Y; g.ldc = Nout; g.bias = b; g.resid = resid; g.ldr = Nout;
-    g.I = M; g.J = Nout; g.R = K; g.r_chunk = K;
-    vt_gemm_launch(g, 1, s);
-}
-
+// ---- launch helpers: pd_train_launch.h's, and the data gradient's own --------------------------------------------------------------
 // dX[M, K] = dY[M, Nout] W (W [Nout, K]).  A reduction of more than VT_DGRAD_SPLIT terms (every layer: 384, qkv's 1152, fc1's 1536) is cut
 // into chunks of VT_DGRAD_CHUNK whose partial sums are added in chunk order: one fmaf chain over 1536 terms left norm2 / proj gradients
 // 3.4 x further from float64 than torch's blocked sums are, and chains of 384 still left a cancelling column sum behind qkv's data
@@ -93,60 +68,8 @@ static void vt_dgrad(pd_vit_trainer *tr, const float *dY, const float *W, float 
     g.B = W; g.b_rs = K; g.b_cs = 1; g.b_rfast = 0;
     g.C = nch > 1 ? tr->ws_d : dX; g.ldc = K;
     g.I = M; g.J = K; g.R = Nout; g.r_chunk = nch > 1 ? VT_DGRAD_CHUNK : Nout;
-    vt_gemm_launch(g, nch, s);
-    if (nch > 1) {
-        const long long total = (long long)M * K;
-        hipLaunchKernelGGL(pd_tr_reduce_kernel<float>, dim3((unsigned)std::min<long long>((total + 255) / 256, 2048)), dim3(256), 0, s, tr->ws_d, total, nch, dX);
-    }
-}
-
-// dW[Nout, K] (+)= sum_m dY[m, :]^T X[m, :] over the chunks of M, partials added in chunk order; db[Nout] (+)= sum_m dY[m, :] likewise
-static void vt_wgrad(pd_vit_trainer *tr, const float *dY, const float *X, float *dW, float *db, int M, int Nout, int K, bool acc, hipStream_t s) {
-    int nch, rows;
-    vt_chunks(M, &nch, &rows);
-    if (dW) {
-        PdTrGemm g;
-        memset(&g, 0, sizeof(g));
-        g.A = dY; g.a_rs = 1; g.a_cs = Nout; g.a_rfast = 0;
-        g.B = X; g.b_rs = K; g.b_cs = 1; g.b_rfast = 0;
-        g.C = nch > 1 ? tr->ws : dW; g.ldc = K;
-        if (nch == 1 && acc) {
-            g.resid = dW;
-            g.ldr = K;
-        }
-        g.I = Nout; g.J = K; g.R = M; g.r_chunk = rows;
-        vt_gemm_launch(g, nch, s);
-        if (nch > 1) {
-            const long long total = (long long)Nout * K;
-            const dim3 grid((unsigned)std::min<long long>((total + 255) / 256, 2048));
-            if (acc) hipLaunchKernelGGL(pd_vt_reduce_acc_kernel<float>, grid, dim3(256), 0, s, tr->ws, total, nch, dW);
-            else hipLaunchKernelGGL(pd_tr_reduce_kernel<float>, grid, dim3(256), 0, s, tr->ws, total, nch, dW);
-        }
-    }
-    if (db) {
-        hipLaunchKernelGGL(pd_tr_colsum_kernel<false>, dim3((Nout + 63) / 64, nch), dim3(256), 0, s, dY, (long long)Nout, nullptr, 0LL, nullptr, M, Nout, rows,
-                           nullptr, tr->ws_col);
-        if (acc) hipLaunchKernelGGL(pd_vt_reduce_acc_kernel<double>, dim3((Nout + 255) / 256), dim3(256), 0, s, tr->ws_col, (long long)Nout, nch, db);
-        else hipLaunchKernelGGL(pd_tr_reduce_kernel<double>, dim3((Nout + 255) / 256), dim3(256), 0, s, tr->ws_col, (long long)Nout, nch, db);
-    }
-}
-
-// LayerNorm's dgamma (+)= sum_m dy xhat, dbeta (+)= sum_m dy
-static void vt_ln_param_grads(pd_vit_trainer *tr, const float *dy, const float *x, const float *stats, float *dgamma, float *dbeta, int M, int D, bool acc,
-                              hipStream_t s) {
-    if (!dgamma && !dbeta) return;
-    int nch, rows;
-    vt_chunks(M, &nch, &rows);
-    double *pa = tr->ws_col, *pb = tr->ws_col + (size_t)PD_TR_MAX_CHUNKS * D;     // [chunks][D] each
-    hipLaunchKernelGGL(pd_tr_colsum_kernel<true>, dim3((D + 63) / 64, nch), dim3(256), 0, s, dy, (long long)D, x, (long long)D, stats, M, D, rows, pa, pb);
-    const dim3 grid((D + 255) / 256);
-    if (acc) {
-        if (dgamma) hipLaunchKernelGGL(pd_vt_reduce_acc_kernel<double>, grid, dim3(256), 0, s, pa, (long long)D, nch, dgamma);
-        if (dbeta) hipLaunchKernelGGL(pd_vt_reduce_acc_kernel<double>, grid, dim3(256), 0, s, pb, (long long)D, nch, dbeta);
-    } else {
-        if (dgamma) hipLaunchKernelGGL(pd_tr_reduce_kernel<double>, grid, dim3(256), 0, s, pa, (long long)D, nch, dgamma);
-        if (dbeta) hipLaunchKernelGGL(pd_tr_reduce_kernel<double>, grid, dim3(256), 0, s, pb, (long long)D, nch, dbeta);
-    }
+    pd_tr_gemm_launch(g, nch, s);
+    if (nch > 1) pd_tr_reduce_launch(tr->ws_d, (long long)M * K, nch, dX, s);
 }
 
 static unsigned vt_blocks(size_t total, unsigned cap) { return (unsigned)std::min<size_t>((total + 255) / 256, cap); }
@@ -195,16 +118,13 @@ extern "C" int pd_vit_trainer_create(const pd_vit_weights *shape, int max_images
     }
     VT_A(tr->fstats, (size_t)max_scales * max_images * 2);
     VT_A(tr->hn, rows * d); VT_A(tr->dres, rows * d); VT_A(tr->dhn, rows * d); VT_A(tr->act, rows * ff); VT_A(tr->dff, rows * ff); VT_A(tr->dqkv, rows * 3 * d);
-    VT_A(tr->la_stats, rows * tr->nhead * PD_TR_LA_STATS);
+    VT_A(tr->wk.la_stats, rows * tr->nhead * PD_TR_LA_STATS);
     VT_A(tr->dpos, (size_t)max_scales * PD_VT_MAX_TOKENS * d);
-    VT_A(tr->ws, std::max(ff * d, d * (size_t)PD_VT_KP) * PD_TR_MAX_CHUNKS);
-    VT_A(tr->ws_col, 2 * std::max(ff, 3 * d) * PD_TR_MAX_CHUNKS);
+    VT_A(tr->wk.ws, std::max(ff * d, d * (size_t)PD_VT_KP) * PD_TR_MAX_CHUNKS);
+    VT_A(tr->wk.ws_col, 2 * std::max(ff, 3 * d) * PD_TR_MAX_CHUNKS);
     VT_A(tr->ws_d, (size_t)VT_DGRAD_MAX_CHUNKS * rows * d);
 #undef VT_A
-    // dynamic-LDS limits are per-process attributes of the kernels: the family's bound (256 keys, head dim 128), as pd_trainer_create sets them
-    if (rc == PD_OK) rc = pd_set_lds(pd_tr_lattn_kernel<false>, pd_tr_lattn_lds(PD_TR_LA_MAX_N, PD_TR_MAX_HD));
-    if (rc == PD_OK) rc = pd_set_lds(pd_tr_lattn_bwd_rows_kernel<false>, pd_tr_lattn_bwd_rows_lds(PD_TR_LA_MAX_N, PD_TR_MAX_HD));
-    if (rc == PD_OK) rc = pd_set_lds(pd_tr_lattn_bwd_keys_kernel<false>, pd_tr_lattn_bwd_keys_lds(PD_TR_LA_MAX_N, PD_TR_MAX_HD));
+    if (rc == PD_OK) rc = pd_tr_set_attention_lds();
     if (rc == PD_OK && hipDeviceSynchronize() != hipSuccess) rc = PD_ERR_HIP;
     if (rc != PD_OK) {
         if (rc == PD_ERR_HIP) pd_set_error("pd_vit_trainer_create: a HIP call failed: %s", hipGetErrorString(hipGetLastError()));
@@ -312,12 +232,12 @@ extern "C" int pd_vit_train_forward(pd_vit_trainer *tr, const pd_vit_weights *w,
     const float scale = 1.0f / sqrtf((float)tr->hd);
     for (int i = 0; i < n_scales; ++i) {
         const PdVtScale &S = sc[i];
-        const int M = S.M, rb = (M + 3) / 4;
+        const int M = S.M;
         const size_t r0 = S.row0;
         float *cols = tr->cols + r0 * PD_VT_KP;
         hipLaunchKernelGGL(pd_vt_im2col_kernel, dim3(vt_blocks((size_t)n * S.P * PD_VT_KP, 8192)), dim3(256), 0, s, images, n, H, W, S.gh, S.gw, inv_sf[i], same_size[i],
                            cols);
-        vt_linear(cols, w->patch_w, w->patch_b, tr->hn, n * S.P, d, PD_VT_KP, nullptr, s);
+        pd_tr_linear(cols, w->patch_w, w->patch_b, tr->hn, n * S.P, d, PD_VT_KP, 0, nullptr, s);
         hipLaunchKernelGGL(pd_vt_assemble_kernel, dim3(vt_blocks((size_t)M * d, 4096)), dim3(256), 0, s, tr->hn, w->cls_token,
                            S.resampled ? pos[i] : w->pos_embed, n, S.T, d, tr->hres[0] + r0 * d);
         for (int l = 0; l < Lc; ++l) {
@@ -325,16 +245,15 @@ extern "C" int pd_vit_train_forward(pd_vit_trainer *tr, const pd_vit_weights *w,
             const PdVtLayerStash &St = tr->L[l];
             float *h0 = tr->hres[2 * l] + r0 * d, *h1 = tr->hres[2 * l + 1] + r0 * d, *h2 = tr->hres[2 * l + 2] + r0 * d;
             float *qkv = St.qkv + r0 * 3 * d, *ctx = St.ctx + r0 * d, *pre = St.pre + r0 * ff;
-            hipLaunchKernelGGL(pd_vt_ln_kernel, dim3(rb), dim3(256), 0, s, h0, tr->hn, Wl.norm1_w, Wl.norm1_b, M, d, VT_EPS, St.stats1 + r0 * 2);
-            vt_linear(tr->hn, Wl.qkv_w, Wl.qkv_b, qkv, M, 3 * d, d, nullptr, s);
-            hipLaunchKernelGGL(pd_tr_lattn_kernel<false>, dim3(n * tr->nhead, (S.T + PD_TR_LA_ROWS - 1) / PD_TR_LA_ROWS), dim3(256), pd_tr_lattn_lds(S.T, tr->hd),
-                               s, qkv, ctx, S.T, tr->nhead, tr->hd, d, scale, PdTrDrop{});
-            vt_linear(ctx, Wl.proj_w, Wl.proj_b, h1, M, d, d, h0, s);
-            hipLaunchKernelGGL(pd_vt_ln_kernel, dim3(rb), dim3(256), 0, s, h1, tr->hn, Wl.norm2_w, Wl.norm2_b, M, d, VT_EPS, St.stats2 + r0 * 2);
-            vt_linear(tr->hn, Wl.fc1_w, Wl.fc1_b, pre, M, ff, d, nullptr, s);
+            pd_tr_ln_launch(h0, tr->hn, Wl.norm1_w, Wl.norm1_b, M, d, VT_EPS, St.stats1 + r0 * 2, s);
+            pd_tr_linear(tr->hn, Wl.qkv_w, Wl.qkv_b, qkv, M, 3 * d, d, 0, nullptr, s);
+            pd_tr_attn_launch(true, qkv, ctx, n, S.T, tr->nhead, tr->hd, d, scale, nullptr, s);
+            pd_tr_linear(ctx, Wl.proj_w, Wl.proj_b, h1, M, d, d, 0, h0, s);
+            pd_tr_ln_launch(h1, tr->hn, Wl.norm2_w, Wl.norm2_b, M, d, VT_EPS, St.stats2 + r0 * 2, s);
+            pd_tr_linear(tr->hn, Wl.fc1_w, Wl.fc1_b, pre, M, ff, d, 0, nullptr, s);
             hipLaunchKernelGGL(pd_vt_gelu_kernel, dim3(vt_blocks((size_t)M * ff / 4, 4096)), dim3(256), 0, s, (const float4 *)pre, (float4 *)tr->act,
                                (size_t)M * ff / 4);
-            vt_linear(tr->act, Wl.fc2_w, Wl.fc2_b, h2, M, d, ff, h1, s);
+            pd_tr_linear(tr->act, Wl.fc2_w, Wl.fc2_b, h2, M, d, ff, 0, h1, s);
         }
         hipLaunchKernelGGL(pd_vt_final_kernel, dim3((n + 3) / 4), dim3(256), 0, s, tr->hres[2 * Lc] + r0 * d, n, S.T, d, w->norm_w, w->norm_b, VT_EPS,
                            i == 0 ? 1 : 0, i == n_scales - 1 ? 1 : 0, n_scales, z_out, tr->fstats + (size_t)i * tr->max_images * 2);
@@ -381,34 +300,28 @@ extern "C" int pd_vit_train_backward(pd_vit_trainer *tr, const pd_vit_weights *w
             const size_t n4 = (size_t)M * ff / 4;
             // MLP sublayer: dres is the gradient of fc2's output
             if (G.fc2_w) hipLaunchKernelGGL(pd_vt_gelu_kernel, dim3(vt_blocks(n4, 4096)), dim3(256), 0, s, (const float4 *)pre, (float4 *)tr->act, n4);
-            vt_wgrad(tr, tr->dres, tr->act, G.fc2_w, G.fc2_b, M, d, ff, acc, s);
+            pd_tr_wgrad(tr->wk, tr->dres, tr->act, G.fc2_w, G.fc2_b, M, d, ff, acc, s);
             vt_dgrad(tr, tr->dres, Wl.fc2_w, tr->dff, M, d, ff, s);
             hipLaunchKernelGGL(pd_vt_gelu_bwd_kernel, dim3(vt_blocks(n4, 4096)), dim3(256), 0, s, (const float4 *)pre, (float4 *)tr->dff, n4);
-            if (G.fc1_w) hipLaunchKernelGGL(pd_vt_ln_kernel, dim3(rb), dim3(256), 0, s, h1, tr->hn, Wl.norm2_w, Wl.norm2_b, M, d, VT_EPS, (float *)nullptr);
-            vt_wgrad(tr, tr->dff, tr->hn, G.fc1_w, G.fc1_b, M, ff, d, acc, s);
+            if (G.fc1_w) pd_tr_ln_launch(h1, tr->hn, Wl.norm2_w, Wl.norm2_b, M, d, VT_EPS, nullptr, s);
+            pd_tr_wgrad(tr->wk, tr->dff, tr->hn, G.fc1_w, G.fc1_b, M, ff, d, acc, s);
             vt_dgrad(tr, tr->dff, Wl.fc1_w, tr->dhn, M, ff, d, s);
-            vt_ln_param_grads(tr, tr->dhn, h1, st2, G.norm2_w, G.norm2_b, M, d, acc, s);
-            hipLaunchKernelGGL(pd_tr_ln_bwd_kernel, dim3(rb), dim3(256), 0, s, tr->dhn, h1, st2, Wl.norm2_w, M, d, tr->dres);
+            pd_tr_ln_param_grads(tr->wk, tr->dhn, h1, st2, G.norm2_w, G.norm2_b, M, d, acc, s);
+            pd_tr_ln_bwd_launch(tr->dhn, h1, st2, Wl.norm2_w, M, d, tr->dres, s);
             // attention sublayer: dres is the gradient of proj's output
-            vt_wgrad(tr, tr->dres, ctx, G.proj_w, G.proj_b, M, d, d, acc, s);
+            pd_tr_wgrad(tr->wk, tr->dres, ctx, G.proj_w, G.proj_b, M, d, d, acc, s);
             vt_dgrad(tr, tr->dres, Wl.proj_w, tr->dhn, M, d, d, s);
-            {
-                const dim3 rows(n * tr->nhead, (T + PD_TR_LA_ROWS - 1) / PD_TR_LA_ROWS), keys(n * tr->nhead, pd_tr_la_tiles(T));
-                hipLaunchKernelGGL(pd_tr_lattn_bwd_rows_kernel<false>, rows, dim3(256), pd_tr_lattn_bwd_rows_lds(T, tr->hd), s, qkv, tr->dhn, tr->dqkv,
-                                   tr->la_stats, T, tr->nhead, tr->hd, d, scale, PdTrDrop{});
-                hipLaunchKernelGGL(pd_tr_lattn_bwd_keys_kernel<false>, keys, dim3(256), pd_tr_lattn_bwd_keys_lds(T, tr->hd), s, qkv, tr->dhn, tr->dqkv,
-                                   tr->la_stats, T, tr->nhead, tr->hd, d, scale, PdTrDrop{});
-            }
-            if (G.qkv_w) hipLaunchKernelGGL(pd_vt_ln_kernel, dim3(rb), dim3(256), 0, s, h0, tr->hn, Wl.norm1_w, Wl.norm1_b, M, d, VT_EPS, (float *)nullptr);
-            vt_wgrad(tr, tr->dqkv, tr->hn, G.qkv_w, G.qkv_b, M, 3 * d, d, acc, s);
+            pd_tr_attn_bwd_launch(true, qkv, tr->dhn, tr->dqkv, tr->wk.la_stats, n, T, tr->nhead, tr->hd, d, scale, nullptr, s);
+            if (G.qkv_w) pd_tr_ln_launch(h0, tr->hn, Wl.norm1_w, Wl.norm1_b, M, d, VT_EPS, nullptr, s);
+            pd_tr_wgrad(tr->wk, tr->dqkv, tr->hn, G.qkv_w, G.qkv_b, M, 3 * d, d, acc, s);
             vt_dgrad(tr, tr->dqkv, Wl.qkv_w, tr->dhn, M, 3 * d, d, s);
-            vt_ln_param_grads(tr, tr->dhn, h0, st1, G.norm1_w, G.norm1_b, M, d, acc, s);
-            hipLaunchKernelGGL(pd_tr_ln_bwd_kernel, dim3(rb), dim3(256), 0, s, tr->dhn, h0, st1, Wl.norm1_w, M, d, tr->dres);
+            pd_tr_ln_param_grads(tr->wk, tr->dhn, h0, st1, G.norm1_w, G.norm1_b, M, d, acc, s);
+            pd_tr_ln_bwd_launch(tr->dhn, h0, st1, Wl.norm1_w, M, d, tr->dres, s);
         }
         // token assembly adjoint: dres is the gradient of x0.  dhn receives the patch GEMM's output gradient in compact rows
         hipLaunchKernelGGL(pd_vt_assemble_bwd_kernel, dim3((T * d + 255) / 256), dim3(256), 0, s, tr->dres, n, T, d, tr->dhn,
                            tr->dpos + (size_t)i * PD_VT_MAX_TOKENS * d);
-        vt_wgrad(tr, tr->dhn, tr->cols + r0 * PD_VT_KP, grads->patch_w, grads->patch_b, n * S.P, d, PD_VT_KP, acc, s);
+        pd_tr_wgrad(tr->wk, tr->dhn, tr->cols + r0 * PD_VT_KP, grads->patch_w, grads->patch_b, n * S.P, d, PD_VT_KP, acc, s);
     }
     if (grads->cls_token || grads->pos_embed) {
         const int g = tr->grid0;

@@ -1,29 +1,24 @@
 // pd_vit_train_kernels.h -- the device code of the backbone trainer (pd_vit_train.hip; include/pd_engine_vit_train.h)
-// that the denoiser trainer's header lacks.  Every matrix product, the LayerNorm backward, the column sums, the split reductions and the
-// key-tiled attention are pd_train_kernels.h's kernels, launched unchanged; the kernels here are the ViT's own pieces:
+// that the denoiser trainer's header lacks.  Every matrix product, LayerNorm and its backward, the column sums, the split reductions and
+// the key-tiled attention are pd_train_kernels.h's kernels, compiled once in pd_train.hip and launched through pd_train_launch.h's helpers;
+// the kernels here are the ViT's own pieces:
 //   pd_vt_im2col_kernel         normalise + bilinear rescale (vit_prep_kernel's arithmetic) straight into patch rows [n P, 768]
 //   pd_vt_assemble_kernel       x0[img, 0] = cls + pos[0], x0[img, 1 + p] = patch_out + pos[1 + p]; pd_vt_assemble_bwd_kernel its adjoint
-//   pd_vt_ln_kernel             pd_tr_ln_kernel with eps as an argument (DINO's LayerNorms have eps 1e-6, the denoiser's 1e-5)
 //   pd_vt_gelu_kernel / _bwd    nn.GELU() in its exact erf form from the stashed pre-activation; dy (Phi(a) + a phi(a))
 //   pd_vt_final_kernel / _bwd / _param   the final LayerNorm of the CLS rows, the average over the scales, and their backward
-//   pd_vt_reduce_acc_kernel     pd_tr_reduce_kernel that ADDS to its destination (a weight gradient accumulated over the scales)
 //   pd_vt_posgrid_kernel        d pos_embed / d cls_token from one scale's per-token position gradient: the adjoint of the bicubic resampling
 // No float atomics; every sum has a fixed order that depends on the shapes of the call alone.
 #pragma once
 #include "pd_denoiser_dev.h"
+#include "pd_train_launch.h"
 
 #include <math.h>
 #include <stddef.h>
 
-// pd_train_kernels.h defines its kernels as ordinary functions for ONE translation unit (pd_train.hip); a second one takes them with
-// internal linkage, so that the two objects link and neither shares a kernel handle (and its dynamic-LDS attribute) with the other
-namespace {
-#include "pd_train_kernels.h"
-}
-
 #define PD_VT_PATCH 16
 #define PD_VT_KP 768                // 3 x 16 x 16: the columns of a patch row, k = c 256 + ky 16 + kx
-#define PD_VT_MAX_TOKENS 256        // = PD_TR_LA_MAX_N: the key-tiled attention's limit
+#define PD_VT_MAX_TOKENS 256        // the key-tiled attention's limit
+static_assert(PD_VT_MAX_TOKENS == PD_TR_LA_MAX_N, "the tokens of an image are the keys of pd_tr_lattn_*");
 
 // Patch rows of the prepared images: (image - mean) / std (image_feature_extractor.py:62-63), F.interpolate(scale_factor, bilinear,
 // align_corners=False) (:86-87; identity: skipped) in the expressions of vit_prep_kernel, written as row (image, patch), column k.
@@ -85,29 +80,6 @@ __global__ __launch_bounds__(256) void pd_vt_assemble_bwd_kernel(const float *__
     dpos[idx] = (float)s;
 }
 
-// pd_tr_ln_kernel with eps as an argument: one wave per row, stats[m] = (mean, rstd) when stats is not null
-__global__ __launch_bounds__(256) void pd_vt_ln_kernel(const float *__restrict__ in, float *__restrict__ out, const float *__restrict__ gamma,
-                                                       const float *__restrict__ beta, int M, int D, float eps, float *__restrict__ stats) {
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (row >= M) return;
-    const float *src = in + (size_t)row * D;
-    float s = 0.0f;
-    for (int c = lane; c < D; c += 64) s += src[c];
-    const float mean = pd_wave_sum(s) / (float)D;
-    float q = 0.0f;
-    for (int c = lane; c < D; c += 64) {
-        const float e = src[c] - mean;
-        q = fmaf(e, e, q);
-    }
-    const float rstd = 1.0f / sqrtf(pd_wave_sum(q) / (float)D + eps);
-    float *dst = out + (size_t)row * D;
-    for (int c = lane; c < D; c += 64) dst[c] = (src[c] - mean) * rstd * gamma[c] + beta[c];
-    if (stats && lane == 0) {
-        stats[2 * (size_t)row] = mean;
-        stats[2 * (size_t)row + 1] = rstd;
-    }
-}
-
 // nn.GELU(), exact erf form, of the stashed fc1 pre-activation (total = rows x hidden, a multiple of 4)
 __device__ __forceinline__ float pd_vt_gelu(float a) { return 0.5f * a * (1.0f + erff(a * 0.70710678118654752f)); }
 __global__ __launch_bounds__(256) void pd_vt_gelu_kernel(const float4 *__restrict__ pre, float4 *__restrict__ out, size_t total4) {
@@ -139,15 +111,8 @@ __global__ __launch_bounds__(256) void pd_vt_final_kernel(const float *__restric
     const int im = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (im >= n) return;
     const float *src = x + (size_t)im * T * D;
-    float s = 0.0f;
-    for (int c = lane; c < D; c += 64) s += src[c];
-    const float mean = pd_wave_sum(s) / (float)D;
-    float q = 0.0f;
-    for (int c = lane; c < D; c += 64) {
-        const float e = src[c] - mean;
-        q = fmaf(e, e, q);
-    }
-    const float rstd = 1.0f / sqrtf(pd_wave_sum(q) / (float)D + eps);
+    float mean, rstd;
+    pd_wave_row_stats(src, D, lane, eps, &mean, &rstd);
     float *dst = z + (size_t)im * D;
     for (int c = lane; c < D; c += 64) {
         const float f = (src[c] - mean) * rstd * gamma[c] + beta[c];
@@ -205,16 +170,6 @@ __global__ __launch_bounds__(256) void pd_vt_final_param_kernel(const float *__r
     }
     if (dgamma) dgamma[c] = accumulate ? dgamma[c] + (float)a : (float)a;
     if (dbeta) dbeta[c] = accumulate ? dbeta[c] + (float)b : (float)b;
-}
-
-// out[e] += ws[0][e] + ws[1][e] + ... in slice order: pd_tr_reduce_kernel for a gradient that already holds the scales before this one
-template <typename T>
-__global__ __launch_bounds__(256) void pd_vt_reduce_acc_kernel(const T *__restrict__ ws, long long total, int nz, float *__restrict__ out) {
-    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long long)gridDim.x * blockDim.x) {
-        T s = ws[e];
-        for (int z = 1; z < nz; ++z) s += ws[(long long)z * total + e];
-        out[e] += (float)s;
-    }
 }
 
 // torch's bicubic kernel (A = -0.75) at distance x from a tap: |x| <= 1 and 1 < |x| < 2

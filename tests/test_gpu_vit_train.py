@@ -6,7 +6,8 @@ the same function.  Nets are vit_oracle.make_vit cut to 1 or 2 blocks (one case 
   1. PARITY: z and every gradient tensor -- and the q / k / v rows of attn.qkv, the CLS row and the patch rows of pos_embed separately,
      each against its own float64 maximum -- is at most max(4 x own, 8 x 2^-24) from float64; a block whose float64 gradient is
      identically zero is exactly zero.  The k rows of attn.qkv.bias are mathematically zero and are printed only.
-  2. DETERMINISM: twice the same bits; a trainer of larger capacity the same bits; ``want=`` subsets the same bits.
+  2. DETERMINISM: twice the same bits; a trainer of larger capacity the same bits; ``want=`` subsets the same bits; alternating with a
+     denoiser trainer (PoseTrainer, which launches the same pd_tr_* kernel handles and shares their dynamic-LDS bounds) the same bits.
   3. STATE: one stash -- backward without forward, a second backward and an overtaken autograd node are refused.
   4. LIVE WEIGHTS: an in-place SGD step changes the next forward with no rebuild, and that forward meets rule 1 at the updated weights.
   5. DROP-IN: off by default (bitwise today's ``multiscale``), on with both opt-ins; through PoseDiffusionModel the backbone gradients
@@ -17,8 +18,13 @@ import pytest
 import torch
 
 from oracle import pd_oracle as O
+import test_gpu_train_dropout as GD
+import test_gpu_train_grad as G
+import train_long_checks as L
 import vit_train_checks as VC
 from posediffusion_amd import host, synth
+from posediffusion_amd.schedule import diffusion_buffers
+from posediffusion_amd.train import PoseTrainer
 from posediffusion_amd.vit_train import VitTrainer, multiscale_with_grad, shape_from_module, token_rows
 
 pytestmark = pytest.mark.gpu
@@ -157,6 +163,37 @@ def test_same_bits_twice_at_a_larger_capacity_and_for_want_subsets(nets):
     with pytest.raises(KeyError, match="unknown gradient names"):
         tr.forward(net.gpu, images.to(DEV), case.scales)
         tr.backward(net.gpu, g_z.to(DEV), ["blocks.7.norm1.weight"])
+
+
+def test_alternating_with_a_denoiser_trainer_each_keeps_its_own_bits():
+    """One device copy of every pd_tr_* kernel serves both trainers (csrc/pd_train_launch.h), so they share kernel handles and the
+    dynamic-LDS bound of each: used in turn in one process, each gives the bits it gives alone.  The backbone side has single-chunk
+    reductions that write (scale 1 / 2 runs first) and accumulate (scale 1); the denoiser side runs the key-tiled attention at 65 frames
+    with dropout at all four sites, i.e. the DROP = true instantiations the backbone trainer never launches."""
+    case = VC.Case(3, 32, 48, (1, 1 / 2), 2)                             # 7 and 2 tokens: 21 + 6 rows
+    images, g_z = VC.inputs(case)
+    vnet = _Net(case.depth)
+    dnet = None
+    try:
+        vtr = vnet.trainer_for(case)                                    # before any PoseTrainer of this test exists
+        z_a, g_a = _engine_pass(vtr, vnet.gpu, images, g_z, case.scales)
+        dnet = G._Net(L.make_two())
+        inp = G._inputs(1, 65)
+        ptr = PoseTrainer(dict(dnet.shape, objective="pred_noise"), diffusion_buffers(), 1, 65, device=torch.device(DEV), max_frames=L.MAX_FRAMES)
+        dnet._trainers["alternating"] = ptr                             # closed with dnet
+        b = GD._bits(ptr, dnet, inp, **L.CAPACITY_DROP)
+        z_again, g_again = _engine_pass(vtr, vnet.gpu, images, g_z, case.scales)
+        b_again = GD._bits(ptr, dnet, inp, **L.CAPACITY_DROP)
+    finally:
+        vnet.close()
+        if dnet is not None:
+            dnet.close()
+    assert L.CAPACITY_DROP["dropout_sites"] == GD.D.ALL and L.CAPACITY_DROP["dropout_p"] > 0
+    assert torch.isfinite(z_a).all() and all(torch.isfinite(v).all() and v.abs().max() > 0 for v in g_a.values())
+    v_differ = [k for k in g_a if not torch.equal(g_a[k], g_again[k])]
+    d_differ = [k for k in b if not torch.equal(b[k], b_again[k])]
+    print(f"alternating: backbone {len(g_a)} gradients, differing {v_differ}; denoiser {len(b)} tensors, differing {d_differ}")
+    assert torch.equal(z_a, z_again) and v_differ == [] and d_differ == []
 
 
 def test_one_stash_backward_needs_its_own_forward(nets):

@@ -13,6 +13,9 @@
      massive_channel (vit_train_edge_cases.CANCELLING_BLOCKS, up to 5.1e-4) are printed only."""
 import copy
 import functools
+import os
+import shutil
+import subprocess
 
 import pytest
 import torch
@@ -22,6 +25,8 @@ from posediffusion_amd import vit_train as VT
 import vit_checks as V
 import vit_train_checks as VC
 import vit_train_edge_cases as EC
+
+CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "posediffusion_amd", "csrc")
 
 
 @functools.lru_cache(maxsize=None)
@@ -47,6 +52,35 @@ def test_vt_chunks_restatement():
     for M in (1, 31, 255, 1000, 2758, 4096, 4352, 5280, 100000):
         chunks, r, last = VC.vt_chunks(M)
         assert 1 <= chunks <= 16 and r % 32 == 0 and 1 <= last <= r and (chunks - 1) * r + last == M
+
+
+_CHUNKS_PROGRAM = r"""
+#define PD_TR_LAUNCH_HOST_ONLY
+#include "pd_train_launch.h"
+#include <stdio.h>
+int main() {
+    for (int M = 1; M <= 20000; ++M) {
+        int chunks, rows;
+        pd_tr_chunks(M, &chunks, &rows);
+        printf("%d %d %d\n", M, chunks, rows);
+    }
+    return 0;
+}
+"""
+
+
+@pytest.mark.skipif(shutil.which("c++") is None and shutil.which("g++") is None, reason="no host C++ compiler")
+def test_vt_chunks_is_pd_tr_chunks_of_the_launch_header(tmp_path):
+    """the pinned figures above rest on vit_train_checks.vt_chunks: it is the trainers' one C++ rule, compiled from its header on the host"""
+    src, exe = tmp_path / "chunks.cpp", tmp_path / "chunks"
+    src.write_text(_CHUNKS_PROGRAM)
+    cxx = shutil.which("c++") or shutil.which("g++")
+    out = subprocess.run([cxx, "-std=c++17", "-I", CSRC, str(src), "-o", str(exe)], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stderr[-2000:]
+    rows = [tuple(int(x) for x in line.split()) for line in subprocess.run([str(exe)], capture_output=True, text=True, timeout=30).stdout.splitlines()]
+    assert [M for M, _, _ in rows] == list(range(1, 20001))
+    for M, chunks, r in rows:
+        assert (chunks, r) == VC.vt_chunks(M)[:2], (M, chunks, r, VC.vt_chunks(M))
 
 
 @pytest.mark.parametrize("name", list(EC.EDGES))

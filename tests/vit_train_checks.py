@@ -149,8 +149,9 @@ def with_row_stride(images: torch.Tensor, stride: int) -> torch.Tensor:
 
 
 def vt_chunks(M: int, max_chunks: int = 16) -> Tuple[int, int, int]:
-    """(chunks, rows per chunk, rows of the last chunk) of a reduction over M token rows: pd_vit_train.hip's vt_chunks restated
-    (``max_chunks`` = PD_TR_MAX_CHUNKS)."""
+    """(chunks, rows per chunk, rows of the last chunk) of a reduction over M token rows: pd_tr_chunks of
+    posediffusion_amd/csrc/pd_train_launch.h restated (``max_chunks`` = PD_TR_MAX_CHUNKS); tests/test_vit_train_edges_cpu.py compiles that
+    header and holds the two against each other."""
     n = min(max_chunks, (M + 255) // 256)
     r = (M + n - 1) // n
     r = (r + 31) // 32 * 32
