@@ -11,13 +11,13 @@
 // reference's fp32 path to rounding-order differences only (SURVEY.md headline fact 5).
 //
 // This file is the host side: engine creation, the split-precision weights, and one step's launches.  The kernels are in the headers:
-//   pd_gemm_small.h (small batches), pd_gemm_stream.h / pd_gemm_split.h (large batches: exact / split precision), pd_attn.h,
+//   pd_gemm_small.h (small batches), pd_gemm_stream.h / pd_gemm_split.h / pd_gemm_strip.h (large batches: exact / split precision / its strip kernel), pd_attn.h,
 //   pd_attn_long.h (more than 64 frames) and pd_qkv_attn.h (attention), pd_denoiser_kernels.h (embeddings, tail, probe); pd_denoiser_plan.h decides which of them a step launches.
 // One timestep per sequence (pd_denoise_step_t, pd_p_losses) changes _first and the tail only: den_first_small_t, den_first_streamed_t,
 // den_tail_t below; the streamed path's per-row-bias GEMM is instantiated in pd_denoiser_first_t.hip.
 #include "pd_denoiser_dev.h"
 #include "pd_gemm_stream.h"
-#include "pd_gemm_split.h"
+#include "pd_gemm_strip.h"
 #include "pd_qkv_attn.h"
 #include "pd_gemm_small.h"
 #include "pd_attn.h"
@@ -152,9 +152,8 @@ static int den_set_lds_attributes() {
     PD_TRY(pd_set_lds(pd_attn_long_kernel<0>, pd_attn_long_lds(PD_MAX_DENOISER_FRAMES, DH)));
     PD_TRY(pd_set_lds(pd_attn_long_kernel<1>, pd_attn_long_lds(PD_MAX_DENOISER_FRAMES, DH)));
     PD_TRY(pd_set_lds(pd_attn_long_kernel<2>, pd_attn_long_lds(PD_MAX_DENOISER_FRAMES, DH)));
-    PD_TRY(pd_set_lds((pd_qkv_attn_kernel<0, PD_QA_DEEP_DEFAULT != 0>), 160 * 1024));
+    PD_TRY(pd_set_lds(pd_qkv_attn_kernel<0>, 160 * 1024));
 #ifdef PD_DEV_KNOBS
-    PD_TRY(pd_set_lds((pd_qkv_attn_kernel<0, PD_QA_DEEP_DEFAULT == 0>), 160 * 1024));
     PD_TRY(pd_set_lds(pd_qkv_attn_kernel<1>, 160 * 1024));
     PD_TRY(pd_set_lds(pd_qkv_attn_kernel<2>, 160 * 1024));
     PD_TRY(pd_set_lds(pd_qkv_attn_kernel<3>, 160 * 1024));
@@ -343,17 +342,15 @@ static void den_layer_bf16(const PdDenoiserDev *d, const PdLayerDev &L, bool lon
     pd_gemm_split<2, 1, 1>((const unsigned *)d->ff, DFF, L.ff2_ws, DFF, L.ff2_b, d->h, M, DM, s);
 }
 // One GEMM of the fp16-plane path, C = epi(A [M, K] W^T): the strip kernel (A by LDS-DMA, no weight fragment fetched twice) at rt 32-row tiles per
-// workgroup, or (rt = 0) the round-1 two-plane kernel; bitwise the same results (tools/split3_probe.hip).  Only the row tiles an epilogue is
-// launched with exist as kernels: 2 for all, 3 for the residual (2) and FF1 (4) epilogues, 1 under -DPD_STRIP_RT1 (= 2: for FF1 too).
+// workgroup, or (rt = 0) the round-1 two-plane kernel: the same results but for a sum's last bit (header of pd_gemm_split.h).  Only the row tiles an epilogue is
+// launched with exist as kernels: 2 for all, 3 for the residual (2) and FF1 (4) epilogues.
 template <int EPI>
 static void den_gemm_f16(int rt, const float *A, int K, const unsigned *W, const float *bias, float *C, int M, int Nout, hipStream_t s, float c_scale,
                          float out_scale = 1.0f) {
     const unsigned *Aw = (const unsigned *)A;        // split words
-    if constexpr (PD_STRIP_RT1 != 0 && (EPI == 2 || (EPI == 4 && PD_STRIP_RT1 == 2)))
-        if (rt == 1) return pd_gemm_strip<EPI, 1, true, 1, PD_STRIP_K64>(Aw, K, W, K, bias, C, M, Nout, s, c_scale, out_scale);
     if constexpr (EPI != 0)
-        if (rt == 3) return pd_gemm_strip<EPI, 3, true, 1, PD_STRIP_K64>(Aw, K, W, K, bias, C, M, Nout, s, c_scale, out_scale);
-    if (rt == 2) return pd_gemm_strip<EPI, 2, true, 1, PD_STRIP_K64>(Aw, K, W, K, bias, C, M, Nout, s, c_scale, out_scale);
+        if (rt == 3) return pd_gemm_strip<EPI, 3>(Aw, K, W, K, bias, C, M, Nout, s, c_scale, out_scale);
+    if (rt == 2) return pd_gemm_strip<EPI, 2>(Aw, K, W, K, bias, C, M, Nout, s, c_scale, out_scale);
     pd_gemm_split<EPI, 1, EPI == 2 ? 1 : 2, true>(Aw, K, W, K, bias, C, M, Nout, s, c_scale, out_scale);
 }
 // fp16-plane mode: the fast mode's kernels with fp16 halves and the static power-of-two scales of pd_denoiser_build_split

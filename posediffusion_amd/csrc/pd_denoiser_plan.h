@@ -5,18 +5,9 @@
 #pragma once
 #include "pd_qkv_attn.h"
 
-// build switches of the fp16-plane path's strip GEMMs (pd_gemm_split.h)
+// build switch of the fp16-plane path's strip GEMMs (pd_gemm_strip.h): a decision, not a kernel form (tools/den_ab.py runs both sides)
 #ifndef PD_STRIP_RT3
 #define PD_STRIP_RT3 1         // round 6: 96-row tiles for the 512-wide strip GEMMs when that takes them from more tiles than CUs to at most one per CU
-#endif
-#ifndef PD_STRIP_RT1
-#define PD_STRIP_RT1 0         // (probe: 32-row tiles instead -- 640 half tiles, more workgroups per CU, twice the weight bytes per MFMA; 2: for FF1 too)
-#endif
-#ifndef PD_STRIP_RT3_FF1
-#define PD_STRIP_RT3_FF1 0     // (the 1 024-wide FF1 has 640 tiles at 64 rows, 432 at 96: three tiles of 1 or two of 1.5 on the busiest CU -- the same)
-#endif
-#ifndef PD_STRIP_K64
-#define PD_STRIP_K64 true      // the strip GEMMs of the fp16-plane mode: A chunks of 64 k per barrier (pd_gemm_split.h)
 #endif
 
 enum PdDenPath {
@@ -35,7 +26,7 @@ struct PdDenStepPlan {
     // PD_DEN_F16_PLANES only (zero on the other paths)
     bool fused_attn;       // in_proj + attention as ONE kernel (pd_qkv_attn.h), else the QKV GEMM and an attention kernel
     bool attn_mma;         // the attention kernel of the two-launch form: pd_attn_mma_kernel, else pd_attn_seq_kernel (or the long kernel, above)
-    int rt_res, rt_ff1;    // 32-row tiles per workgroup (1, 2 or 3) of the strip GEMMs: out-projection and FF2 (512 wide, residual epilogue); FF1
+    int rt_res, rt_ff1;    // 32-row tiles per workgroup (2 or 3) of the strip GEMMs: out-projection and FF2 (512 wide, residual epilogue); FF1
     int strip;             // PD_DEN_STRIP: bit mask {QKV, out, FF1, FF2} of the GEMMs on the strip kernel; the others run pd_gemm_split
 };
 
@@ -67,8 +58,8 @@ static inline PdDenStepPlan pd_den_step_plan(int B, int N, int split, int fused_
     // 512-wide outputs: 96-row tiles where 64-row tiles would give the busiest CUs two tiles and most CUs one (5 120 rows: 320 tiles on 256 CUs ->
     // 216 tiles of 1.5 x the work: the launch is as long as its busiest CU).  Same sums in the same order: bitwise the same C.
     const bool rt3 = PD_STRIP_RT3 && (((p.M + 63) / 64) * (DM / 128)) > cus && (((p.M + 95) / 96) * (DM / 128)) <= cus;
-    p.rt_res = !rt3 ? 2 : PD_STRIP_RT1 ? 1 : 3;
-    p.rt_ff1 = !rt3 ? 2 : PD_STRIP_RT1 == 2 ? 1 : PD_STRIP_RT3_FF1 ? 3 : 2;
+    p.rt_res = rt3 ? 3 : 2;
+    p.rt_ff1 = 2;          // the 1 024-wide FF1 has 640 tiles at 64 rows, 432 at 96: three tiles of 1 or two of 1.5 on the busiest CU -- measured the same
     p.strip = knob_strip;
     return p;
 }

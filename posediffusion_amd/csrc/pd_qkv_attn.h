@@ -15,19 +15,13 @@
 // The sums are accumulated in the order of the two kernels this replaces, so the result is BITWISE theirs (tests/test_gpu_parity_r5.py
 // compares the two paths); PD_OPT_DENOISER_FUSED_ATTN = 0 keeps the two-launch path (comparison / testing, and N > 32).
 #pragma once
-#include "pd_gemm_split.h"
+#include "pd_gemm_strip.h"
 
-#ifndef PD_QA_XCD_MAP
-#define PD_QA_XCD_MAP 1
-#endif
 #define PD_QA_WAVES 12
 #define PD_QA_THREADS (PD_QA_WAVES * 64)
-#define PD_QA_ROWS 96                       // six 16-row tiles (three of 32 rows on the 32x32x16 form)
+#define PD_QA_ROWS 96                       // six 16-row tiles
 #define PD_QA_LDR (3 * DH + 4)              // row stride of the Q | K | V image in LDS (floats): 388 = 4 mod 32 banks, like DH + 4
 #define PD_QA_LS 36                         // row stride of a team's score tile
-#ifndef PD_QA_DEEP_DEFAULT
-#define PD_QA_DEEP_DEFAULT 0                // 1: weight fragments a whole chunk ahead (DEEP below) -- measured no faster (925 vs 926 us per step), 35 more registers
-#endif
 
 struct PdQkvAttnArgs {
     const unsigned *A;        // LayerNorm output as split words [M][DM] (pd_ln_rows_kernel<DM, 2>)
@@ -53,22 +47,19 @@ static inline size_t pd_qkv_attn_lds(int N) {
 
 // BARE (development builds only, -DPD_DEV_KNOBS + PD_QA_BARE=n; results meaningless for n > 0): what bounds the kernel -- 1 no weight-fragment loads
 // inside the K loop, 2 no LDS-DMA inside it, 3 neither, 4 everything but the MFMAs, 5 the product only (no Q | K | V image, no attention)
-// DEEP: the weight fragments of chunk c + 1 (both 32-k blocks: 8 KiB per wave) are requested at the START of chunk c into a second register set,
-// before any MFMA of the chunk is issued (a wave issues in order: loads placed behind a block's 18 MFMAs leave only when the matrix pipe has
-// taken them all) -- a whole chunk of matrix work to hide behind instead of half of one; the same MFMA order, bitwise the same result.
-template <int BARE, bool DEEP = false>
+template <int BARE>
 __global__ __launch_bounds__(PD_QA_THREADS) void pd_qkv_attn_kernel(PdQkvAttnArgs g) {
     constexpr int KC = 32, RT = 3, TM = PD_QA_ROWS, CHA = TM * KC, LDR = PD_QA_LDR, LS = PD_QA_LS;
-    constexpr bool M16 = PD_STRIP_MFMA16 != 0;      // the product's MFMA shape: the in_proj strip instance's (pd_gemm_split.h), which the fused path equals bit for bit
     extern __shared__ __attribute__((aligned(1024))) unsigned qa_lds[];
-    const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, hi = lane >> 5;
+    const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    // block -> (group of sequences, head).  XCD b % 8 runs block b.  PD_QA_XCD_MAP 0 (rounds 5 - 6): the four heads of a group are neighbours -- XCD x hosts head x % 4
-    // (786 KB of weights) and touches the rows of HALF of all groups: every group's rows cross the fabric four times (55 MB per launch at 5 120 rows against 21 if
-    // every operand crossed once; profiles/round6_pmc_summary.json).  1: in chunks of 16 blocks = 4 groups, XCDs 0 - 3 host heads {0, 1}, XCDs 4 - 7 heads {2, 3}, XCD x
-    // the groups = x mod 4: two heads' weights (1.6 MB) and a quarter of the groups' rows per L2, every row crosses twice.  Same workgroups, same arithmetic.
+    // block -> (group of sequences, head).  XCD b % 8 runs block b.  With the four heads of a group as neighbours (rounds 5 - 6) XCD x hosts head x % 4 (786 KB of
+    // weights) and touches the rows of HALF of all groups: every group's rows cross the fabric four times (55 MB per launch at 5 120 rows against 21 if every
+    // operand crossed once; profiles/round6_pmc_summary.json).  Here, in chunks of 16 blocks = 4 groups, XCDs 0 - 3 host heads {0, 1}, XCDs 4 - 7 heads {2, 3}, XCD x
+    // the groups = x mod 4: two heads' weights (1.6 MB) and a quarter of the groups' rows per L2, every row crosses twice: 18.5 MB fetched per launch where the neighbour
+    // order fetched 27.7 (all four heads of a group on ONE XCD -- every row crosses once, 3.1 MB of weights per L2 -- fetched and took the same;
+    // profiles/round6_qkv_xcd_map.txt).  Same workgroups, same arithmetic; the groups beyond the last whole chunk keep the neighbour order.
     int head = blockIdx.x & 3, grp = blockIdx.x >> 2;
-#if PD_QA_XCD_MAP == 1
     {
         const int ngrp = gridDim.x >> 2, c = blockIdx.x >> 4, r = blockIdx.x & 15;
         if (4 * c + 4 <= ngrp) {
@@ -76,22 +67,13 @@ __global__ __launch_bounds__(PD_QA_THREADS) void pd_qkv_attn_kernel(PdQkvAttnArg
             grp = 4 * c + (r & 3);
         }
     }
-#elif PD_QA_XCD_MAP == 2      // (measured alternative: all four heads of a group on ONE XCD -- every row crosses once, 3.1 MB of weights per L2)
-    {
-        const int ngrp = gridDim.x >> 2, c = blockIdx.x >> 5, r = blockIdx.x & 31;
-        if (8 * c + 8 <= ngrp) {
-            head = r >> 3;
-            grp = 8 * c + (r & 7);
-        }
-    }
-#endif
     const int N = g.N, G = g.G, M = g.B * N;
     const int seq0 = grp * G, nseq = min(G, g.B - seq0), m0 = seq0 * N, rows = nseq * N;     // this workgroup's token rows [m0, m0 + rows)
     // ---- 1. the in_proj product ------------------------------------------------------------------------------------------------------
-    // The wave's 32-column strip as two 16-column tiles over the 16-row tiles that hold rows: nt16 = ceil(rows / 16) of six (N = 20: 80 rows = five, where three
-    // 32-row tiles multiplied 96), one v_mfma_f32_16x16x32_f16 per (row tile, column tile, product) and 32-k block -- pd_gemm_strip_kernel's M16 form, element for
-    // element: bitwise its C.  The K loop exists once per tile count (nt16 is uniform over the workgroup, and over the launch but for the last group): the
-    // tiles not run cost no fragment read, no un-zip, no MFMA and no staged row, and their accumulators are never written out.
+    // The wave's 32-column strip as two 16-column tiles over the 16-row tiles that hold rows: nt16 = ceil(rows / 16) of six (N = 20: 80 rows = five), one
+    // v_mfma_f32_16x16x32_f16 per (row tile, column tile, product) and 32-k block -- pd_gemm_strip_kernel's product, element for element: bitwise its C.  The
+    // K loop exists once per tile count (nt16 is uniform over the workgroup, and over the launch but for the last group): the tiles not run cost no fragment
+    // read, no un-zip, no MFMA and no staged row, and their accumulators are never written out.
     // staging: pieces of 1 KiB = 8 rows x 32 words; a 32-k block of A has 12 of them, wave w moves piece w -- if a tile that is run holds its rows
     const int nt16 = __builtin_amdgcn_readfirstlane((rows + 15) >> 4);
     const int stages = __builtin_amdgcn_readfirstlane(8 * wave < 16 * nt16 ? 1 : 0);
@@ -99,43 +81,17 @@ __global__ __launch_bounds__(PD_QA_THREADS) void pd_qkv_attn_kernel(PdQkvAttnArg
     unsigned oa;
     {
         const int r = 8 * wave + prow;
-        oa = (unsigned)(((size_t)min(m0 + r, M - 1) * DM + 4 * (pslot ^ pd_strip_swz<M16>(r))) * sizeof(unsigned));
+        oa = (unsigned)(((size_t)min(m0 + r, M - 1) * DM + 4 * (pslot ^ pd_strip_swz(r))) * sizeof(unsigned));
     }
     const unsigned lds_a = (unsigned)(size_t)(qa_lds + wave * 256);
     const int third = wave >> 2;                                                     // 0 q, 1 k, 2 v
     const int ntile = third * (DM / 32) + head * (DH / 32) + (wave & 3);              // this wave's 32-column tile of the 1536 in_proj rows
     constexpr int KS = DM / 16;
-    // M16: the lane's (column % 16, k group) of a 32-k block in the planes' 32-column x 16-k fragment order (pd_gemm_strip_kernel)
-    const uint4 *wq = (const uint4 *)g.W + (size_t)ntile * KS * 128 + (M16 ? (kg >> 1) * 128 + (kg & 1) * 32 + l15 : lane);
-    typedef unsigned wv4 __attribute__((ext_vector_type(4)));
-    f32x16 acc[M16 ? 1 : RT];
-    f32x4 acc4[M16 ? 2 * RT : 1][2];                                                 // M16: [16-row tile][16-column tile]
+    // the lane's (column % 16, k group) of a 32-k block in the planes' 32-column x 16-k fragment order (pd_gemm_strip_kernel)
+    const uint4 *wq = (const uint4 *)g.W + (size_t)ntile * KS * 128 + ((kg >> 1) * 128 + (kg & 1) * 32 + l15);
+    f32x4 acc4[2 * RT][2];                                                           // [16-row tile][16-column tile]
 #pragma unroll
-    for (int mi = 0; mi < (M16 ? 1 : RT); ++mi)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[mi][i] = 0.0f;
-#pragma unroll
-    for (int t = 0; t < (M16 ? 2 * RT : 1); ++t) acc4[t][0] = acc4[t][1] = f32x4{0.f, 0.f, 0.f, 0.f};
-    auto mmaw = [](const uint4 &a, const wv4 &b, const f32x16 &c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-    };
-    auto mma16 = [](const uint4 &a, const wv4 &b, const f32x4 &c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-    };
-    // (M16: w0 / w1 = column tile 0 {hi | lo}, w2 / w3 = column tile 1 -- the lo plane 1 KiB, the second column tile 16 lanes further)
-#define PD_QA_WLOAD(w0, w1, w2, w3, b)                                                                                               \
-    do {                                                                                                                             \
-        const uint4 *wp_ = wq + (size_t)(b) * 256;                                                                                   \
-        if constexpr (M16)                                                                                                           \
-            asm volatile("global_load_dwordx4 %0, %4, off\n\tglobal_load_dwordx4 %1, %4, off offset:1024\n\t"                       \
-                         "global_load_dwordx4 %2, %4, off offset:256\n\tglobal_load_dwordx4 %3, %4, off offset:1280"                 \
-                         : "=&v"(w0), "=&v"(w1), "=&v"(w2), "=&v"(w3) : "v"(wp_) : "memory");                                        \
-        else                                                                                                                         \
-            asm volatile("global_load_dwordx4 %0, %4, off\n\tglobal_load_dwordx4 %1, %4, off offset:1024\n\t"                       \
-                         "global_load_dwordx4 %2, %4, off offset:2048\n\tglobal_load_dwordx4 %3, %4, off offset:3072"                \
-                         : "=&v"(w0), "=&v"(w1), "=&v"(w2), "=&v"(w3) : "v"(wp_) : "memory");                                        \
-    } while (0)
-#define PD_QA_WAIT(n, w0, w1, w2, w3) asm volatile("s_waitcnt vmcnt(" #n ")" : "+v"(w0), "+v"(w1), "+v"(w2), "+v"(w3) : : "memory")
+    for (int t = 0; t < 2 * RT; ++t) acc4[t][0] = acc4[t][1] = f32x4{0.f, 0.f, 0.f, 0.f};
     // vmcnt(6) for a wave that stages (its two DMA pieces may fly), vmcnt(4) for one that does not -- ONE statement, the scalar branch inside it: with a wait per
     // branch the register allocator joins the two definitions of the fragments by copies, which it is free to place ahead of a wait (they read registers still in flight)
 #define PD_QA_WAIT_STAGED(stg, w0, w1, w2, w3)                                                                                       \
@@ -148,135 +104,73 @@ __global__ __launch_bounds__(PD_QA_THREADS) void pd_qkv_attn_kernel(PdQkvAttnArg
 #pragma unroll
         for (int h = 0; h < 2; ++h) pd_dma_piece((const float *)(g.A + (2 * c + h) * KC), oa, da + h * CHA * 4);
     };
-    // one 32-k block: fragment reads + un-zip + 18 MFMAs; w0 / w1 = k step 0 {hi | lo}, w2 / w3 = k step 1.  Per output element and k step:
-    // lo x hi, hi x lo, hi x hi -- pd_gemm_strip_kernel's order.  M16: NT 16-row tiles, 6 MFMAs each, the same order per element over the block's 32 k
-    auto block = [&](auto nt_, const unsigned *a, const wv4 &w0, const wv4 &w1, const wv4 &w2, const wv4 &w3) {
+    // one 32-k block: NT 16-row tiles, fragment reads + un-zip + 6 MFMAs each; w0 / w1 = column tile 0 {hi | lo}, w2 / w3 = column tile 1 (PD_STRIP_WLOAD).
+    // Per output element: lo x hi, hi x lo, hi x hi -- pd_gemm_strip_kernel's order
+    auto block = [&](auto nt_, const unsigned *a, const pd_wv4 &w0, const pd_wv4 &w1, const pd_wv4 &w2, const pd_wv4 &w3) {
         constexpr int NT = decltype(nt_)::value;
-        if constexpr (M16) {
-            const int sz = pd_strip_swz<true>(l15);
+        const int sz = pd_strip_swz(l15);
 #pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                const uint4 p = *(const uint4 *)(a + t * 16 * KC + 4 * ((2 * kg) ^ sz));
-                const uint4 q = *(const uint4 *)(a + t * 16 * KC + 4 * ((2 * kg + 1) ^ sz));
-                const uint4 h8 = make_uint4(__builtin_amdgcn_perm(p.y, p.x, 0x05040100u), __builtin_amdgcn_perm(p.w, p.z, 0x05040100u),
-                                            __builtin_amdgcn_perm(q.y, q.x, 0x05040100u), __builtin_amdgcn_perm(q.w, q.z, 0x05040100u));
-                const uint4 l8 = make_uint4(__builtin_amdgcn_perm(p.y, p.x, 0x07060302u), __builtin_amdgcn_perm(p.w, p.z, 0x07060302u),
-                                            __builtin_amdgcn_perm(q.y, q.x, 0x07060302u), __builtin_amdgcn_perm(q.w, q.z, 0x07060302u));
-                f32x4 &c0 = acc4[M16 ? t : 0][0], &c1 = acc4[M16 ? t : 0][1];
-                c0 = mma16(l8, w0, c0); c1 = mma16(l8, w2, c1);
-                c0 = mma16(h8, w1, c0); c1 = mma16(h8, w3, c1);
-                c0 = mma16(h8, w0, c0); c1 = mma16(h8, w2, c1);
-            }
-        } else {
-        uint4 ah[RT], al[RT];
-#pragma unroll
-        for (int st = 0; st < 2; ++st) {
-#pragma unroll
-            for (int mi = 0; mi < RT; ++mi) {
-                const uint4 p = *(const uint4 *)(a + mi * 32 * KC + 4 * ((4 * st + 2 * hi) ^ ((l31 >> 1) & 7)));
-                const uint4 q = *(const uint4 *)(a + mi * 32 * KC + 4 * ((4 * st + 2 * hi + 1) ^ ((l31 >> 1) & 7)));
-                ah[mi] = make_uint4(__builtin_amdgcn_perm(p.y, p.x, 0x05040100u), __builtin_amdgcn_perm(p.w, p.z, 0x05040100u),
-                                    __builtin_amdgcn_perm(q.y, q.x, 0x05040100u), __builtin_amdgcn_perm(q.w, q.z, 0x05040100u));
-                al[mi] = make_uint4(__builtin_amdgcn_perm(p.y, p.x, 0x07060302u), __builtin_amdgcn_perm(p.w, p.z, 0x07060302u),
-                                    __builtin_amdgcn_perm(q.y, q.x, 0x07060302u), __builtin_amdgcn_perm(q.w, q.z, 0x07060302u));
-            }
-            const wv4 &wh = st ? w2 : w0, &wl = st ? w3 : w1;
-#pragma unroll
-            for (int mi = 0; mi < RT; ++mi) acc[M16 ? 0 : mi] = mmaw(al[mi], wh, acc[M16 ? 0 : mi]);
-#pragma unroll
-            for (int mi = 0; mi < RT; ++mi) acc[M16 ? 0 : mi] = mmaw(ah[mi], wl, acc[M16 ? 0 : mi]);
-#pragma unroll
-            for (int mi = 0; mi < RT; ++mi) acc[M16 ? 0 : mi] = mmaw(ah[mi], wh, acc[M16 ? 0 : mi]);
-        }
+        for (int t = 0; t < NT; ++t) {
+            const uint4 p = *(const uint4 *)(a + t * 16 * KC + 4 * ((2 * kg) ^ sz));
+            const uint4 q = *(const uint4 *)(a + t * 16 * KC + 4 * ((2 * kg + 1) ^ sz));
+            const uint4 h8 = pd_unzip_hi(p, q), l8 = pd_unzip_lo(p, q);
+            f32x4 &c0 = acc4[t][0], &c1 = acc4[t][1];
+            c0 = pd_mma16(l8, w0, c0); c1 = pd_mma16(l8, w2, c1);
+            c0 = pd_mma16(h8, w1, c0); c1 = pd_mma16(h8, w3, c1);
+            c0 = pd_mma16(h8, w0, c0); c1 = pd_mma16(h8, w2, c1);
         }
     };
-    const int lrow = M16 ? l15 : l31;                // the lane's row within a tile
     auto kloop = [&](auto nt_) {
-        wv4 a0, a1, a2, a3, b0, b1, b2, b3;               // weight fragments of the chunk's first / second 32-k block
+        pd_wv4 a0, a1, a2, a3, b0, b1, b2, b3;            // weight fragments of the chunk's first / second 32-k block
         constexpr int nk64 = DM / 64;
         stage64(0, 0);
-        PD_QA_WLOAD(a0, a1, a2, a3, 0);
-        PD_QA_WLOAD(b0, b1, b2, b3, 1);
-        PD_QA_WAIT(0, a0, a1, a2, a3);
-        PD_QA_WAIT(0, b0, b1, b2, b3);
+        PD_STRIP_WLOAD(wq, a0, a1, a2, a3, 0);
+        PD_STRIP_WLOAD(wq, b0, b1, b2, b3, 1);
+        PD_STRIP_WAIT(0, a0, a1, a2, a3);
+        PD_STRIP_WAIT(0, b0, b1, b2, b3);
         __syncthreads();
-        if constexpr (DEEP) {
-            static_assert(!DEEP || BARE == 0, "the deep form has no development variants");
-            wv4 c0, c1, c2, c3, d0, d1, d2, d3;              // the second set: chunk c + 1 while a / b hold chunk c, and vice versa
-            for (int c = 0; c < nk64; c += 2) {              // nk64 is even
-                {
-                    const unsigned *a = qa_lds + 0 * 2 * CHA + lrow * KC;
-                    stage64(c + 1, 1);
-                    PD_QA_WLOAD(c0, c1, c2, c3, 2 * (c + 1));
-                    PD_QA_WLOAD(d0, d1, d2, d3, 2 * (c + 1) + 1);
-                    block(nt_, a, a0, a1, a2, a3);
-                    block(nt_, a + CHA, b0, b1, b2, b3);
-                    PD_QA_WAIT(0, c0, c1, c2, c3);           // everything requested at the start of this chunk has landed
-                    PD_QA_WAIT(0, d0, d1, d2, d3);
-                    __syncthreads();
-                }
-                {
-                    const int cn = min(c + 2, nk64 - 1);     // the chunk after the last is the last again (never used)
-                    const unsigned *a = qa_lds + 1 * 2 * CHA + lrow * KC;
-                    stage64(cn, 0);
-                    PD_QA_WLOAD(a0, a1, a2, a3, 2 * cn);
-                    PD_QA_WLOAD(b0, b1, b2, b3, 2 * cn + 1);
-                    block(nt_, a, c0, c1, c2, c3);
-                    block(nt_, a + CHA, d0, d1, d2, d3);
-                    PD_QA_WAIT(0, a0, a1, a2, a3);
-                    PD_QA_WAIT(0, b0, b1, b2, b3);
-                    __syncthreads();
-                }
-            }
-        } else
         for (int c = 0; c < nk64; ++c) {
             const int cn = min(c + 1, nk64 - 1);                 // the chunk after the last is the last again (never used)
-            const unsigned *a = qa_lds + (c & 1) * 2 * CHA + lrow * KC;
+            const unsigned *a = qa_lds + (c & 1) * 2 * CHA + l15 * KC;
             if constexpr (BARE == 0) {
                 if (c + 1 < nk64) {
                     stage64(cn, (c + 1) & 1);                    // in flight, oldest first: the second block's weights [4, from the previous turn], this DMA [2]
                     block(nt_, a, a0, a1, a2, a3);
-                    PD_QA_WLOAD(a0, a1, a2, a3, 2 * cn);         //   ... + the next chunk's first block [4]
+                    PD_STRIP_WLOAD(wq, a0, a1, a2, a3, 2 * cn);  //   ... + the next chunk's first block [4]
                     // the second block's weights have landed; the DMA [2, a wave that stages] and the loads just issued [4] may fly
                     PD_QA_WAIT_STAGED(stages, b0, b1, b2, b3);
                     block(nt_, a + CHA, b0, b1, b2, b3);
-                    PD_QA_WLOAD(b0, b1, b2, b3, 2 * cn + 1);     //   ... + the next chunk's second block [4]
-                    PD_QA_WAIT(4, a0, a1, a2, a3);               // the next chunk's rows and first block have landed; the second block may still fly
+                    PD_STRIP_WLOAD(wq, b0, b1, b2, b3, 2 * cn + 1);      //   ... + the next chunk's second block [4]
+                    PD_STRIP_WAIT(4, a0, a1, a2, a3);            // the next chunk's rows and first block have landed; the second block may still fly
                 } else {                                         // the last chunk requests nothing (round 6; it used to re-stage itself: 1 / 8 of the loop's L2 traffic
                     block(nt_, a, a0, a1, a2, a3);               //   and a whole load latency at the loop's end, for operands never used)
-                    PD_QA_WAIT(0, b0, b1, b2, b3);
+                    PD_STRIP_WAIT(0, b0, b1, b2, b3);
                     block(nt_, a + CHA, b0, b1, b2, b3);
                 }
             } else {                                             // development variants (see BARE): every wait drains
                 if constexpr (BARE != 2 && BARE != 3) stage64(cn, (c + 1) & 1);
                 if constexpr (BARE != 4) block(nt_, a, a0, a1, a2, a3);
-                if constexpr (BARE != 1 && BARE != 3) PD_QA_WLOAD(a0, a1, a2, a3, 2 * cn);
+                if constexpr (BARE != 1 && BARE != 3) PD_STRIP_WLOAD(wq, a0, a1, a2, a3, 2 * cn);
                 if constexpr (BARE != 4) block(nt_, a + CHA, b0, b1, b2, b3);
-                if constexpr (BARE != 1 && BARE != 3) PD_QA_WLOAD(b0, b1, b2, b3, 2 * cn + 1);
-                PD_QA_WAIT(0, a0, a1, a2, a3);
-                PD_QA_WAIT(0, b0, b1, b2, b3);
+                if constexpr (BARE != 1 && BARE != 3) PD_STRIP_WLOAD(wq, b0, b1, b2, b3, 2 * cn + 1);
+                PD_STRIP_WAIT(0, a0, a1, a2, a3);
+                PD_STRIP_WAIT(0, b0, b1, b2, b3);
             }
             __syncthreads();
         }
-        PD_QA_WAIT(0, b0, b1, b2, b3);
+        PD_STRIP_WAIT(0, b0, b1, b2, b3);
     };
-    if constexpr (M16) {
-        switch (nt16) {
-        case 1: kloop(std::integral_constant<int, 1>()); break;
-        case 2: kloop(std::integral_constant<int, 2>()); break;
-        case 3: kloop(std::integral_constant<int, 3>()); break;
-        case 4: kloop(std::integral_constant<int, 4>()); break;
-        case 5: kloop(std::integral_constant<int, 5>()); break;
-        default: kloop(std::integral_constant<int, 6>()); break;
-        }
-    } else {
-        kloop(std::integral_constant<int, 6>());
+    switch (nt16) {
+    case 1: kloop(std::integral_constant<int, 1>()); break;
+    case 2: kloop(std::integral_constant<int, 2>()); break;
+    case 3: kloop(std::integral_constant<int, 3>()); break;
+    case 4: kloop(std::integral_constant<int, 4>()); break;
+    case 5: kloop(std::integral_constant<int, 5>()); break;
+    default: kloop(std::integral_constant<int, 6>()); break;
     }
-#undef PD_QA_WLOAD
-#undef PD_QA_WAIT
 #undef PD_QA_WAIT_STAGED
     if constexpr (BARE == 5) {
-        if (acc[0][0] + acc4[0][0][0] == 123.456f) g.ctx[tid] = 1u;                // keep the product alive
+        if (acc4[0][0][0] == 123.456f) g.ctx[tid] = 1u;                            // keep the product alive
         return;
     }
     // ---- 2. Q | K | V of the workgroup's rows as fp32 in LDS (every wave is past its last fragment read: the barrier that ended the loop) ----
@@ -284,34 +178,20 @@ __global__ __launch_bounds__(PD_QA_THREADS) void pd_qkv_attn_kernel(PdQkvAttnArg
     float *Sall = img + (size_t)(G * N + 1) * LDR;               // [3 teams][32][LS]
     {
         const float qscale = 0.08838834764831845f;               // 1/sqrt(128): pd_attn_mma_kernel scales q as it stages it
-        if constexpr (M16) {                                     // 16x16 tiles: lane = column % 16 + 16 (row / 4), register = row % 4; a tile not run holds no row < rows
+        // 16x16 tiles: lane = column % 16 + 16 (row / 4), register = row % 4; a tile not run holds no row < rows
 #pragma unroll
-            for (int ct = 0; ct < 2; ++ct) {
-                const float bias = g.bias[ntile * 32 + 16 * ct + l15];               // in_proj row = column of the QKV matrix
-                const int lcol = third * DH + (wave & 3) * 32 + 16 * ct + l15;
+        for (int ct = 0; ct < 2; ++ct) {
+            const float bias = g.bias[ntile * 32 + 16 * ct + l15];               // in_proj row = column of the QKV matrix
+            const int lcol = third * DH + (wave & 3) * 32 + 16 * ct + l15;
 #pragma unroll
-                for (int t = 0; t < 2 * RT; ++t)
+            for (int t = 0; t < 2 * RT; ++t)
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        const int row = 16 * t + 4 * kg + i;
-                        float v = fmaf(acc4[M16 ? t : 0][ct][i], g.c_scale, bias);   // = what pd_gemm_strip_kernel stored as QKV
-                        if (third == 0) v *= qscale;
-                        if (row < rows) img[row * LDR + lcol] = v;
-                    }
-            }
-        } else {
-        const int col = ntile * 32 + l31;                        // in_proj row = column of the QKV matrix
-        const float bias = g.bias[col];
-        const int lcol = third * DH + (wave & 3) * 32 + l31;
-#pragma unroll
-        for (int mi = 0; mi < RT; ++mi)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const int row = mi * 32 + 4 * hi + (i & 3) + 8 * (i >> 2);
-                float v = fmaf(acc[M16 ? 0 : mi][i], g.c_scale, bias);     // = what pd_gemm_strip_kernel stored as QKV
-                if (third == 0) v *= qscale;
-                if (row < rows) img[row * LDR + lcol] = v;
-            }
+                for (int i = 0; i < 4; ++i) {
+                    const int row = 16 * t + 4 * kg + i;
+                    float v = fmaf(acc4[t][ct][i], g.c_scale, bias);             // = what pd_gemm_strip_kernel stored as QKV
+                    if (third == 0) v *= qscale;
+                    if (row < rows) img[row * LDR + lcol] = v;
+                }
         }
         for (int c = tid; c < LDR; c += PD_QA_THREADS) img[G * N * LDR + c] = 0.0f;       // the row every index beyond N reads
     }
@@ -417,8 +297,6 @@ static inline void pd_qkv_attn(const unsigned *hn, const unsigned *Wh, const flo
     const size_t lds = pd_qkv_attn_lds(N);
 #ifdef PD_DEV_KNOBS
     static const int bare = pd_dev_knob("PD_QA_BARE", 0);
-    static const int deep = pd_dev_knob("PD_QA_DEEP", PD_QA_DEEP_DEFAULT);
-    if (bare == 0 && !deep) { hipLaunchKernelGGL((pd_qkv_attn_kernel<0, false>), grid, blk, lds, s, g); return; }
     switch (bare) {
     case 1: hipLaunchKernelGGL(pd_qkv_attn_kernel<1>, grid, blk, lds, s, g); return;
     case 2: hipLaunchKernelGGL(pd_qkv_attn_kernel<2>, grid, blk, lds, s, g); return;
@@ -428,5 +306,5 @@ static inline void pd_qkv_attn(const unsigned *hn, const unsigned *Wh, const flo
     default: break;
     }
 #endif
-    hipLaunchKernelGGL((pd_qkv_attn_kernel<0, PD_QA_DEEP_DEFAULT != 0>), grid, blk, lds, s, g);
+    hipLaunchKernelGGL(pd_qkv_attn_kernel<0>, grid, blk, lds, s, g);
 }

@@ -21,7 +21,7 @@
 #include <vector>
 
 #include "pd_gemm_stream.h"
-#include "pd_gemm_split.h"
+#include "pd_gemm_strip.h"
 
 #define VD 384          // embedding dim
 #define VH 6            // heads
@@ -42,7 +42,7 @@ struct pd_vit {
         float *qkv_wp, *qkv_b, *proj_wp, *proj_b, *fc1_wp, *fc1_b, *fc2a_wp, *fc2b_wp, *fc2_b;
         float *qkv_wf, *proj_wf, *fc1_wf, *fc2_wf;      // row-major copies (LayerNorm scale folded) for the streamed GEMM
         unsigned *qkv_ws, *proj_ws, *fc1_ws, *fc2_ws;   // split into bf16 hi / lo, in MFMA fragment order (pd_frag_split_kernel)
-        unsigned *qkv_wh, *proj_wh, *fc1_wh, *fc2_wh;   // fp16 hi / lo planes of w * 2^e (round 6: the denoiser's fp16-plane mode, pd_gemm_strip_kernel<.., F16>)
+        unsigned *qkv_wh, *proj_wh, *fc1_wh, *fc2_wh;   // fp16 hi / lo planes of w * 2^e (round 6: the denoiser's fp16-plane mode, pd_gemm_strip_kernel)
         float qkv_cs, proj_cs, fc1_cs, fc2_cs;          // accumulator scales 2^-(e_operand + e_weight)
         float ctx_scale, hid_scale;                     // 2^e of the attention output / the GELU hidden rows (split-word operands of proj / fc2)
     } L[VDEPTH_MAX];
@@ -474,7 +474,7 @@ __global__ __launch_bounds__(256) void vit_attn_kernel(const float *__restrict__
                 if constexpr (SPLIT == 1)
                     *(unsigned *)dst = pd_split_word(v);       // feeds vit_gemm_split_kernel
                 else if constexpr (SPLIT == 2)
-                    *(unsigned *)dst = pd_split_word_h(v * out_scale);     // feeds pd_gemm_strip_kernel<.., F16>
+                    *(unsigned *)dst = pd_split_word_h(v * out_scale);     // feeds pd_gemm_strip_kernel
                 else
                     *dst = v;
             }
@@ -679,12 +679,12 @@ extern "C" int pd_vit_forward_scale(pd_vit *v, const float *images, int n_img, i
             // operand pairs (22 bits, static power-of-two scales) with fp32 accumulation; exact erf GELU in FC1's epilogue
             const int M = (int)tokens;
             hipLaunchKernelGGL((pd_ln_rows_kernel<VD, 2>), dim3((M + 3) / 4), dim3(256), 0, s, v->x, v->xn, M, 1e-6f, v->ln_scale);
-            pd_gemm_strip<0, 2, true, 1, true>((const unsigned *)v->xn, VD, L.qkv_wh, VD, L.qkv_b, v->qkv, M, 3 * VD, s, L.qkv_cs);
+            pd_gemm_strip<0, 2>((const unsigned *)v->xn, VD, L.qkv_wh, VD, L.qkv_b, v->qkv, M, 3 * VD, s, L.qkv_cs);
             hipLaunchKernelGGL(vit_attn_kernel<2>, dim3(n_img * VH * nqb), dim3(256), attn_lds, s, v->qkv, v->ctx, T, nqb, L.ctx_scale);
-            pd_gemm_strip<2, 2, true, 1, true>((const unsigned *)v->ctx, VD, L.proj_wh, VD, L.proj_b, v->x, M, VD, s, L.proj_cs);
+            pd_gemm_strip<2, 2>((const unsigned *)v->ctx, VD, L.proj_wh, VD, L.proj_b, v->x, M, VD, s, L.proj_cs);
             hipLaunchKernelGGL((pd_ln_rows_kernel<VD, 2>), dim3((M + 3) / 4), dim3(256), 0, s, v->x, v->xn, M, 1e-6f, v->ln_scale);
-            pd_gemm_strip<3, 2, true, 1, true>((const unsigned *)v->xn, VD, L.fc1_wh, VD, L.fc1_b, v->hid, M, VFF, s, L.fc1_cs, L.hid_scale);
-            pd_gemm_strip<2, 2, true, 1, true>((const unsigned *)v->hid, VFF, L.fc2_wh, VFF, L.fc2_b, v->x, M, VD, s, L.fc2_cs);
+            pd_gemm_strip<3, 2>((const unsigned *)v->xn, VD, L.fc1_wh, VD, L.fc1_b, v->hid, M, VFF, s, L.fc1_cs, L.hid_scale);
+            pd_gemm_strip<2, 2>((const unsigned *)v->hid, VFF, L.fc2_wh, VFF, L.fc2_b, v->x, M, VD, s, L.fc2_cs);
             continue;
         }
         if (streamed && v->exact_fp32 == 2) {

@@ -365,7 +365,7 @@ def test_trace_tools_separate_the_ggs_launch_shapes(tmp_path):
 
 
 def test_fused_attention_block_mapping_covers_every_group_and_head_once():
-    """pd_qkv_attn_kernel's block -> (sequence group, head) mapping (csrc/pd_qkv_attn.h, PD_QA_XCD_MAP = 1, restated here): in chunks of 16 blocks the XCDs
+    """pd_qkv_attn_kernel's block -> (sequence group, head) mapping (csrc/pd_qkv_attn.h, restated here): in chunks of 16 blocks the XCDs
     0 - 3 (= block % 8) host heads {0, 1}, XCDs 4 - 7 heads {2, 3}, XCD x the groups = x mod 4; the groups past the last whole chunk keep the neighbour
     mapping.  Every (group, head) must be some block's, exactly once, for any number of groups; inside whole chunks a block's XCD decides its head pair."""
     for ngrp in list(range(1, 40)) + [64, 65, 103]:

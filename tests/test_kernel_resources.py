@@ -71,8 +71,11 @@ def test_denoiser_kernels_keep_their_register_budget(tmp_path):
     assert len(strip) == 5, sorted(kernels)
     # (round 6) the EPI 2 variants also hold the residual tile, requested a K chunk before the epilogue needs it: 4 RT more 16-byte registers, one wave
     # per SIMD less -- their launches are one workgroup per CU at the bench's shapes (96-row tiles: 216 workgroups; 64-row tiles at 2 060 rows: 132)
+    pairs = {name: re.search(r"pd_gemm_strip_kernelILi(\d+)ELi(\d+)EEv", name) for name in strip}       # <EPI, RT> and nothing else
+    assert all(pairs.values()), sorted(strip)
+    assert {(int(m.group(1)), int(m.group(2))) for m in pairs.values()} == {(0, 2), (2, 2), (4, 2), (2, 3), (4, 3)}, sorted(strip)
     for name, r in strip.items():
-        rt3, epi2 = "ELi3ELb1E" in name, "kernelILi2E" in name
+        rt3, epi2 = "ELi3EEv" in name, "kernelILi2E" in name
         assert r["Occupancy"] >= (3 if rt3 else 4) - (1 if epi2 else 0) and r["VGPRs Spill"] == 0 and r["ScratchSize"] == 0, (name, r)
     dma = {k: v for k, v in kernels.items() if "pd_gemm_dma_kernel" in k}
     assert len(dma) == 5, sorted(kernels)                       # EPI 0, 0 + LN, 1 + LN, 2, and (round 5) 4: _first's step piece + the hoisted z piece

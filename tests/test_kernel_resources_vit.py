@@ -28,6 +28,9 @@ def test_vit_strip_kernels_do_not_spill(tmp_path):
             cur[m.group(1).split("[")[0].strip()] = int(m.group(2))
     strip = {k: v for k, v in kernels.items() if "pd_gemm_strip_kernel" in k}
     assert len(strip) == 3, sorted(kernels)                     # qkv (EPI 0), proj / fc2 (EPI 2), fc1 (EPI 3: GELU), 64-row tiles, fp16 planes, 64-k form
+    pairs = {name: re.search(r"pd_gemm_strip_kernelILi(\d+)ELi(\d+)EEv", name) for name in strip}       # <EPI, RT> and nothing else
+    assert all(pairs.values()), sorted(strip)
+    assert {(int(m.group(1)), int(m.group(2))) for m in pairs.values()} == {(0, 2), (2, 2), (3, 2)}, sorted(strip)
     for name, r in strip.items():
         assert r["VGPRs Spill"] == 0 and r.get("SGPRs Spill", 0) == 0 and r["ScratchSize"] == 0, (name, r)
         # one wave per SIMD less for the instance that holds the residual tile, as in the denoiser

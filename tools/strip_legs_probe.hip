@@ -1,8 +1,8 @@
-// strip_legs_probe.hip -- where a launch of pd_gemm_strip_kernel<.., F16, K64> goes (round 6; development probe, not part of the library): every workgroup
+// strip_legs_probe.hip -- where a launch of pd_gemm_strip_kernel goes (round 6; development probe, not part of the library): every workgroup
 // stamps {wall start / end (wall_clock64, 100 MHz), shader cycles at entry / first operands landed / K loop done / stores drained, XCC id, HW id}; the host
 // prints the launch's timeline (start skew, how many workgroups share a CU) and the legs.  Shapes: the large-batch denoiser's GEMMs at 5 120 rows.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=fast -DPD_STRIP_LEGS -Iinclude tools/strip_legs_probe.hip -o tools/strip_legs_probe && tools/strip_legs_probe
-#include "../posediffusion_amd/csrc/pd_gemm_split.h"
+#include "../posediffusion_amd/csrc/pd_gemm_strip.h"
 #include <algorithm>
 #include <map>
 #include <math.h>
@@ -34,8 +34,8 @@ static void run(const char *name, int M, int N, int K, unsigned *A, uint4 *W, fl
     const int wgs = ((M + TM - 1) / TM) * (N / 128);
     VitSplitArgs g{A, (const unsigned *)W, bias, C, M, N, K, K, 0.5f, 4.0f};
     g.legs = nullptr;
-    (void)hipFuncSetAttribute((const void *)pd_gemm_strip_kernel<EPI, RT, true, 1, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pd_gemm_strip_lds<RT, true>());
-    auto launch = [&]() { hipLaunchKernelGGL((pd_gemm_strip_kernel<EPI, RT, true, 1, 0, true>), dim3(wgs), dim3(256), (pd_gemm_strip_lds<RT, true>()), s, g); };
+    (void)hipFuncSetAttribute((const void *)pd_gemm_strip_kernel<EPI, RT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pd_gemm_strip_lds<RT>());
+    auto launch = [&]() { hipLaunchKernelGGL((pd_gemm_strip_kernel<EPI, RT>), dim3(wgs), dim3(256), (pd_gemm_strip_lds<RT>()), s, g); };
     hipEvent_t e0, e1;
     (void)hipEventCreate(&e0);
     (void)hipEventCreate(&e1);

@@ -96,13 +96,19 @@ RENAMED = [("pd_vt_ln_kernel", "pd_tr_ln_kernel"), ("pd_vt_reduce_acc_kernel<flo
            ("pd_tr_reduce_kernel<double>", "pd_tr_reduce_kernel<double, false>")]
 
 
+def _short(name):
+    """template arguments that only some libraries' sources have: the strip GEMM as <EPI, RT>, the fused attention kernel as <BARE>"""
+    name = re.sub(r"(pd_gemm_strip_kernel<\d+, \d+), true, 1, 0, true>", r"\1>", name.replace("void ", ""))
+    return re.sub(r"(pd_qkv_attn_kernel<\d+), false>", r"\1>", name)
+
+
 def traces(dir_a, dir_b):
     (cols, a), (cols_b, b) = _launches(dir_a), _launches(dir_b)
     assert cols == cols_b
     ren = dict(RENAMED)
-    mapped = [(ren.get(r[0].replace("void ", ""), r[0].replace("void ", "")),) + r[1:] for r in a]
-    b = [(r[0].replace("void ", ""),) + r[1:] for r in b]
-    names_raw = sum(1 for x, y in zip(a, b) if x[0].replace("void ", "") != y[0])
+    mapped = [(ren.get(_short(r[0]), _short(r[0])),) + r[1:] for r in a]
+    b = [(_short(r[0]),) + r[1:] for r in b]
+    names_raw = sum(1 for x, y in zip(a, b) if _short(x[0]) != y[0])
     shape_diff = [i for i, (x, y) in enumerate(zip(mapped, b)) if x[1:] != y[1:]]
     name_diff = [i for i, (x, y) in enumerate(zip(mapped, b)) if x[0] != y[0]]
     digest = lambda rows: hashlib.sha256(repr(rows).encode()).hexdigest()[:16]       # noqa: E731
