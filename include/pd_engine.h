@@ -224,7 +224,7 @@ int pd_p_losses(pd_engine *eng, const float *x_start, const float *z, const int6
  *             pd_engine_set_frame_counts with the same B uses the new counts.
  *   errors    a count outside [1, N] and a call whose B differs from the B of the counts: PD_ERR_INVALID_ARG (the message names the rule);
  *             pd_denoise_step_t and pd_p_losses: PD_ERR_UNSUPPORTED while counts are set (training batches are uniform); pd_time_kernel
- *             ignores the counts.
+ *             ignores the counts.  (A training batch of mixed frame counts: pd_trainer_set_frame_counts, pd_engine_train.h.)
  * Ordered on `stream` (the counts reach the device as kernel arguments); no device synchronisation, no allocation; may be called while
  * earlier work of the same stream is in flight.  The engine keeps a host copy for validation.  With no counts set every call launches
  * exactly what it launched before this entry point existed. */

@@ -66,6 +66,31 @@ void pd_trainer_destroy(pd_trainer *tr);
 int pd_trainer_set_option(pd_trainer *tr, int option, int value);
 int pd_trainer_get_option(pd_trainer *tr, int option, int *value);
 
+/* Sequences of different frame counts in one padded batch -- the trainer's pd_engine_set_frame_counts.  n_frames: HOST int32 [B], each in
+ * [1, N of the later forward]; NULL or B == 0 clears.  Ordered on `stream`: the counts travel as kernel arguments of a small launch into
+ * a device array sized for max_B at pd_trainer_create, so the call neither synchronises nor allocates and the caller's array is free on
+ * return; a host copy serves validation.  The frame limit (64, or PD_TR_OPT_MAX_FRAMES) applies to N.  PD_ERR_INVALID_ARG naming the rule:
+ * here for B outside [0, max_B] or a count outside [1, min(max_N, 256)]; at a forward whose B differs from the counts' B or whose N is
+ * below a count ("every count must lie in [1, N]"), before anything is launched.
+ * While counts are set, pd_train_forward, pd_train_forward_dropout and the pd_train_backward of such a forward mean:
+ *   layout      sequence b has n_frames[b] frames in rows 0 .. n_frames[b]-1 of its N-row block; the other rows are padding.  Nothing is
+ *               packed: the row stride stays N, the pivot column stays at row 0 of each block, and the dropout masks keep their
+ *               definition on the PADDED layout (rows (b nhead + h) N + i and m = b N + i with the padded N).
+ *   attention   a sequence sees its keys < n_frames[b] only, in the forward and in the backward's recomputation of P.  The key-tiled
+ *               kernels serve every N (the short ones hold a uniform batch); at N <= 64 they give the short kernels' bits.
+ *   outputs     padding rows of loss, x_0_pred, x_t, model_out and dz_out are +0.0f.
+ *   inputs      padding rows of x_start, z, noise and g_loss are never read: valid rows of every output and every parameter gradient
+ *               do not depend on what they hold, NaN included.  Every gradient row of a padding row is exactly zero, so it adds nothing
+ *               to the weight, bias and LayerNorm sums or to the time embedding's sum over frames.
+ *   definition  S = sum of g_loss loss over the valid rows.  Slot b's outputs and dz are, bit for bit, those of sequence b run alone
+ *               with N = n_frames[b] (every forward and data-gradient stage is per token row, and attention performs the same operations
+ *               on the same operands in the same order); a parameter gradient is the sum over the sequences run alone, up to the order
+ *               of its sum over rows (chunked by M = B x N, padding rows included as exact zeros).
+ *   pending     the counts of a forward belong to its stash, like the options: the backward uses them even if this function was called
+ *               or cleared in between.
+ * With no counts set every call launches exactly what it launched before and gives the same bits.  NULL trainer: PD_ERR_INVALID_ARG. */
+int pd_trainer_set_frame_counts(pd_trainer *tr, int B, const int32_t *n_frames, void *stream);
+
 /* The contract of pd_p_losses (same outputs, same t_seq clamping -- a clamped timestep raises the trainer's own error word,
  * pd_trainer_check_async) with the weights taken from `w` at the time of the call, and the stash the backward needs:
  * per layer the residual stream at both sublayer inputs, both LayerNorm (mean, rstd) pairs, qkv, ctx and the post-ReLU FF activations;

@@ -168,6 +168,7 @@ TRAIN_SIGNATURES = {
     "pd_trainer_destroy": (None, [_vp]),
     "pd_trainer_set_option": (_i, [_vp, _i, _i]),
     "pd_trainer_get_option": (_i, [_vp, _i, C.POINTER(_i)]),
+    "pd_trainer_set_frame_counts": (_i, [_vp, _i, C.POINTER(C.c_int32), _vp]),
     "pd_train_forward": (_i, [_vp, C.POINTER(pd_weights), _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "pd_train_forward_dropout": (_i, [_vp, C.POINTER(pd_weights), _vp, _vp, _vp, _vp, _i, _i, _i, C.c_float, C.c_uint, C.c_uint64, C.c_uint32,
                                       _vp, _vp, _vp, _vp, _vp]),

@@ -15,6 +15,9 @@
 // before the weight, bias and data gradients of out_proj / linear2 read it.  A call without dropout launches the DROP = false kernels.
 // Attention: N <= 64 runs pd_tr_attn_kernel / pd_tr_attn_bwd_kernel (a sequence whole in LDS), N > 64 -- admitted once PD_TR_OPT_MAX_FRAMES
 // raises the limit -- the key-tiled pd_tr_lattn_* kernels (pd_train_lattn.h); the family a forward ran is remembered with its stash.
+// Frame counts (pd_trainer_set_frame_counts): a padded batch whose sequences have their own frame counts.  The key-tiled
+// attention then serves every N with the counts as the number of keys and rows, q_sample / embed / tail treat padding rows as absent, and
+// everything between is per-row work on rows whose gradient is exactly zero.  A forward copies the counts into its stash's own array.
 // This file is the only one that compiles pd_train_kernels.h: the launch helpers below (pd_train_launch.h) are the backbone trainer's way
 // to the same kernels (pd_vit_train.hip), with acc = false here and its per-scale accumulate switch there.
 #include "pd_train_kernels.h"
@@ -55,7 +58,13 @@ struct pd_trainer {
     int max_frames = PD_TR_MAX_N;                        // PD_TR_OPT_MAX_FRAMES
     int long_attn = 0;                                   // PD_TR_OPT_LONG_ATTN
     int pend_long = 0;                                   // the pending forward ran the key-tiled attention: so does its backward
+    // frame counts per sequence (pd_trainer_set_frame_counts): d_nf follows the entry point, d_nf_pend is the pending forward's own copy
+    int *d_nf = nullptr, *d_nf_pend = nullptr;           // [max_B] each
+    int *nf_host = nullptr;                              // [max_B] host copy, for validation
+    int nf_B = 0;                                        // 0: no counts set
+    int pend_nf = 0;                                     // the pending forward ran with counts (d_nf_pend holds them)
     PdDevAllocs mem{"pd_trainer_create"};
+    ~pd_trainer() { delete[] nf_host; }
 };
 
 // ---- launch helpers shared with pd_vit_train.hip (pd_train_launch.h) --------------------------
@@ -172,11 +181,12 @@ void pd_tr_ln_bwd_launch(const float *dy, const float *x, const float *stats, co
 }
 
 // attention forward of one layer: the short kernel (a sequence whole in LDS) or the key-tiled one
-void pd_tr_attn_launch(bool tiled, const float *qkv, float *ctx, int B, int N, int nh, int hd, int d, float scale, const PdTrDrop *dr, hipStream_t s) {
+void pd_tr_attn_launch(bool tiled, const float *qkv, float *ctx, int B, int N, int nh, int hd, int d, float scale, const PdTrDrop *dr, hipStream_t s,
+                       const int *nf) {
     if (tiled) {
         const dim3 grid(B * nh, (N + PD_TR_LA_ROWS - 1) / PD_TR_LA_ROWS);
-        if (dr) hipLaunchKernelGGL(pd_tr_lattn_kernel<true>, grid, dim3(256), pd_tr_lattn_lds(N, hd), s, qkv, ctx, N, nh, hd, d, scale, *dr);
-        else hipLaunchKernelGGL(pd_tr_lattn_kernel<false>, grid, dim3(256), pd_tr_lattn_lds(N, hd), s, qkv, ctx, N, nh, hd, d, scale, PdTrDrop{});
+        if (dr) hipLaunchKernelGGL(pd_tr_lattn_kernel<true>, grid, dim3(256), pd_tr_lattn_lds(N, hd), s, qkv, ctx, nf, N, nh, hd, d, scale, *dr);
+        else hipLaunchKernelGGL(pd_tr_lattn_kernel<false>, grid, dim3(256), pd_tr_lattn_lds(N, hd), s, qkv, ctx, nf, N, nh, hd, d, scale, PdTrDrop{});
     } else if (dr) {
         hipLaunchKernelGGL(pd_tr_attn_kernel<true>, dim3(B * nh), dim3(256), pd_tr_attn_lds(N, hd), s, qkv, ctx, N, nh, hd, d, scale, *dr);
     } else {
@@ -186,16 +196,16 @@ void pd_tr_attn_launch(bool tiled, const float *qkv, float *ctx, int B, int N, i
 
 // attention backward of one layer: dqkv from qkv and dctx; tiled = phase A (dQ, row statistics) then phase B (dK, dV)
 void pd_tr_attn_bwd_launch(bool tiled, const float *qkv, const float *dctx, float *dqkv, float *la_stats, int B, int N, int nh, int hd, int d,
-                           float scale, const PdTrDrop *dr, hipStream_t s) {
+                           float scale, const PdTrDrop *dr, hipStream_t s, const int *nf) {
     if (tiled) {
         const dim3 rows(B * nh, (N + PD_TR_LA_ROWS - 1) / PD_TR_LA_ROWS), keys(B * nh, pd_tr_la_tiles(N));
         const size_t la = pd_tr_lattn_bwd_rows_lds(N, hd), lb = pd_tr_lattn_bwd_keys_lds(N, hd);
         if (dr) {
-            hipLaunchKernelGGL(pd_tr_lattn_bwd_rows_kernel<true>, rows, dim3(256), la, s, qkv, dctx, dqkv, la_stats, N, nh, hd, d, scale, *dr);
-            hipLaunchKernelGGL(pd_tr_lattn_bwd_keys_kernel<true>, keys, dim3(256), lb, s, qkv, dctx, dqkv, la_stats, N, nh, hd, d, scale, *dr);
+            hipLaunchKernelGGL(pd_tr_lattn_bwd_rows_kernel<true>, rows, dim3(256), la, s, qkv, dctx, dqkv, la_stats, nf, N, nh, hd, d, scale, *dr);
+            hipLaunchKernelGGL(pd_tr_lattn_bwd_keys_kernel<true>, keys, dim3(256), lb, s, qkv, dctx, dqkv, la_stats, nf, N, nh, hd, d, scale, *dr);
         } else {
-            hipLaunchKernelGGL(pd_tr_lattn_bwd_rows_kernel<false>, rows, dim3(256), la, s, qkv, dctx, dqkv, la_stats, N, nh, hd, d, scale, PdTrDrop{});
-            hipLaunchKernelGGL(pd_tr_lattn_bwd_keys_kernel<false>, keys, dim3(256), lb, s, qkv, dctx, dqkv, la_stats, N, nh, hd, d, scale, PdTrDrop{});
+            hipLaunchKernelGGL(pd_tr_lattn_bwd_rows_kernel<false>, rows, dim3(256), la, s, qkv, dctx, dqkv, la_stats, nf, N, nh, hd, d, scale, PdTrDrop{});
+            hipLaunchKernelGGL(pd_tr_lattn_bwd_keys_kernel<false>, keys, dim3(256), lb, s, qkv, dctx, dqkv, la_stats, nf, N, nh, hd, d, scale, PdTrDrop{});
         }
     } else if (dr) {
         hipLaunchKernelGGL(pd_tr_attn_bwd_kernel<true>, dim3(B * nh), dim3(256), pd_tr_attn_bwd_lds(N, hd), s, qkv, dctx, dqkv, N, nh, hd, d, scale, *dr);
@@ -268,7 +278,9 @@ extern "C" int pd_trainer_create(const pd_weights *shape, const float *sqrt_alph
     tr->ws_col_floats = 2 * widest_c * PD_TR_MAX_CHUNKS;
     TR_A(tr->wk.ws, tr->ws_floats); TR_A(tr->wk.ws_col, tr->ws_col_floats);
     TR_A(tr->d_err, 4);
+    TR_A(tr->d_nf, (size_t)max_B); TR_A(tr->d_nf_pend, (size_t)max_B);
 #undef TR_A
+    tr->nf_host = new int[max_B]();
     if (rc == PD_OK && hipMemcpy(tr->qa, sqrt_alphas_cumprod, T * sizeof(float), hipMemcpyDeviceToDevice) != hipSuccess) rc = PD_ERR_HIP;
     if (rc == PD_OK && hipMemcpy(tr->qb, sqrt_one_minus_alphas_cumprod, T * sizeof(float), hipMemcpyDeviceToDevice) != hipSuccess) rc = PD_ERR_HIP;
     if (rc == PD_OK && tr->c_recip) {
@@ -327,6 +339,39 @@ extern "C" int pd_trainer_get_option(pd_trainer *tr, int option, int *value) {
     return PD_OK;
 }
 
+extern "C" int pd_trainer_set_frame_counts(pd_trainer *tr, int B, const int32_t *n_frames, void *stream) {
+    if (!tr) {
+        pd_set_error("pd_trainer_set_frame_counts: NULL trainer");
+        return PD_ERR_INVALID_ARG;
+    }
+    if (!n_frames || B == 0) {
+        tr->nf_B = 0;                // cleared: every later forward is a uniform one (a pending stash keeps its own counts)
+        return PD_OK;
+    }
+    if (B < 0 || B > tr->max_B) {
+        pd_set_error("pd_trainer_set_frame_counts: B=%d must lie in [0, max_B=%d]", B, tr->max_B);
+        return PD_ERR_INVALID_ARG;
+    }
+    const int cap = std::min(tr->max_N, PD_TR_LA_MAX_N);
+    for (int b = 0; b < B; ++b)
+        if (n_frames[b] < 1 || n_frames[b] > cap) {
+            pd_set_error("pd_trainer_set_frame_counts: n_frames[%d]=%d: every count must lie in [1, N] (N <= %d)", b, (int)n_frames[b], cap);
+            return PD_ERR_INVALID_ARG;
+        }
+    hipStream_t s = (hipStream_t)stream;
+    for (int first = 0; first < B; first += PD_TR_NF_CHUNK) {
+        const int n = std::min(PD_TR_NF_CHUNK, B - first);
+        PdTrCountsChunk c;
+        memset(&c, 0, sizeof(c));
+        for (int i = 0; i < n; ++i) c.w[i >> 2] |= (unsigned)(n_frames[first + i] - 1) << (8 * (i & 3));
+        hipLaunchKernelGGL(pd_tr_set_counts_kernel, dim3((n + 255) / 256), dim3(256), 0, s, c, first, n, tr->d_nf);
+    }
+    PD_HIP_CHECK(hipGetLastError());
+    for (int b = 0; b < B; ++b) tr->nf_host[b] = n_frames[b];
+    tr->nf_B = B;
+    return PD_OK;
+}
+
 static int tr_weights_match(const pd_trainer *tr, const pd_weights *w, const char *who) {
     if (!w) {
         pd_set_error("%s: NULL weights", who);
@@ -368,6 +413,18 @@ static int tr_forward(pd_trainer *tr, const pd_weights *w, const float *x_start,
             pd_set_error("%s: N=%d exceeds the trainer's limit of %d frames per sequence (PD_TR_OPT_MAX_FRAMES)", who, N, tr->max_frames);
         return PD_ERR_UNSUPPORTED;
     }
+    if (tr->nf_B) {
+        if (B != tr->nf_B) {
+            pd_set_error("%s: frame counts per sequence are set for B=%d (pd_trainer_set_frame_counts), called with B=%d: a call must use the B "
+                         "of the counts, or clear them", who, tr->nf_B, B);
+            return PD_ERR_INVALID_ARG;
+        }
+        for (int b = 0; b < B; ++b)
+            if (tr->nf_host[b] > N) {
+                pd_set_error("%s: n_frames[%d]=%d (pd_trainer_set_frame_counts) exceeds N=%d: every count must lie in [1, N]", who, b, tr->nf_host[b], N);
+                return PD_ERR_INVALID_ARG;
+            }
+    }
     PD_TRY(tr_weights_match(tr, w, who));
     if (x0_pred_out && !tr->pred_x0 && !tr->c_recip) {
         pd_set_error("%s: x0_pred_out under pred_noise needs sqrt_recip / sqrt_recipm1_alphas_cumprod at pd_trainer_create", who);
@@ -377,17 +434,23 @@ static int tr_forward(pd_trainer *tr, const pd_weights *w, const float *x_start,
     const int M = B * N, d = tr->d, rb = (M + 3) / 4;
     tr->pend_B = tr->pend_N = 0;
     tr->pend_sites = 0;
-    const bool tiled = tr->long_attn || N > PD_TR_MAX_N;
+    // with counts the key-tiled family serves every N; the counts of this forward become its stash's own
+    const int *nf = nullptr;
+    if (tr->nf_B) {
+        hipLaunchKernelGGL(pd_tr_copy_counts_kernel, dim3((B + 255) / 256), dim3(256), 0, s, tr->d_nf, B, tr->d_nf_pend);
+        nf = tr->d_nf_pend;
+    }
+    const bool tiled = tr->long_attn || N > PD_TR_MAX_N || nf;
     PdTrDrop site;
     float *xt = tr->xt;
-    hipLaunchKernelGGL(pd_tr_q_sample_kernel, dim3((M * 9 + 255) / 256), dim3(256), 0, s, x_start, noise, t_seq, tr->qa, tr->qb, M, N, tr->timesteps, xt,
-                       tr->t_b, tr->d_err);
+    hipLaunchKernelGGL(pd_tr_q_sample_kernel, dim3((M * 9 + 255) / 256), dim3(256), 0, s, x_start, noise, t_seq, tr->qa, tr->qb, nf, M, N, tr->timesteps,
+                       xt, tr->t_b, tr->d_err);
     hipLaunchKernelGGL(pd_tr_time_kernel, dim3(B), dim3(128), 0, s, tr->t_b, w->time_w0, w->time_b0, w->time_w2, w->time_b2, tr->t_emb256, tr->t_a0,
                        tr->t_sact, tr->t_emb);
     {
         const size_t total = (size_t)M * tr->Kf;
-        hipLaunchKernelGGL(pd_tr_embed_kernel, dim3((unsigned)std::min<size_t>((total + 255) / 256, 4096)), dim3(256), 0, s, xt, z, tr->t_emb, M, N, tr->z,
-                           tr->pivot, tr->Kf, tr->emb);
+        hipLaunchKernelGGL(pd_tr_embed_kernel, dim3((unsigned)std::min<size_t>((total + 255) / 256, 4096)), dim3(256), 0, s, xt, z, tr->t_emb, nf, M, N,
+                           tr->z, tr->pivot, tr->Kf, tr->emb);
     }
     pd_tr_linear(tr->emb, w->first_w, w->first_b, tr->hres[0], M, d, tr->Kf, 0, nullptr, s);
     const float scale = 1.0f / sqrtf((float)tr->hd);
@@ -397,7 +460,7 @@ static int tr_forward(pd_trainer *tr, const pd_weights *w, const float *x_start,
         float *h0 = tr->hres[2 * l], *h1 = tr->hres[2 * l + 1], *h2 = tr->hres[2 * l + 2];
         pd_tr_ln_launch(h0, tr->hn, W.norm1_w, W.norm1_b, M, d, 1e-5f, S.stats1, s);
         pd_tr_linear(tr->hn, W.in_proj_w, W.in_proj_b, S.qkv, M, 3 * d, d, 0, nullptr, s);
-        pd_tr_attn_launch(tiled, S.qkv, S.ctx, B, N, tr->nhead, tr->hd, d, scale, tr_site(drop, sites, l, 0, &site), s);
+        pd_tr_attn_launch(tiled, S.qkv, S.ctx, B, N, tr->nhead, tr->hd, d, scale, tr_site(drop, sites, l, 0, &site), s, nf);
         pd_tr_linear(S.ctx, W.out_proj_w, W.out_proj_b, h1, M, d, d, 0, h0, s, tr_site(drop, sites, l, 1, &site));
         pd_tr_ln_launch(h1, tr->hn, W.norm2_w, W.norm2_b, M, d, 1e-5f, S.stats2, s);
         pd_tr_linear(tr->hn, W.linear1_w, W.linear1_b, S.ffa, M, tr->ff, d, 1, nullptr, s, tr_site(drop, sites, l, 2, &site));
@@ -407,7 +470,7 @@ static int tr_forward(pd_trainer *tr, const pd_weights *w, const float *x_start,
     PdTrTail ta;
     memset(&ta, 0, sizeof(ta));
     ta.hid = tr->hid_pre; ta.lnw = w->last_ln_w; ta.lnb = w->last_ln_b; ta.w3 = w->last3_w; ta.b3 = w->last3_b;
-    ta.xt = xt; ta.target = tr->pred_x0 ? x_start : noise; ta.t_b = tr->t_b; ta.c_recip = tr->c_recip; ta.c_recipm1 = tr->c_recipm1;
+    ta.xt = xt; ta.target = tr->pred_x0 ? x_start : noise; ta.t_b = tr->t_b; ta.nf = nf; ta.c_recip = tr->c_recip; ta.c_recipm1 = tr->c_recipm1;
     ta.loss_out = loss_out; ta.x0_out = x0_pred_out; ta.model_out = model_out;
     ta.stats = tr->hid_stats; ta.hid_post = tr->hid_post; ta.dl = tr->dl;
     ta.M = M; ta.H = tr->hid; ta.n_frames = N; ta.pred_x0 = tr->pred_x0; ta.loss_type = loss_type;
@@ -419,6 +482,7 @@ static int tr_forward(pd_trainer *tr, const pd_weights *w, const float *x_start,
     tr->pend_drop = drop;
     tr->pend_sites = sites;
     tr->pend_long = tiled ? 1 : 0;
+    tr->pend_nf = nf ? 1 : 0;
     return PD_OK;
 }
 
@@ -475,13 +539,14 @@ extern "C" int pd_train_backward(pd_trainer *tr, const pd_weights *w, const floa
     tr->pend_B = tr->pend_N = 0;
     const PdTrDrop &drop = tr->pend_drop;
     const unsigned sites = tr->pend_sites;
+    const int *nf = tr->pend_nf ? tr->d_nf_pend : nullptr;   // the forward's counts, whatever pd_trainer_set_frame_counts did since
     PdTrDrop site;
     const unsigned mask_blocks = (unsigned)std::min<long long>(((long long)((M + 3) / 4) * d + 255) / 256, 4096);
     // tail: loss derivative -> _last.3 -> ReLU mask -> LayerNorm(hidden) backward
     PdTrTailBwd tb;
     memset(&tb, 0, sizeof(tb));
     tb.g_loss = g_loss; tb.dl = tr->dl; tb.w3 = w->last3_w; tb.lnw = w->last_ln_w; tb.hid = tr->hid_pre; tb.hid_post = tr->hid_post; tb.stats = tr->hid_stats;
-    tb.gout = tr->gout; tb.dy = tr->dy_hid; tb.dhid = tr->dhid; tb.M = M; tb.H = hid;
+    tb.gout = tr->gout; tb.dy = tr->dy_hid; tb.dhid = tr->dhid; tb.M = M; tb.H = hid; tb.n_frames = N; tb.nf = nf;
     hipLaunchKernelGGL(pd_tr_tail_bwd_kernel, dim3(rb), dim3(256), 0, s, tb);
     pd_tr_wgrad(tr->wk, tr->gout, tr->hid_post, grads->last3_w, grads->last3_b, M, 9, hid, false, s);
     pd_tr_ln_param_grads(tr->wk, tr->dy_hid, tr->hid_pre, tr->hid_stats, grads->last_ln_w, grads->last_ln_b, M, hid, false, s);
@@ -517,7 +582,7 @@ extern "C" int pd_train_backward(pd_trainer *tr, const pd_weights *w, const floa
         }
         pd_tr_wgrad(tr->wk, dy1, S.ctx, G.out_proj_w, G.out_proj_b, M, d, d, false, s);
         tr_dgrad(dy1, W.out_proj_w, d, 0, tr->dhn, M, d, d, nullptr, 0, false, s);
-        pd_tr_attn_bwd_launch(tr->pend_long != 0, S.qkv, tr->dhn, tr->dqkv, tr->wk.la_stats, B, N, tr->nhead, tr->hd, d, scale, tr_site(drop, sites, l, 0, &site), s);
+        pd_tr_attn_bwd_launch(tr->pend_long != 0, S.qkv, tr->dhn, tr->dqkv, tr->wk.la_stats, B, N, tr->nhead, tr->hd, d, scale, tr_site(drop, sites, l, 0, &site), s, nf);
         if (G.in_proj_w) pd_tr_ln_launch(h0, tr->hn, W.norm1_w, W.norm1_b, M, d, 1e-5f, S.stats1, s);
         pd_tr_wgrad(tr->wk, tr->dqkv, tr->hn, G.in_proj_w, G.in_proj_b, M, 3 * d, d, false, s);
         tr_dgrad(tr->dqkv, W.in_proj_w, d, 0, tr->dhn, M, 3 * d, d, nullptr, 0, false, s);

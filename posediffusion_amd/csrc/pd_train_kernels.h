@@ -202,13 +202,42 @@ __global__ __launch_bounds__(256) void pd_tr_colsum_kernel(const float *__restri
 // --------------------------------------------------------------------------------------------
 // forward pieces
 // --------------------------------------------------------------------------------------------
+// Frame counts (pd_trainer_set_frame_counts): nf is null on a uniform call, else nf[b] = the frames of sequence b, whose rows
+// nf[b] .. n_frames - 1 of its n_frames-row block are padding.  The first kernels of the pass write +0 there INSTEAD OF reading the
+// caller's rows, the tail writes +0 outputs and dl = 0, its backward takes gout = 0 by a select: every stashed value of a padding row is
+// finite and every gradient row of a padding row is exactly zero, so it adds nothing to any sum over rows.
+__device__ __forceinline__ bool pd_tr_is_padding(const int *__restrict__ nf, int m, int n_frames) {
+    if (!nf) return false;
+    const int b = m / n_frames;
+    return m - b * n_frames >= nf[b];
+}
+// the counts as kernel arguments (count - 1 in a byte, PD_TR_NF_CHUNK per launch), as pd_engine_set_frame_counts sends them: ordered on the
+// stream like any launch, no staging buffer that a later call could overwrite in flight
+#define PD_TR_NF_CHUNK 1024
+struct PdTrCountsChunk {
+    unsigned w[PD_TR_NF_CHUNK / 4];
+};
+__global__ void pd_tr_set_counts_kernel(PdTrCountsChunk v, int first, int n, int *__restrict__ dst) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) dst[first + i] = (int)((v.w[i >> 2] >> (8 * (i & 3))) & 255u) + 1;
+}
+// the counts of a forward belong to its stash: copied at forward time, so that a later pd_trainer_set_frame_counts leaves the backward alone
+__global__ void pd_tr_copy_counts_kernel(const int *__restrict__ src, int n, int *__restrict__ dst) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) dst[i] = src[i];
+}
+
 // q_sample (gaussian_diffuser.py:211-216) in torch's own roundings, and the clamped timestep of every sequence (t_b[b])
 __global__ void pd_tr_q_sample_kernel(const float *__restrict__ x_start, const float *__restrict__ noise, const int64_t *__restrict__ t_seq,
-                                      const float *__restrict__ qa, const float *__restrict__ qb, int M, int n_frames, int timesteps,
-                                      float *__restrict__ xt, int *__restrict__ t_b, unsigned int *err) {
+                                      const float *__restrict__ qa, const float *__restrict__ qb, const int *__restrict__ nf, int M, int n_frames,
+                                      int timesteps, float *__restrict__ xt, int *__restrict__ t_b, unsigned int *err) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= M * 9) return;
     const int m = i / 9, b = m / n_frames;
+    if (pd_tr_is_padding(nf, m, n_frames)) {            // (never row 0 of a sequence, which writes t_b below)
+        xt[i] = 0.0f;
+        return;
+    }
     const long long tv = t_seq[b];
     int t = (int)tv;
     if (tv < 0 || tv >= timesteps) {
@@ -253,13 +282,16 @@ __global__ __launch_bounds__(128) void pd_tr_time_kernel(const int *__restrict__
 // _first's input rows [M, Kf] in the reference's column order (models/denoiser.py:56-68), Kf = 317 + z + pivot, no padding:
 //   [0,180) harmonic(x) | [180,189) x | [189,317) t_emb of the row's sequence | [317,317+z) z | pivot (frame 0 of a sequence)
 __global__ __launch_bounds__(256) void pd_tr_embed_kernel(const float *__restrict__ x, const float *__restrict__ z, const float *__restrict__ temb,
-                                                          int M, int n_frames, int zdim, int pivot, int Kf, float *__restrict__ out) {
+                                                          const int *__restrict__ nf, int M, int n_frames, int zdim, int pivot, int Kf,
+                                                          float *__restrict__ out) {
     const size_t total = (size_t)M * Kf;
     for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
         const int c = (int)(idx % Kf);
         const int row = (int)(idx / Kf);
         float v = 0.0f;
-        if (c < 180) {
+        if (pd_tr_is_padding(nf, row, n_frames)) {
+            // a padding row is +0 in every column: z is not read
+        } else if (c < 180) {
             const int s = c / 90, rem = c - s * 90, d = rem / 10, kk = rem - d * 10;
             const float a = x[(size_t)row * 9 + d] * (float)(1 << kk);
             v = sinf(s ? a + 1.5707963267948966f : a);
@@ -484,6 +516,7 @@ struct PdTrTail {
     const float *lnw, *lnb, *w3, *b3;
     const float *xt, *target;       // [M, 9]
     const int *t_b;                 // [B]
+    const int *nf;                  // [B] frame counts, or null (uniform)
     const float *c_recip, *c_recipm1;   // [timesteps] or null (x0_out then stays unwritten under pred_noise)
     float *loss_out, *x0_out, *model_out;   // [M, 9]; x0_out / model_out may be null
     float *stats, *hid_post, *dl;
@@ -531,6 +564,13 @@ __global__ __launch_bounds__(256) void pd_tr_tail_kernel(PdTrTail g) {
     }
     if (lane < 9) {
         const size_t at = (size_t)m * 9 + lane;
+        if (pd_tr_is_padding(g.nf, m, g.n_frames)) {   // +0 outputs, no loss derivative; the target row is not read
+            if (g.model_out) g.model_out[at] = 0.0f;
+            if (g.x0_out && (g.pred_x0 || g.c_recip)) g.x0_out[at] = 0.0f;
+            g.loss_out[at] = 0.0f;
+            g.dl[at] = 0.0f;
+            return;
+        }
         e += g.b3[lane];
         if (g.model_out) g.model_out[at] = e;
         if (g.x0_out) {
@@ -551,15 +591,17 @@ __global__ __launch_bounds__(256) void pd_tr_tail_kernel(PdTrTail g) {
 // backward = dhid.  gout [M, 9], dy [M, H] (LayerNorm's dgamma / dbeta, _last.3's weight gradient) and dhid [M, H] are written.
 struct PdTrTailBwd {
     const float *g_loss, *dl, *w3, *lnw, *hid, *hid_post, *stats;
+    const int *nf;                  // [B] frame counts of the forward, or null (uniform)
     float *gout, *dy, *dhid;
-    int M, H;
+    int M, H, n_frames;
 };
 __global__ __launch_bounds__(256) void pd_tr_tail_bwd_kernel(PdTrTailBwd g) {
     const int lane = threadIdx.x & 63, m = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (m >= g.M) return;
     float gv = 0.0f;
     if (lane < 9) {
-        gv = g.g_loss[(size_t)m * 9 + lane] * g.dl[(size_t)m * 9 + lane];
+        // a padding row's g_loss is not read (a product with the stashed dl = 0 would pass a NaN on)
+        gv = pd_tr_is_padding(g.nf, m, g.n_frames) ? 0.0f : g.g_loss[(size_t)m * 9 + lane] * g.dl[(size_t)m * 9 + lane];
         g.gout[(size_t)m * 9 + lane] = gv;
     }
     const float mean = g.stats[2 * (size_t)m], rstd = g.stats[2 * (size_t)m + 1];

@@ -21,10 +21,16 @@
 // Summation order at N <= 64 (one tile): absent tiles contribute e = 0, dP = 0, P = 0 and are not added at all, so every operation is that
 // of pd_tr_attn_kernel / pd_tr_attn_bwd_kernel on the same operands -- the same fmaf chains from zero, the same selects, the same products --
 // and the results are theirs bit for bit (PD_TR_OPT_LONG_ATTN = 1 runs these kernels there; tests/test_gpu_train_long.py).
+//
+// Frame counts (pd_trainer_set_frame_counts): `nf` is null on a uniform call, else nf[b] = the frames of sequence b.  N is then the ROW
+// STRIDE alone -- block base, `stats` index, dropout mask row, LDS sizes -- and nk = nf[b] the number of keys and query rows: tile count,
+// jn, the lane selects and the row clamps follow nk, so a slot sees the operations of its sequence alone at N = nk and gives its bits.
+// The grid is that of the padded N: a workgroup whose rows (tile) lie at or beyond nk writes +0 to the padding rows of ctx / dQ (dK, dV)
+// it owns and leaves; `stats` of padding rows are neither written nor read.
 #pragma once
 #include <stddef.h>
 
-#define PD_TR_LA_TILE 64            // keys per tile = lanes of a wavefront
+#define PD_TR_LA_TILE 64           // keys per tile = lanes of a wavefront
 #define PD_TR_LA_RPW 4              // query rows per wave
 #define PD_TR_LA_ROWS (4 * PD_TR_LA_RPW)   // query rows per workgroup (forward, phase A) and per block of phase B
 #define PD_TR_LA_MAX_TILES 4
@@ -58,6 +64,13 @@ __device__ __forceinline__ void pd_tr_la_stage_rows(const float *__restrict__ sr
         float4 q = *(const float4 *)(src + (size_t)min(i0 + r, N - 1) * ld + 4 * d4);
         q.x *= mul; q.y *= mul; q.z *= mul; q.w *= mul;
         *(float4 *)(dst + r * LD + 4 * d4) = q;
+    }
+}
+// +0 into columns 0 .. hd - 1 of rows r0 .. r1 - 1 of dst (row stride ld): the padding rows a workgroup owns while frame counts are set
+__device__ __forceinline__ void pd_tr_la_zero_rows(float *__restrict__ dst, size_t ld, int r0, int r1, int hd) {
+    for (int idx = threadIdx.x; idx < (r1 - r0) * hd; idx += 256) {
+        const int r = idx / hd, c = idx - r * hd;
+        dst[(size_t)(r0 + r) * ld + c] = 0.0f;
     }
 }
 // keys j0 .. j0 + jn - 1 of K (which = 1) or V (which = 2) into dst [64][hd + 4]
@@ -141,25 +154,30 @@ __device__ __forceinline__ void pd_tr_la_mask(const PdTrDrop &dr, unsigned int r
 }
 
 template <bool DROP>
-__global__ __launch_bounds__(256) void pd_tr_lattn_kernel(const float *__restrict__ qkv, float *__restrict__ ctx, int N, int nhead, int hd, int d,
-                                                          float scale, PdTrDrop dr) {
+__global__ __launch_bounds__(256) void pd_tr_lattn_kernel(const float *__restrict__ qkv, float *__restrict__ ctx, const int *__restrict__ nf, int N,
+                                                          int nhead, int hd, int d, float scale, PdTrDrop dr) {
     constexpr int R = PD_TR_LA_RPW, TK = PD_TR_LA_TILE, NT = PD_TR_LA_MAX_TILES;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int LD = hd + 4;
     const int b = blockIdx.x / nhead, h = blockIdx.x % nhead, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int i0 = blockIdx.y * PD_TR_LA_ROWS, nt = pd_tr_la_tiles(N), PS = TK * nt;
+    const int nk = nf ? nf[b] : N;                                      // keys and query rows of this sequence; N stays the row stride
+    const int i0 = blockIdx.y * PD_TR_LA_ROWS, nt = pd_tr_la_tiles(nk), PS = TK * nt;
     const size_t ld3 = (size_t)3 * d;
     const float *base = qkv + (size_t)b * N * ld3 + (size_t)h * hd;
+    if (i0 >= nk) {                                                     // padding rows only (uniform over the workgroup): ctx = +0
+        pd_tr_la_zero_rows(ctx + (size_t)b * N * d + (size_t)h * hd, (size_t)d, i0, min(i0 + PD_TR_LA_ROWS, N), hd);
+        return;
+    }
     float *T = lds, *Q = T + TK * LD, *P = Q + PD_TR_LA_ROWS * LD;      // tile [64][LD], Q [16][LD], P [16][PS]
-    pd_tr_la_stage_rows(base, ld3, i0, N, hd, scale, Q);
+    pd_tr_la_stage_rows(base, ld3, i0, nk, hd, scale, Q);
     float s[R][NT];
-    pd_tr_la_scores(base, ld3, d, N, hd, Q + wave * R * LD, T, s);
+    pd_tr_la_scores(base, ld3, d, nk, hd, Q + wave * R * LD, T, s);
     float *pw = P + wave * R * PS;
 #pragma unroll
     for (int t = 0; t < R; ++t) {
         float mx, inv;
-        pd_tr_la_softmax(s[t], N, lane, &mx, &inv);
-        const int i = min(i0 + wave * R + t, N - 1);
+        pd_tr_la_softmax(s[t], nk, lane, &mx, &inv);
+        const int i = min(i0 + wave * R + t, nk - 1);
 #pragma unroll
         for (int kt = 0; kt < NT; ++kt)
             if (kt < nt) {
@@ -172,7 +190,7 @@ __global__ __launch_bounds__(256) void pd_tr_lattn_kernel(const float *__restric
 #pragma unroll
     for (int t = 0; t < R; ++t) o[t][0] = o[t][1] = 0.0f;
     for (int kt = 0; kt < nt; ++kt) {
-        const int j0 = kt * TK, jn = min(TK, N - j0);
+        const int j0 = kt * TK, jn = min(TK, nk - j0);
         __syncthreads();                                        // the tile buffer is free (and, first round, the wave's P rows are written)
         pd_tr_la_stage_tile(base, ld3, d, 2, j0, jn, hd, T);
         __syncthreads();
@@ -196,7 +214,7 @@ __global__ __launch_bounds__(256) void pd_tr_lattn_kernel(const float *__restric
 #pragma unroll
             for (int cc = 0; cc < 2; ++cc) {
                 const int dd = lane + 64 * cc;
-                if (dd < hd) out[dd] = o[t][cc];
+                if (dd < hd) out[dd] = i < nk ? o[t][cc] : 0.0f;
             }
         }
     }
@@ -205,31 +223,36 @@ __global__ __launch_bounds__(256) void pd_tr_lattn_kernel(const float *__restric
 // phase A of the backward: dQ and the row statistics
 template <bool DROP>
 __global__ __launch_bounds__(256) void pd_tr_lattn_bwd_rows_kernel(const float *__restrict__ qkv, const float *__restrict__ dctx,
-                                                                   float *__restrict__ dqkv, float *__restrict__ stats, int N, int nhead, int hd,
-                                                                   int d, float scale, PdTrDrop dr) {
+                                                                   float *__restrict__ dqkv, float *__restrict__ stats, const int *__restrict__ nf,
+                                                                   int N, int nhead, int hd, int d, float scale, PdTrDrop dr) {
     constexpr int R = PD_TR_LA_RPW, TK = PD_TR_LA_TILE, NT = PD_TR_LA_MAX_TILES;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int LD = hd + 4;
     const int b = blockIdx.x / nhead, h = blockIdx.x % nhead, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int i0 = blockIdx.y * PD_TR_LA_ROWS, nt = pd_tr_la_tiles(N), PS = TK * nt;
+    const int nk = nf ? nf[b] : N;
+    const int i0 = blockIdx.y * PD_TR_LA_ROWS, nt = pd_tr_la_tiles(nk), PS = TK * nt;
     const size_t ld3 = (size_t)3 * d;
     const float *base = qkv + (size_t)b * N * ld3 + (size_t)h * hd;
     const float *dO = dctx + (size_t)b * N * d + (size_t)h * hd;
     float *dbase = dqkv + (size_t)b * N * ld3 + (size_t)h * hd;
+    if (i0 >= nk) {                                                     // padding rows only: dQ = +0 (in_proj's weight gradient sums these rows)
+        pd_tr_la_zero_rows(dbase, ld3, i0, min(i0 + PD_TR_LA_ROWS, N), hd);
+        return;
+    }
     float *T = lds, *Q = T + TK * LD, *G = Q + PD_TR_LA_ROWS * LD, *DS = G + PD_TR_LA_ROWS * LD;    // tile, Q [16][LD], dO [16][LD], dS [16][PS]
-    pd_tr_la_stage_rows(base, ld3, i0, N, hd, scale, Q);
-    pd_tr_la_stage_rows(dO, (size_t)d, i0, N, hd, 1.0f, G);
+    pd_tr_la_stage_rows(base, ld3, i0, nk, hd, scale, Q);
+    pd_tr_la_stage_rows(dO, (size_t)d, i0, nk, hd, 1.0f, G);
     float p[R][NT], dp[R][NT];
-    pd_tr_la_scores(base, ld3, d, N, hd, Q + wave * R * LD, T, p);
+    pd_tr_la_scores(base, ld3, d, nk, hd, Q + wave * R * LD, T, p);
     float mx[R], inv[R];
 #pragma unroll
-    for (int t = 0; t < R; ++t) pd_tr_la_softmax(p[t], N, lane, &mx[t], &inv[t]);
+    for (int t = 0; t < R; ++t) pd_tr_la_softmax(p[t], nk, lane, &mx[t], &inv[t]);
 #pragma unroll
     for (int kt = 0; kt < NT; ++kt) {
 #pragma unroll
         for (int t = 0; t < R; ++t) dp[t][kt] = 0.0f;
         if (kt < nt) {
-            const int j0 = kt * TK, jn = min(TK, N - j0);
+            const int j0 = kt * TK, jn = min(TK, nk - j0);
             __syncthreads();
             pd_tr_la_stage_tile(base, ld3, d, 2, j0, jn, hd, T);
             __syncthreads();
@@ -242,7 +265,7 @@ __global__ __launch_bounds__(256) void pd_tr_lattn_bwd_rows_kernel(const float *
     float *dsw = DS + wave * R * PS;
 #pragma unroll
     for (int t = 0; t < R; ++t) {
-        const int i = i0 + wave * R + t, ic = min(i, N - 1);
+        const int i = i0 + wave * R + t, ic = min(i, nk - 1);
 #pragma unroll
         for (int kt = 0; kt < NT; ++kt)
             if (kt < nt) {
@@ -265,7 +288,7 @@ __global__ __launch_bounds__(256) void pd_tr_lattn_bwd_rows_kernel(const float *
             if (kt < nt) dsw[t * PS + kt * TK + lane] = p[t][kt] * (dp[t][kt] - rs);
         // rs has one value per half of the wave: the fused first step adds a lane's exact product to its partner's rounded one, which is
         // not symmetric between lanes l and l ^ 32; the later steps stay inside a half.  Phase B needs the value of its key's lane.
-        if ((lane & 31) == 0 && i < N) {
+        if ((lane & 31) == 0 && i < nk) {
             float *st = stats + ((size_t)blockIdx.x * N + i) * PD_TR_LA_STATS;
             if (lane == 0) {
                 st[0] = mx[t];
@@ -278,7 +301,7 @@ __global__ __launch_bounds__(256) void pd_tr_lattn_bwd_rows_kernel(const float *
 #pragma unroll
     for (int t = 0; t < R; ++t) o[t][0] = o[t][1] = 0.0f;
     for (int kt = 0; kt < nt; ++kt) {
-        const int j0 = kt * TK, jn = min(TK, N - j0);
+        const int j0 = kt * TK, jn = min(TK, nk - j0);
         __syncthreads();
         pd_tr_la_stage_tile(base, ld3, d, 1, j0, jn, hd, T);
         __syncthreads();
@@ -301,7 +324,7 @@ __global__ __launch_bounds__(256) void pd_tr_lattn_bwd_rows_kernel(const float *
 #pragma unroll
             for (int cc = 0; cc < 2; ++cc) {
                 const int dd = lane + 64 * cc;
-                if (dd < hd) dbase[(size_t)i * ld3 + dd] = scale * o[t][cc];
+                if (dd < hd) dbase[(size_t)i * ld3 + dd] = i < nk ? scale * o[t][cc] : 0.0f;
             }
         }
     }
@@ -310,34 +333,41 @@ __global__ __launch_bounds__(256) void pd_tr_lattn_bwd_rows_kernel(const float *
 // phase B of the backward: dK and dV of one tile of 64 keys
 template <bool DROP>
 __global__ __launch_bounds__(256) void pd_tr_lattn_bwd_keys_kernel(const float *__restrict__ qkv, const float *__restrict__ dctx,
-                                                                   float *__restrict__ dqkv, const float *__restrict__ stats, int N, int nhead,
-                                                                   int hd, int d, float scale, PdTrDrop dr) {
+                                                                   float *__restrict__ dqkv, const float *__restrict__ stats,
+                                                                   const int *__restrict__ nf, int N, int nhead, int hd, int d, float scale,
+                                                                   PdTrDrop dr) {
     constexpr int R = PD_TR_LA_RPW, TK = PD_TR_LA_TILE, PL = PD_TR_LA_PL, KPW = PD_TR_LA_TILE / 4;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int LD = hd + 4;
     const int b = blockIdx.x / nhead, h = blockIdx.x % nhead, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int j0 = blockIdx.y * TK, jn = min(TK, N - j0);
+    const int nk = nf ? nf[b] : N;
+    const int j0 = blockIdx.y * TK, jn = min(TK, nk - j0);
     const size_t ld3 = (size_t)3 * d;
     const float *base = qkv + (size_t)b * N * ld3 + (size_t)h * hd;
     const float *dO = dctx + (size_t)b * N * d + (size_t)h * hd;
     float *dbase = dqkv + (size_t)b * N * ld3 + (size_t)h * hd;
+    if (j0 >= nk) {                                                     // a tile of padding keys only: dK = dV = +0
+        pd_tr_la_zero_rows(dbase + d, ld3, j0, min(j0 + TK, N), hd);
+        pd_tr_la_zero_rows(dbase + 2 * d, ld3, j0, min(j0 + TK, N), hd);
+        return;
+    }
     float *Kt = lds, *Vt = Kt + TK * LD, *Q = Vt + TK * LD, *G = Q + PD_TR_LA_ROWS * LD, *Pb = G + PD_TR_LA_ROWS * LD, *Sb = Pb + PD_TR_LA_ROWS * PL;
     pd_tr_la_stage_tile(base, ld3, d, 1, j0, jn, hd, Kt);
     pd_tr_la_stage_tile(base, ld3, d, 2, j0, jn, hd, Vt);
     float dk[KPW][2], dv[KPW][2];
 #pragma unroll
     for (int k = 0; k < KPW; ++k) dk[k][0] = dk[k][1] = dv[k][0] = dv[k][1] = 0.0f;
-    for (int i0 = 0; i0 < N; i0 += PD_TR_LA_ROWS) {
-        const int in = min(PD_TR_LA_ROWS, N - i0);
-        pd_tr_la_stage_rows(base, ld3, i0, N, hd, scale, Q);    // (the previous block's recomputation has passed the barrier below)
-        pd_tr_la_stage_rows(dO, (size_t)d, i0, N, hd, 1.0f, G);
+    for (int i0 = 0; i0 < nk; i0 += PD_TR_LA_ROWS) {
+        const int in = min(PD_TR_LA_ROWS, nk - i0);
+        pd_tr_la_stage_rows(base, ld3, i0, nk, hd, scale, Q);   // (the previous block's recomputation has passed the barrier below)
+        pd_tr_la_stage_rows(dO, (size_t)d, i0, nk, hd, 1.0f, G);
         __syncthreads();                                        // first round: the K and V tiles too
         float sc[R], dpv[R];
         pd_tr_la_dots(Q + wave * R * LD, Kt, LD, hd / 4, lane, jn, sc);
         pd_tr_la_dots(G + wave * R * LD, Vt, LD, hd / 4, lane, jn, dpv);
 #pragma unroll
         for (int t = 0; t < R; ++t) {
-            const int r = wave * R + t, ic = min(i0 + r, N - 1);
+            const int r = wave * R + t, ic = min(i0 + r, nk - 1);
             const float *st = stats + ((size_t)blockIdx.x * N + ic) * PD_TR_LA_STATS;
             const float mx = st[0], inv = st[1], rs = st[2 + (lane >> 5)];
             const float e = lane < jn ? expf(sc[t] - mx) : 0.0f;
@@ -370,13 +400,13 @@ __global__ __launch_bounds__(256) void pd_tr_lattn_bwd_keys_kernel(const float *
 #pragma unroll
     for (int k = 0; k < KPW; ++k) {
         const int j = wave + 4 * k;
-        if (j < jn) {
+        if (j0 + j < N) {                                       // keys jn .. of the tile are padding rows: +0
 #pragma unroll
             for (int cc = 0; cc < 2; ++cc) {
                 const int dd = lane + 64 * cc;
                 if (dd < hd) {
-                    dbase[(size_t)(j0 + j) * ld3 + d + dd] = scale * dk[k][cc];
-                    dbase[(size_t)(j0 + j) * ld3 + 2 * d + dd] = dv[k][cc];
+                    dbase[(size_t)(j0 + j) * ld3 + d + dd] = j < jn ? scale * dk[k][cc] : 0.0f;
+                    dbase[(size_t)(j0 + j) * ld3 + 2 * d + dd] = j < jn ? dv[k][cc] : 0.0f;
                 }
             }
         }

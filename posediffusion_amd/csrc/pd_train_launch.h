@@ -80,11 +80,12 @@ PD_TR_LOCAL void pd_tr_reduce_launch(const float *ws, long long total, int nz, f
 PD_TR_LOCAL void pd_tr_ln_launch(const float *in, float *out, const float *gamma, const float *beta, int M, int D, float eps, float *stats, hipStream_t s);
 // its data gradient, ADDED to dres
 PD_TR_LOCAL void pd_tr_ln_bwd_launch(const float *dy, const float *x, const float *stats, const float *gamma, int M, int D, float *dres, hipStream_t s);
-// attention forward of one layer: the short kernel (a sequence whole in LDS, N <= 64) or the key-tiled one
+// attention forward of one layer: the short kernel (a sequence whole in LDS, N <= 64) or the key-tiled one.  nf: DEVICE [B] frame counts per
+// sequence (pd_trainer_set_frame_counts; N is then the row stride alone), key-tiled kernels only; null = uniform, the call as it always was
 PD_TR_LOCAL void pd_tr_attn_launch(bool tiled, const float *qkv, float *ctx, int B, int N, int nhead, int hd, int d, float scale, const PdTrDrop *dr,
-                                   hipStream_t s);
+                                   hipStream_t s, const int *nf = nullptr);
 // attention backward of one layer: dqkv from qkv and dctx; tiled = phase A (dQ, row statistics into la_stats) then phase B (dK, dV)
 PD_TR_LOCAL void pd_tr_attn_bwd_launch(bool tiled, const float *qkv, const float *dctx, float *dqkv, float *la_stats, int B, int N, int nhead, int hd,
-                                       int d, float scale, const PdTrDrop *dr, hipStream_t s);
+                                       int d, float scale, const PdTrDrop *dr, hipStream_t s, const int *nf = nullptr);
 
 #endif

@@ -15,7 +15,13 @@ diffuser in ``.train()`` mode whose encoder layers have dropout p > 0.  ``engine
 with masks of its own counter-based generator -- one int64 seed per call from torch's default CPU generator, so ``torch.manual_seed``
 reproduces a run -- and differentiates that function.  The masks are not torch's: the distribution is the reference's, the bits are not.
 The trainer takes sequences of up to 64 frames by default; ``engine_grad_max_frames`` (64 .. 256) raises that (PD_TR_OPT_MAX_FRAMES:
-above 64 frames the attention and its backward run key-tiled kernels)."""
+above 64 frames the attention and its backward run key-tiled kernels).
+``n_frames=`` on ``p_losses`` / ``forward`` (this package's extension): [B] frame counts of a padded batch -- sequence b has n_frames[b]
+frames in rows 0 .. of its N-row block, padding rows of ``x_start``, ``z`` and ``noise`` are never read and padding rows of the results
+are +0.  Such a call goes through the trainer in either grad mode (the engine's forward-only path takes uniform batches): with
+``engine_grad`` and grad mode on the loss is differentiable, otherwise it is the trainer's forward alone.  ``loss`` is [B, N, 9] with +0
+at padding, so the reference's ``loss.mean()`` divides by the padded size; the mean over real frames is
+``loss.sum() / (9 * sum(n_frames))``."""
 import os
 from collections import namedtuple
 
@@ -198,14 +204,19 @@ class GaussianDiffusion(nn.Module):
                                "the trainer applies ONE p at the four sites of every layer")
         return ps[0]
 
-    def _p_losses_grad(self, x_start, t, z, noise):
-        """p_losses through the trainer: ``loss`` carries grad with respect to the denoiser's parameters and z."""
-        from posediffusion_amd.train import p_losses_with_grad
+    def _p_losses_grad(self, x_start, t, z, noise, n_frames=None, grad=True):
+        """p_losses through the trainer: ``loss`` carries grad with respect to the denoiser's parameters and z.  ``grad = False`` (a call
+        with ``n_frames`` under no_grad or without ``engine_grad``): the trainer's forward alone, its stash dropped."""
+        from posediffusion_amd.train import check_frame_counts, p_losses_with_grad
+        if n_frames is not None:
+            n_frames = check_frame_counts(n_frames, x_start.shape[0], x_start.shape[1])
         if self.loss_type not in ("l1", "l2"):
             raise ValueError(f"invalid loss type {self.loss_type}")
         limit = int(getattr(self, "engine_grad_max_frames", 64))
         drop = {}
-        if self.training and getattr(self, "engine_dropout", False):
+        if not getattr(self, "engine_grad", False):
+            pass                                                                    # forward-only default: the eval-mode network, as on the engine
+        elif self.training and getattr(self, "engine_dropout", False):
             p = self._dropout_p()
             if p > 0:                                                               # one draw per call, on the CPU: no device sync
                 drop = {"dropout_p": p, "seed": int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64)), "step": 0}
@@ -217,16 +228,27 @@ class GaussianDiffusion(nn.Module):
             raise RuntimeError(f"engine_grad: N={N} exceeds the trainer's limit of {limit} frames per sequence; set engine_grad_max_frames = {N} "
                                "(at most 256) to train on sequences of this length")
         tr = host.get_trainer(self.model, self, B, N, max_frames=limit)
-        out = p_losses_with_grad(tr, self.model, x_start, z, t, noise, self.loss_type, **drop)
+        if grad:
+            out = p_losses_with_grad(tr, self.model, x_start, z, t, noise, self.loss_type, n_frames=n_frames, **drop)
+        else:
+            with torch.no_grad():
+                out = tr.forward(dict(self.model.named_parameters()), x_start, z, t, noise, self.loss_type, n_frames=n_frames, **drop)
+            tr.drop_stash()
         return {"loss": out["loss"], "noise": noise, "x_0_pred": out["x_0_pred"], "x_t": out["x_t"], "t": t}
 
-    def p_losses(self, x_start, t, z=None, noise=None):
+    def p_losses(self, x_start, t, z=None, noise=None, n_frames=None):
         """``{"loss", "noise", "x_0_pred", "x_t", "t"}`` as the reference returns them; loss elementwise (reduction "none").
-        Eval-mode forward; no grad unless ``engine_grad`` is set and grad mode is on (see the module docstring)."""
+        Eval-mode forward; no grad unless ``engine_grad`` is set and grad mode is on (see the module docstring).
+        ``n_frames`` [B]: frame counts of a padded batch (module docstring); the call then runs on the trainer in either grad mode."""
         limit = int(getattr(self, "engine_grad_max_frames", 64))
         if not 64 <= limit <= 256:
             raise ValueError(f"engine_grad_max_frames = {limit} is outside [64, 256]")
-        if z is not None and getattr(self, "engine_grad", False) and torch.is_grad_enabled():
+        grad = getattr(self, "engine_grad", False) and torch.is_grad_enabled()
+        if n_frames is not None:
+            if z is None:
+                raise NotImplementedError("the denoiser cannot run unconditionally: p_losses needs the image features z")
+            return self._p_losses_grad(x_start, t, z, noise, n_frames=n_frames, grad=grad)
+        if z is not None and grad:
             return self._p_losses_grad(x_start, t, z, noise)
         return self._p_losses_forward_only(x_start, t, z=z, noise=noise)
 

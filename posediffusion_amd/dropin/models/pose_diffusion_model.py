@@ -5,7 +5,10 @@ batch_repeat=-1)`` keeps the reference signature; `training=False` returns
 ``{"pred_cameras": PerspectiveCameras(R, T, focal_length) in PyTorch3D NDC, "z": features}``.
 `training=True` (with ``gt_cameras``) follows :111-126: the diffusion results of ``GaussianDiffusion.forward`` on the encoded cameras plus
 ``pred_cameras`` decoded from ``x_0_pred`` -- the forward half only: eval-mode network, no grad (dropin/models/gaussian_diffuser.py).
-Extension: ``z=`` accepts precomputed image features instead of ``image`` (skips the feature extractor)."""
+Extensions: ``z=`` accepts precomputed image features instead of ``image`` (skips the feature extractor).  ``n_frames=`` [B] (training
+branch): frame counts of a padded batch, handed to the diffuser -- ``gt_cameras`` still holds B x N cameras, the padding entries being any
+valid camera; their ``pred_cameras`` entries carry no meaning, and ``loss`` is +0 there (mean over real frames:
+``loss.sum() / (9 * sum(n_frames))``)."""
 from typing import Dict, List, Optional
 
 import torch
@@ -38,7 +41,7 @@ class PoseDiffusionModel(nn.Module):
             nn.init.constant_(m.weight, 1.0)
 
     def forward(self, image: torch.Tensor = None, gt_cameras=None, sequence_name: Optional[List[str]] = None, cond_fn=None,
-                cond_start_step=0, training=True, batch_repeat=-1, z: Optional[torch.Tensor] = None):
+                cond_start_step=0, training=True, batch_repeat=-1, z: Optional[torch.Tensor] = None, n_frames=None):
         if training and gt_cameras is None:
             raise NotImplementedError("the training branch needs ground-truth cameras (gt_cameras): it computes the diffusion loss of their "
                                       "pose encoding; call with training=False to sample")
@@ -52,9 +55,11 @@ class PoseDiffusionModel(nn.Module):
             if batch_repeat > 0:
                 pose_encoding = pose_encoding.reshape(B * batch_repeat, -1, self.target_dim)
                 z = z.repeat(batch_repeat, 1, 1)
+                if n_frames is not None:
+                    n_frames = [int(v) for v in (n_frames.tolist() if hasattr(n_frames, "tolist") else n_frames)] * batch_repeat
             else:
                 pose_encoding = pose_encoding.reshape(B, -1, self.target_dim)
-            diffusion_results = self.diffuser(pose_encoding, z=z)
+            diffusion_results = self.diffuser(pose_encoding, z=z) if n_frames is None else self.diffuser(pose_encoding, z=z, n_frames=n_frames)
             diffusion_results["pred_cameras"] = pose_encoding_to_camera(diffusion_results["x_0_pred"],
                                                                         pose_encoding_type=self.pose_encoding_type, engine=eng)
             return diffusion_results

@@ -82,7 +82,8 @@ def get_trainer(denoiser: torch.nn.Module, diffuser: torch.nn.Module, B: int, N:
     """``PoseTrainer`` (posediffusion_amd/train.py) for these live modules.  It reads the parameters where they are at every call, so it
     is cached on shape, device, objective and capacity -- NOT on parameter versions: an optimiser step keeps it.  The capacity never
     shrinks.  ``max_frames`` above 64 RAISES the frames per sequence the trainer admits (PD_TR_OPT_MAX_FRAMES), never lowers them on a
-    cached one."""
+    cached one.  Frame counts per sequence (``PoseTrainer.forward(..., n_frames=)``) belong to a call, not to the trainer: B and N here
+    are those of the PADDED batch."""
     from .train import PoseTrainer, shape_from_modules
     dev = next(denoiser.parameters()).device
     if dev.type != "cuda":

@@ -8,9 +8,14 @@ frames by default and up to 256 with ``max_frames`` / ``set_max_frames`` (PD_TR_
 key-tiled kernels, which at N <= 64 give the bits of the default ones (``set_long_attn``, for the tests).
 Without ``dropout_p`` it is the eval-mode function; with it, the ``.train()``-mode one: dropout at the four sites of every encoder layer
 (``DROPOUT_SITES``), masks from Philox4x32-10 keyed by ``(seed, step)`` and recomputed by the backward (pd_train_forward_dropout).
+``n_frames=`` / ``set_frame_counts``: a padded batch whose sequences have different frame counts (pd_trainer_set_frame_counts) --
+sequence b has n_frames[b] frames in rows 0 .. of its N-row block, padding rows of every output are +0 and what they hold on input is
+never read.  ``loss`` is [B, N, 9] with +0 at padding, so ``loss.mean()`` divides by the PADDED size; the mean over the real frames is
+``loss.sum() / (9 * sum(n_frames))``.
 No CPU path: a missing library or GPU raises."""
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 from typing import Dict, Iterable, List, Optional
 
@@ -52,6 +57,18 @@ def shape_from_modules(denoiser: torch.nn.Module, diffuser: Optional[torch.nn.Mo
             "z_dim": denoiser._first.weight.shape[1] - (9 * 21 + t_emb_dim // 2 + int(pivot)),
             "norm_first": bool(layer.norm_first), "pivot": pivot,
             "objective": getattr(diffuser, "objective", "pred_noise") if diffuser is not None else "pred_noise"}
+
+
+def check_frame_counts(n_frames, B: int, N: int) -> List[int]:
+    """``n_frames`` as a list of ints after the rule of pd_trainer_set_frame_counts: one count per sequence, each in [1, N]."""
+    if isinstance(n_frames, torch.Tensor):
+        n_frames = n_frames.detach().cpu().tolist()
+    counts = [int(v) for v in n_frames]
+    if len(counts) != B:
+        raise ValueError(f"n_frames must hold one frame count per sequence ({B}), got {len(counts)}")
+    if min(counts) < 1 or max(counts) > N:
+        raise ValueError(f"n_frames: every count must lie in [1, N] (N={N}), got {counts}")
+    return counts
 
 
 def _set(struct, field: str, ptr: Optional[int]):
@@ -173,18 +190,54 @@ class PoseTrainer:
     def check_async(self):
         _lib.check(self.lib.pd_trainer_check_async(self._h), "pd_trainer_check_async")
 
+    # ---------------------------------------------------------------- frame counts per sequence
+    def set_frame_counts(self, n_frames=None) -> None:
+        """pd_trainer_set_frame_counts: ``n_frames`` [B] ints -- sequence b of every later ``forward`` with that B has n_frames[b] frames,
+        in rows 0 .. n_frames[b]-1 of its N-row block; the other rows are padding.  ``None`` clears.  A pending stash keeps the counts of
+        its own forward.  Ordered on the current stream, no synchronisation; the C entry validates and its message is the one raised."""
+        if n_frames is None:
+            _lib.check(self.lib.pd_trainer_set_frame_counts(self._h, 0, None, self._stream()), "pd_trainer_set_frame_counts")
+            return
+        if isinstance(n_frames, torch.Tensor):
+            n_frames = n_frames.detach().cpu().tolist()
+        counts = [int(v) for v in n_frames]
+        arr = (C.c_int32 * max(len(counts), 1))(*counts)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.pd_trainer_set_frame_counts(self._h, len(counts), arr, self._stream()), "pd_trainer_set_frame_counts")
+
+    @contextlib.contextmanager
+    def _counts(self, n_frames):
+        """The ``n_frames=`` keyword of ``forward``: set for the call, cleared afterwards (also when the call raises)."""
+        if n_frames is None:
+            yield
+            return
+        self.set_frame_counts(n_frames)
+        try:
+            yield
+        finally:
+            self.set_frame_counts(None)
+
+    def drop_stash(self) -> None:
+        """Forget the pending forward (a forward-only call): ``backward`` refuses until the next ``forward``."""
+        self._pending = None
+
     # ---------------------------------------------------------------- forward / backward
     def forward(self, params: Dict[str, torch.Tensor], x_start: torch.Tensor, z: torch.Tensor, t: torch.Tensor, noise: torch.Tensor,
-                loss_type: str = "l1", dropout_p: float = 0.0, dropout_sites: int = ALL, seed: int = 0, step: int = 0) -> Dict[str, torch.Tensor]:
+                loss_type: str = "l1", dropout_p: float = 0.0, dropout_sites: int = ALL, seed: int = 0, step: int = 0,
+                n_frames=None) -> Dict[str, torch.Tensor]:
         """pd_train_forward: ``{"loss", "x_0_pred", "x_t", "model_out"}`` (each [B, N, 9]) from the live ``params`` (state-dict names ->
         tensors), with the stash one ``backward`` consumes.  ``dropout_p`` > 0: pd_train_forward_dropout at the sites in ``dropout_sites``
         (bits of ``DROPOUT_SITES``) with the masks of ``(seed, step)`` (seed: any int, taken modulo 2^64; step: uint32); ``backward`` then
-        differentiates that function.  ``dropout_p == 0`` or ``dropout_sites == 0`` is the call without dropout, bit for bit."""
+        differentiates that function.  ``dropout_p == 0`` or ``dropout_sites == 0`` is the call without dropout, bit for bit.
+        ``n_frames`` [B]: frame counts per sequence (``set_frame_counts``), set for this call and cleared after it; the stash keeps them
+        for ``backward``.  Padding rows of the four outputs are +0; the mean loss over real frames is ``loss.sum() / (9 * sum(n_frames))``."""
         if loss_type not in _LOSS_TYPES:
             raise ValueError(f"invalid loss type {loss_type}")
         if not 0 <= int(step) < 2 ** 32:
             raise ValueError(f"step must fit 32 unsigned bits, got {step}")
         B, N, _ = x_start.shape
+        if n_frames is not None:
+            n_frames = check_frame_counts(n_frames, B, N)
         live = self._live(params)
         x_start, z, noise = self._f32(x_start, (B, N, 9)), self._f32(z, (B, N, int(self.shape["z_dim"]))), self._f32(noise, (B, N, 9))
         t = torch.as_tensor(t).reshape(-1).to(device=self.device, dtype=torch.int64).contiguous()
@@ -193,7 +246,7 @@ class PoseTrainer:
         out = {k: torch.empty_like(x_start) for k in ("loss", "x_0_pred", "x_t", "model_out")}
         w = self._weights_struct(live)
         self._pending = None
-        with torch.cuda.device(self.device):
+        with torch.cuda.device(self.device), self._counts(n_frames):
             outs = (out["loss"].data_ptr(), out["x_0_pred"].data_ptr(), out["x_t"].data_ptr(), out["model_out"].data_ptr(), self._stream())
             ins = (self._h, C.byref(w), x_start.data_ptr(), z.data_ptr(), t.data_ptr(), noise.data_ptr(), B, N, _LOSS_TYPES[loss_type])
             if float(dropout_p) == 0.0 and 0 <= int(dropout_sites) <= ALL:
@@ -247,7 +300,7 @@ class PoseTrainer:
 class _PLossesFn(torch.autograd.Function):
     """(trainer, loss_type, x_start, z, t, noise, *params) -> (loss, x_0_pred, x_t, model_out); only ``loss`` is differentiable, with
     respect to the parameters (passed flat so that autograd routes their gradients) and z.  ``loss_type`` is the string, or the tuple
-    ``(loss_type, dropout_p, dropout_sites, seed, step)`` of a forward with dropout."""
+    ``(loss_type, dropout_p, dropout_sites, seed, step[, n_frames])`` of a forward with dropout and / or frame counts."""
 
     @staticmethod
     def forward(ctx, trainer, loss_type, x_start, z, t, noise, *params):
@@ -278,11 +331,15 @@ class _PLossesFn(torch.autograd.Function):
 
 
 def p_losses_with_grad(trainer: PoseTrainer, denoiser: torch.nn.Module, x_start, z, t, noise, loss_type: str = "l1", dropout_p: float = 0.0,
-                       dropout_sites: int = ALL, seed: int = 0, step: int = 0) -> Dict[str, torch.Tensor]:
-    """The p_losses dict of ``trainer.forward`` (same dropout keywords) with ``loss`` attached to ``denoiser``'s parameters (and to z when
-    it requires grad)."""
+                       dropout_sites: int = ALL, seed: int = 0, step: int = 0, n_frames=None) -> Dict[str, torch.Tensor]:
+    """The p_losses dict of ``trainer.forward`` (same dropout and ``n_frames`` keywords) with ``loss`` attached to ``denoiser``'s
+    parameters (and to z when it requires grad).  With ``n_frames`` the gradient of padding rows of z is +0."""
+    if n_frames is not None:
+        n_frames = check_frame_counts(n_frames, x_start.shape[0], x_start.shape[1])
     named = dict(denoiser.named_parameters())
     params = [named[n] for n in trainer.names]
     mode = loss_type if float(dropout_p) == 0.0 and 0 <= int(dropout_sites) <= ALL else (loss_type, dropout_p, dropout_sites, seed, step)
+    if n_frames is not None:
+        mode = ((loss_type, 0.0, ALL, 0, 0) if isinstance(mode, str) else mode) + (n_frames,)
     loss, x0, xt, mo = _PLossesFn.apply(trainer, mode, x_start, z, t, noise, *params)
     return {"loss": loss, "x_0_pred": x0, "x_t": xt, "model_out": mo}
