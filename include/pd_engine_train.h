@@ -14,6 +14,9 @@
  *     encoder layers' dropout (masks from a counter-based generator, recomputed by the backward, never stored);
  *   - no float atomics in any reduction: gradients are bitwise reproducible and do not depend on the trainer's capacity (every
  *     reduction over token rows is chunked by a function of M = B x N alone and its partial sums are added in chunk order);
+ *   - three outputs of the forward are differentiable: loss, model_out and x_0_pred (pd_train_backward_ex takes an upstream gradient of
+ *     each; pd_train_backward is the loss alone); x_t is data.  pd_pose_to_camera_backward takes a loss on the cameras decoded from
+ *     x_0_pred back to x_0_pred;
  *   - the image backbone is not this object's: dz is handed back for whoever owns z -- pd_vit_trainer (pd_engine_vit_train.h) takes it on
  *     to the backbone's parameters.
  * Conventions are those of pd_engine.h (return codes, pd_last_error, `stream` = hipStream_t as void *).  Both calls are asynchronous on
@@ -124,11 +127,41 @@ int pd_train_forward_dropout(pd_trainer *tr, const pd_weights *w, const float *x
 
 /* With S = sum(g_loss * loss) over the [B, N, 9] elements: writes dS/dtheta for every non-NULL member of `grads` (an overwrite, in the
  * parameter's own layout; a NULL member's weight-gradient launch is not issued) and dS/dz [B, N, z_dim] when dz_out is non-NULL.
- * Loss derivative: sign(d) with sign(0) = 0 (l1), 2 d (l2), d = model_out - target; x_0_pred carries no gradient.
+ * Loss derivative: sign(d) with sign(0) = 0 (l1), 2 d (l2), d = model_out - target; x_0_pred and model_out carry no gradient here
+ * (pd_train_backward_ex takes theirs).
  * After pd_train_forward_dropout it differentiates that call's function (same masks).
- * Consumes the stash: PD_ERR_STATE when no forward is pending.  `w` must point to the same unmodified tensors as the forward's. */
+ * Consumes the stash: PD_ERR_STATE when no forward is pending.  `w` must point to the same unmodified tensors as the forward's.
+ * It is pd_train_backward_ex(tr, w, g_loss, NULL, NULL, grads, dz_out, stream): the same launches, the same bits. */
 int pd_train_backward(pd_trainer *tr, const pd_weights *w, const float *g_loss, const pd_weight_grads *grads, float *dz_out,
                       void *stream);
+
+/* pd_train_backward with upstream gradients of the other two differentiable outputs of the forward:
+ *   S = sum(g_loss * loss) + sum(g_model_out * model_out) + sum(g_x0_pred * x_0_pred)   over the valid rows,
+ * each upstream [B, N, 9] DEVICE fp32, each may be NULL (the term is absent); all three NULL: PD_ERR_INVALID_ARG.  x_t is data.
+ * The row vector that enters _last.3 is the sum of the PRESENT terms in this order -- an absent term is not added, not even as "+ 0":
+ *   g_loss * dl,   g_model_out,   k_b * g_x0_pred
+ * with k_b = 1 under pred_x0 (x_0_pred is model_out) and k_b = -sqrt_recipm1_alphas_cumprod[t_b] under pred_noise (x_0_pred =
+ * sqrt_recip x_t - sqrt_recipm1 model_out; the fp32 table copied at pd_trainer_create, at the forward's clamped t).  One term alone is
+ * that single fp32 product, or the plain value for g_model_out (and for g_x0_pred under pred_x0).  g_x0_pred under pred_noise on a
+ * trainer created without the recip tables: PD_ERR_STATE naming them, before anything is launched (the stash stays pending).
+ * Padding rows of all three upstreams are never read, NaN included; the row vector is zero there.
+ * Everything else is pd_train_backward's contract: it consumes the stash, uses the forward's pending attention family, frame counts and
+ * dropout masks, skips the launches of NULL members of `grads`, and uses no float atomics. */
+int pd_train_backward_ex(pd_trainer *tr, const pd_weights *w, const float *g_loss, const float *g_model_out, const float *g_x0_pred,
+                         const pd_weight_grads *grads, float *dz_out, void *stream);
+
+/* Backward of pd_pose_to_camera_ex (pose_encoding_to_camera, util/camera_transform.py:64-105).  Stateless like pd_camera_to_pose: no
+ * pd_engine.  The decode is recomputed from enc [n, 9] with the forward kernel's expressions; g_R [n, 9], g_T [n, 3], g_focal [n, 2]
+ * (DEVICE fp32) may each be NULL (= zero), not all three.  g_enc_out [n, 9]:
+ *   columns 0-2  g_T, copied;
+ *   columns 3-6  the gradient through pytorch3d's quaternion_to_matrix (real part first, two_s = 2 / |q|^2, no normalisation);
+ *   columns 7-8  g_focal * f where min <= f = exp(logFL + bias) <= max, 0 outside (torch.clamp passes the gradient on the closed
+ *                interval).
+ * One thread per camera, the forward's grid.  PD_ERR_INVALID_ARG naming the function for NULL enc / g_enc_out, n_cameras <= 0 or
+ * all-NULL upstreams. */
+int pd_pose_to_camera_backward(const float *enc, const float *g_R, const float *g_T, const float *g_focal,
+                               int n_cameras, float log_focal_length_bias, float min_focal_length,
+                               float max_focal_length, float *g_enc_out, void *stream);
 
 /* The tests' window into the stash of the pending (or last) forward: layer < num_layers -> that layer's [B x N, dim_ff] post-ReLU FF
  * activations; layer == num_layers -> _last's [B x N, mlp_hidden] post-ReLU values.  n_floats must be exactly that size.  The stash is

@@ -173,6 +173,8 @@ TRAIN_SIGNATURES = {
     "pd_train_forward_dropout": (_i, [_vp, C.POINTER(pd_weights), _vp, _vp, _vp, _vp, _i, _i, _i, C.c_float, C.c_uint, C.c_uint64, C.c_uint32,
                                       _vp, _vp, _vp, _vp, _vp]),
     "pd_train_backward": (_i, [_vp, C.POINTER(pd_weights), _vp, C.POINTER(pd_weight_grads), _vp, _vp]),
+    "pd_train_backward_ex": (_i, [_vp, C.POINTER(pd_weights), _vp, _vp, _vp, C.POINTER(pd_weight_grads), _vp, _vp]),
+    "pd_pose_to_camera_backward": (_i, [_vp, _vp, _vp, _vp, _i, C.c_float, C.c_float, C.c_float, _vp, _vp]),
     "pd_train_debug_relu": (_i, [_vp, _i, _vp, C.c_longlong, _vp]),
     "pd_trainer_check_async": (_i, [_vp]),
 }

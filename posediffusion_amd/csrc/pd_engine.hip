@@ -144,7 +144,53 @@ __global__ void pd_camera_kernel(const float *__restrict__ enc, int n, float *__
     F[c * 2 + 1] = pd_clamp_torch(expf(x[8] + fl_bias), fl_min, fl_max);
 }
 
-// camera_to_pose_encoding (camera_transform.py:108-129), one thread per camera: enc = [T | matrix_to_quaternion(R) | log(clamp(focal)) - bias].
+// backward of pd_camera_kernel, one thread per camera on the forward's grid: g_enc = [g_T | d quaternion_to_matrix | g_focal f inside the
+// clamp].  The decode is recomputed from enc with the forward's expressions.  With s = two_s = 2 / |q|^2 and R = I + s A(q), A's entries
+// quadratic in q:  dS/dq_x = s (sum_e gR_e dA_e/dq_x) - s^2 q_x (sum_e gR_e A_e)   (ds/dq_x = -s^2 q_x).
+// torch.clamp passes the gradient on the closed interval [min, max] (a NaN focal fails both comparisons: 0).  NULL upstream = zero.
+__global__ void pd_camera_bwd_kernel(const float *__restrict__ enc, const float *__restrict__ gR, const float *__restrict__ gT,
+                                     const float *__restrict__ gF, int n, float fl_bias, float fl_min, float fl_max,
+                                     float *__restrict__ g_enc) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= n) return;
+    const float *x = enc + (size_t)c * 9;
+    float *o = g_enc + (size_t)c * 9;
+    o[0] = gT ? gT[c * 3 + 0] : 0.0f;
+    o[1] = gT ? gT[c * 3 + 1] : 0.0f;
+    o[2] = gT ? gT[c * 3 + 2] : 0.0f;
+    float gq[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (gR) {
+        const float *m = gR + (size_t)c * 9;
+        const float g0 = m[0], g1 = m[1], g2 = m[2], g3 = m[3], g4 = m[4], g5 = m[5], g6 = m[6], g7 = m[7], g8 = m[8];
+        const float r = x[3], i = x[4], j = x[5], k = x[6];
+        const float two_s = 2.0f / (r * r + i * i + j * j + k * k);
+        // sum_e gR_e A_e with the forward's A: R_e = delta_e + two_s A_e
+        const float ga = -g0 * (j * j + k * k) + g1 * (i * j - k * r) + g2 * (i * k + j * r) + g3 * (i * j + k * r) - g4 * (i * i + k * k) +
+                         g5 * (j * k - i * r) + g6 * (i * k - j * r) + g7 * (j * k + i * r) - g8 * (i * i + j * j);
+        const float s12 = g1 + g3, s02 = g2 + g6, s57 = g5 + g7;           // symmetric pairs
+        const float a31 = g3 - g1, a26 = g2 - g6, a75 = g7 - g5;           // antisymmetric pairs (the real part's terms)
+        const float dr = k * a31 + j * a26 + i * a75;
+        const float di = j * s12 + k * s02 + r * a75 - 2.0f * i * (g4 + g8);
+        const float dj = i * s12 + k * s57 + r * a26 - 2.0f * j * (g0 + g8);
+        const float dk = i * s02 + j * s57 + r * a31 - 2.0f * k * (g0 + g4);
+        const float t = two_s * two_s * ga;
+        gq[0] = two_s * dr - t * r;
+        gq[1] = two_s * di - t * i;
+        gq[2] = two_s * dj - t * j;
+        gq[3] = two_s * dk - t * k;
+    }
+    o[3] = gq[0] + 0.0f;                     // (-0 of an all-zero g_R becomes the +0 of a NULL one)
+    o[4] = gq[1] + 0.0f;
+    o[5] = gq[2] + 0.0f;
+    o[6] = gq[3] + 0.0f;
+#pragma unroll
+    for (int a = 0; a < 2; ++a) {
+        const float f = expf(x[7 + a] + fl_bias);
+        o[7 + a] = (gF && f >= fl_min && f <= fl_max) ? gF[c * 2 + a] * f : 0.0f;
+    }
+}
+
+// camera_to_pose_encoding (camera_transform.py:108-129), one thread per camera: enc =[T | matrix_to_quaternion(R) | log(clamp(focal)) - bias].
 // The quaternion follows current pytorch3d (transforms/rotation_conversions.py matrix_to_quaternion): the four candidates
 // q_abs = sqrt(max(0, 1 +- m00 +- m11 +- m22)), the candidate row of the largest q_abs divided by 2 max(q_abs, 0.1), standardised to a
 // non-negative real part.  pytorch3d itself is not a dependency of this project: the yardstick of this kernel is the fp64 restatement of
@@ -500,6 +546,24 @@ extern "C" int pd_pose_to_camera_ex(pd_engine *eng, const float *enc, int n_came
 extern "C" int pd_pose_to_camera(pd_engine *eng, const float *enc, int n_cameras, float *R_out, float *T_out,
                                  float *focal_out, void *stream) {
     return pd_pose_to_camera_ex(eng, enc, n_cameras, R_out, T_out, focal_out, 1.8f, 0.1f, 20.0f, stream);
+}
+
+// declared in include/pd_engine_train.h (the function list of pd_engine.h is pinned); stateless like pd_camera_to_pose
+extern "C" int pd_pose_to_camera_backward(const float *enc, const float *g_R, const float *g_T, const float *g_focal, int n_cameras,
+                                          float log_focal_length_bias, float min_focal_length, float max_focal_length, float *g_enc_out,
+                                          void *stream) {
+    if (!enc || !g_enc_out || n_cameras <= 0) {
+        pd_set_error("pd_pose_to_camera_backward: invalid arguments (n_cameras=%d; enc and g_enc_out must not be NULL)", n_cameras);
+        return PD_ERR_INVALID_ARG;
+    }
+    if (!g_R && !g_T && !g_focal) {
+        pd_set_error("pd_pose_to_camera_backward: g_R, g_T and g_focal are all NULL: at least one upstream gradient is needed");
+        return PD_ERR_INVALID_ARG;
+    }
+    hipLaunchKernelGGL(pd_camera_bwd_kernel, dim3((n_cameras + 63) / 64), dim3(64), 0, (hipStream_t)stream, enc, g_R, g_T, g_focal,
+                       n_cameras, log_focal_length_bias, min_focal_length, max_focal_length, g_enc_out);
+    PD_HIP_CHECK(hipGetLastError());
+    return PD_OK;
 }
 
 // ---- GGS API ------------------------------------------------------------------------------------

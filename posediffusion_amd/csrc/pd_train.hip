@@ -523,17 +523,18 @@ extern "C" int pd_train_forward_dropout(pd_trainer *tr, const pd_weights *w, con
     return tr_forward(tr, w, x_start, z, t_seq, noise, B, N, loss_type, drop, sites, "pd_train_forward_dropout", loss_out, x0_pred_out, xt_out, model_out, stream);
 }
 
-extern "C" int pd_train_backward(pd_trainer *tr, const pd_weights *w, const float *g_loss, const pd_weight_grads *grads, float *dz_out,
-                                 void *stream) {
-    if (!tr || !g_loss || !grads) {
-        pd_set_error("pd_train_backward: NULL trainer, g_loss or grads");
-        return PD_ERR_INVALID_ARG;
-    }
+// pd_train_backward (g_loss alone) and pd_train_backward_ex: `who` names the entry point in every message
+static int tr_backward(pd_trainer *tr, const pd_weights *w, const float *g_loss, const float *g_model_out, const float *g_x0_pred,
+                       const pd_weight_grads *grads, float *dz_out, void *stream, const char *who) {
     if (tr->pend_B < 1 || tr->pend_N < 1) {
-        pd_set_error("pd_train_backward: no forward is pending (pd_train_forward fills the stash that one backward consumes)");
+        pd_set_error("%s: no forward is pending (pd_train_forward fills the stash that one backward consumes)", who);
         return PD_ERR_STATE;
     }
-    PD_TRY(tr_weights_match(tr, w, "pd_train_backward"));
+    if (g_x0_pred && !tr->pred_x0 && !tr->c_recipm1) {
+        pd_set_error("%s: g_x0_pred under pred_noise needs sqrt_recip / sqrt_recipm1_alphas_cumprod at pd_trainer_create", who);
+        return PD_ERR_STATE;
+    }
+    PD_TRY(tr_weights_match(tr, w, who));
     hipStream_t s = (hipStream_t)stream;
     const int B = tr->pend_B, N = tr->pend_N, M = B * N, d = tr->d, ff = tr->ff, hid = tr->hid, rb = (M + 3) / 4, Lc = tr->layers;
     tr->pend_B = tr->pend_N = 0;
@@ -545,7 +546,8 @@ extern "C" int pd_train_backward(pd_trainer *tr, const pd_weights *w, const floa
     // tail: loss derivative -> _last.3 -> ReLU mask -> LayerNorm(hidden) backward
     PdTrTailBwd tb;
     memset(&tb, 0, sizeof(tb));
-    tb.g_loss = g_loss; tb.dl = tr->dl; tb.w3 = w->last3_w; tb.lnw = w->last_ln_w; tb.hid = tr->hid_pre; tb.hid_post = tr->hid_post; tb.stats = tr->hid_stats;
+    tb.g_loss = g_loss; tb.g_mo = g_model_out; tb.g_x0 = g_x0_pred; tb.c_recipm1 = tr->c_recipm1; tb.t_b = tr->t_b; tb.pred_x0 = tr->pred_x0;
+    tb.dl = tr->dl; tb.w3 = w->last3_w; tb.lnw = w->last_ln_w; tb.hid = tr->hid_pre; tb.hid_post = tr->hid_post; tb.stats = tr->hid_stats;
     tb.gout = tr->gout; tb.dy = tr->dy_hid; tb.dhid = tr->dhid; tb.M = M; tb.H = hid; tb.n_frames = N; tb.nf = nf;
     hipLaunchKernelGGL(pd_tr_tail_bwd_kernel, dim3(rb), dim3(256), 0, s, tb);
     pd_tr_wgrad(tr->wk, tr->gout, tr->hid_post, grads->last3_w, grads->last3_b, M, 9, hid, false, s);
@@ -603,6 +605,28 @@ extern "C" int pd_train_backward(pd_trainer *tr, const pd_weights *w, const floa
     }
     PD_HIP_CHECK(hipGetLastError());
     return PD_OK;
+}
+
+extern "C" int pd_train_backward(pd_trainer *tr, const pd_weights *w, const float *g_loss, const pd_weight_grads *grads, float *dz_out,
+                                 void *stream) {
+    if (!tr || !g_loss || !grads) {
+        pd_set_error("pd_train_backward: NULL trainer, g_loss or grads");
+        return PD_ERR_INVALID_ARG;
+    }
+    return tr_backward(tr, w, g_loss, nullptr, nullptr, grads, dz_out, stream, "pd_train_backward");
+}
+
+extern "C" int pd_train_backward_ex(pd_trainer *tr, const pd_weights *w, const float *g_loss, const float *g_model_out, const float *g_x0_pred,
+                                    const pd_weight_grads *grads, float *dz_out, void *stream) {
+    if (!tr || !grads) {
+        pd_set_error("pd_train_backward_ex: NULL trainer or grads");
+        return PD_ERR_INVALID_ARG;
+    }
+    if (!g_loss && !g_model_out && !g_x0_pred) {
+        pd_set_error("pd_train_backward_ex: g_loss, g_model_out and g_x0_pred are all NULL: at least one upstream gradient is needed");
+        return PD_ERR_INVALID_ARG;
+    }
+    return tr_backward(tr, w, g_loss, g_model_out, g_x0_pred, grads, dz_out, stream, "pd_train_backward_ex");
 }
 
 extern "C" int pd_train_debug_relu(pd_trainer *tr, int layer, float *dst, long long n_floats, void *stream) {

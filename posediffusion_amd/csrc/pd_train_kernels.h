@@ -587,21 +587,44 @@ __global__ __launch_bounds__(256) void pd_tr_tail_kernel(PdTrTail g) {
     }
 }
 
-// tail backward of one row per wave: gout = g_loss dl -> _last.3 -> ReLU mask (stashed post-ReLU values) = dy -> LayerNorm(hidden)
-// backward = dhid.  gout [M, 9], dy [M, H] (LayerNorm's dgamma / dbeta, _last.3's weight gradient) and dhid [M, H] are written.
+// tail backward of one row per wave: gout -> _last.3 -> ReLU mask (stashed post-ReLU values) = dy -> LayerNorm(hidden) backward = dhid.
+// gout = the sum of the upstream terms that are PRESENT (pd_train_backward_ex), in this order: g_loss dl, g_mo, k_b g_x0 with k_b = 1
+// under pred_x0 and -sqrt_recipm1_alphas_cumprod[t_b] under pred_noise (x_0_pred = c_recip x_t - c_recipm1 model_out, :316).  An absent
+// term is not added: one term alone is that single fp32 product (the plain value for g_mo, and for g_x0 under pred_x0), and the sums are
+// separate roundings, never contracted with a product.  gout [M, 9], dy [M, H] (LayerNorm's dgamma / dbeta, _last.3's weight gradient)
+// and dhid [M, H] are written.
 struct PdTrTailBwd {
     const float *g_loss, *dl, *w3, *lnw, *hid, *hid_post, *stats;
+    const float *g_mo, *g_x0;       // [M, 9] upstreams of model_out and x_0_pred; each of the three may be null (not all)
+    const float *c_recipm1;         // [timesteps]; read only for g_x0 under pred_noise
+    const int *t_b;                 // [B] the forward's clamped timesteps
     const int *nf;                  // [B] frame counts of the forward, or null (uniform)
     float *gout, *dy, *dhid;
-    int M, H, n_frames;
+    int M, H, n_frames, pred_x0;
 };
 __global__ __launch_bounds__(256) void pd_tr_tail_bwd_kernel(PdTrTailBwd g) {
     const int lane = threadIdx.x & 63, m = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (m >= g.M) return;
     float gv = 0.0f;
     if (lane < 9) {
-        // a padding row's g_loss is not read (a product with the stashed dl = 0 would pass a NaN on)
-        gv = pd_tr_is_padding(g.nf, m, g.n_frames) ? 0.0f : g.g_loss[(size_t)m * 9 + lane] * g.dl[(size_t)m * 9 + lane];
+        // a padding row's upstreams are not read (a product with the stashed dl = 0 would pass a NaN on)
+        if (!pd_tr_is_padding(g.nf, m, g.n_frames)) {
+            const size_t at = (size_t)m * 9 + lane;
+            bool have = false;
+            if (g.g_loss) {
+                gv = __fmul_rn(g.g_loss[at], g.dl[at]);
+                have = true;
+            }
+            if (g.g_mo) {
+                const float v = g.g_mo[at];
+                gv = have ? __fadd_rn(gv, v) : v;
+                have = true;
+            }
+            if (g.g_x0) {
+                const float v = g.pred_x0 ? g.g_x0[at] : __fmul_rn(-g.c_recipm1[g.t_b[m / g.n_frames]], g.g_x0[at]);
+                gv = have ? __fadd_rn(gv, v) : v;
+            }
+        }
         g.gout[(size_t)m * 9 + lane] = gv;
     }
     const float mean = g.stats[2 * (size_t)m], rstd = g.stats[2 * (size_t)m + 1];

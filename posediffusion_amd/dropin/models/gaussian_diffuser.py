@@ -14,6 +14,10 @@ diffuser in ``.train()`` mode whose encoder layers have dropout p > 0.  ``engine
 ``engine_grad``) trains the model as built: in ``.train()`` mode the trainer applies the encoder layers' dropout p at their four sites
 with masks of its own counter-based generator -- one int64 seed per call from torch's default CPU generator, so ``torch.manual_seed``
 reproduces a run -- and differentiates that function.  The masks are not torch's: the distribution is the reference's, the bits are not.
+``engine_grad_outputs = True`` (a third opt-in, under ``engine_grad``) returns ``x_0_pred`` with its graph, as the reference's ``p_losses``
+does: any loss written on it -- or on the ``pred_cameras`` that ``PoseDiffusionModel.forward(..., training=True)`` decodes from it -- flows
+back into the denoiser and z (pd_train_backward_ex, pd_pose_to_camera_backward).  The trainer keeps ONE stash: every such term must be
+part of the one total whose ``.backward()`` follows the call.  ``x_t`` stays data.
 The trainer takes sequences of up to 64 frames by default; ``engine_grad_max_frames`` (64 .. 256) raises that (PD_TR_OPT_MAX_FRAMES:
 above 64 frames the attention and its backward run key-tiled kernels).
 ``n_frames=`` on ``p_losses`` / ``forward`` (this package's extension): [B] frame counts of a padded batch -- sequence b has n_frames[b]
@@ -64,6 +68,7 @@ class GaussianDiffusion(nn.Module):
         #                                                denoiser's parameters and z (the trainer's hand-written backward); the default stays forward-only
         self.engine_grad_max_frames = 64               # frames per sequence engine_grad admits; raise it (<= 256) to train on longer sequences (PD_TR_OPT_MAX_FRAMES)
         self.engine_dropout = False                    # True (with engine_grad, in .train() mode): the trainer applies the encoder layers' dropout instead of refusing it
+        self.engine_grad_outputs = False               # True (with engine_grad): x_0_pred is differentiable too, so a loss on it or on the cameras decoded from it flows back
         self.ggs_long_pair_items = False               # True: above 64 frames, take frame pairs of more than 512 matches (PD_OPT_GGS_LONG_PAIR_ITEMS)
 
     # ---- schedule helpers (:190-216): elementwise on the buffers, same names and argument order; the sampler itself has these
@@ -229,6 +234,8 @@ class GaussianDiffusion(nn.Module):
                                "(at most 256) to train on sequences of this length")
         tr = host.get_trainer(self.model, self, B, N, max_frames=limit)
         if grad:
+            if getattr(self, "engine_grad_outputs", False):
+                drop["differentiable_outputs"] = True
             out = p_losses_with_grad(tr, self.model, x_start, z, t, noise, self.loss_type, n_frames=n_frames, **drop)
         else:
             with torch.no_grad():

@@ -4,7 +4,10 @@
 batch_repeat=-1)`` keeps the reference signature; `training=False` returns
 ``{"pred_cameras": PerspectiveCameras(R, T, focal_length) in PyTorch3D NDC, "z": features}``.
 `training=True` (with ``gt_cameras``) follows :111-126: the diffusion results of ``GaussianDiffusion.forward`` on the encoded cameras plus
-``pred_cameras`` decoded from ``x_0_pred`` -- the forward half only: eval-mode network, no grad (dropin/models/gaussian_diffuser.py).
+``pred_cameras`` decoded from ``x_0_pred`` -- by default the forward half only: eval-mode network, no grad (dropin/models/gaussian_diffuser.py).
+With ``diffuser.engine_grad`` and ``diffuser.engine_grad_outputs`` set, ``x_0_pred`` carries grad and so do ``pred_cameras.R``, ``.T`` and
+``.focal_length`` (the decode's backward is pd_pose_to_camera_backward): a camera-space term added to the total reaches the denoiser and,
+through dz, the backbone.
 Extensions: ``z=`` accepts precomputed image features instead of ``image`` (skips the feature extractor).  ``n_frames=`` [B] (training
 branch): frame counts of a padded batch, handed to the diffuser -- ``gt_cameras`` still holds B x N cameras, the padding entries being any
 valid camera; their ``pred_cameras`` entries carry no meaning, and ``loss`` is +0 there (mean over real frames:

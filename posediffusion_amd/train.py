@@ -8,6 +8,10 @@ frames by default and up to 256 with ``max_frames`` / ``set_max_frames`` (PD_TR_
 key-tiled kernels, which at N <= 64 give the bits of the default ones (``set_long_attn``, for the tests).
 Without ``dropout_p`` it is the eval-mode function; with it, the ``.train()``-mode one: dropout at the four sites of every encoder layer
 (``DROPOUT_SITES``), masks from Philox4x32-10 keyed by ``(seed, step)`` and recomputed by the backward (pd_train_forward_dropout).
+``backward(..., g_model_out=, g_x0_pred=)`` / ``p_losses_with_grad(..., differentiable_outputs=True)``: the prediction is differentiable
+too, as the reference's ``p_losses`` returns it -- upstream gradients of ``model_out`` and ``x_0_pred`` enter the backward beside the
+loss's (pd_train_backward_ex), and ``pose_to_camera_with_grad`` differentiates the decode of ``x_0_pred`` into cameras
+(pd_pose_to_camera_backward), so a camera-space loss term reaches the denoiser's parameters and z.
 ``n_frames=`` / ``set_frame_counts``: a padded batch whose sequences have different frame counts (pd_trainer_set_frame_counts) --
 sequence b has n_frames[b] frames in rows 0 .. of its N-row block, padding rows of every output are +0 and what they hold on input is
 never read.  ``loss`` is [B, N, 9] with +0 at padding, so ``loss.mean()`` divides by the PADDED size; the mean over the real frames is
@@ -258,21 +262,29 @@ class PoseTrainer:
         self._pending = self._last_shape = (B, N)
         return out
 
-    def backward(self, params: Dict[str, torch.Tensor], g_loss: torch.Tensor, want: Optional[Iterable[str]] = None) -> Dict[str, torch.Tensor]:
-        """pd_train_backward: ``{name: d sum(g_loss * loss) / d param}`` for the names in ``want`` (state-dict names, plus ``"z"``; default:
-        every parameter and z).  ``params`` must be the tensors of the forward, unmodified.  A name left out is not computed."""
-        if self._pending is None:                # pd_train_backward itself refuses (PD_ERR_STATE): its message is the one raised
+    def backward(self, params: Dict[str, torch.Tensor], g_loss: Optional[torch.Tensor] = None, want: Optional[Iterable[str]] = None,
+                 g_model_out: Optional[torch.Tensor] = None, g_x0_pred: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+        """``{name: dS / d param}`` for the names in ``want`` (state-dict names, plus ``"z"``; default: every parameter and z), with
+        S = sum(g_loss * loss) + sum(g_model_out * model_out) + sum(g_x0_pred * x_0_pred); an upstream left ``None`` is absent (a NULL
+        pointer, not zeros).  ``g_loss`` alone is pd_train_backward, anything else pd_train_backward_ex.  ``params`` must be the tensors
+        of the forward, unmodified.  A name left out is not computed."""
+        ex = g_model_out is not None or g_x0_pred is not None or g_loss is None
+        if self._pending is None:                # the C entry itself refuses (PD_ERR_STATE): its message is the one raised
             dummy = torch.zeros(1, device=self.device)
             _lib.check(self.lib.pd_train_backward(self._h, C.byref(self._weights_struct(None)), dummy.data_ptr(), C.byref(_lib.pd_weight_grads()),
                                                   None, self._stream()), "pd_train_backward")
             raise RuntimeError("pd_train_backward accepted a call without a pending forward")
+        if g_loss is None and g_model_out is None and g_x0_pred is None:      # refused by the C entry (PD_ERR_INVALID_ARG); the stash stays
+            _lib.check(self.lib.pd_train_backward_ex(self._h, C.byref(self._weights_struct(None)), None, None, None,
+                                                     C.byref(_lib.pd_weight_grads()), None, self._stream()), "pd_train_backward_ex")
+            raise RuntimeError("pd_train_backward_ex accepted a call without an upstream gradient")
         B, N = self._pending
         want = set(self.names + ["z"]) if want is None else set(want)
         unknown = want - set(self.names) - {"z"}
         if unknown:
             raise KeyError(f"unknown gradient names {sorted(unknown)}")
         live = self._live(params)
-        g_loss = self._f32(g_loss, (B, N, 9))
+        g_loss, g_model_out, g_x0_pred = (None if g is None else self._f32(g, (B, N, 9)) for g in (g_loss, g_model_out, g_x0_pred))
         grads = {n: torch.empty_like(live[n]) for n in self.names if n in want}
         if "z" in want:
             grads["z"] = torch.empty(B, N, int(self.shape["z_dim"]), device=self.device)
@@ -280,9 +292,16 @@ class PoseTrainer:
         _fill(g, self.num_layers, lambda n: grads[n].data_ptr() if n in grads else None)
         w = self._weights_struct(live)
         self._pending = None
+        dz = grads["z"].data_ptr() if "z" in grads else None
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.pd_train_backward(self._h, C.byref(w), g_loss.data_ptr(), C.byref(g),
-                                                  grads["z"].data_ptr() if "z" in grads else None, self._stream()), "pd_train_backward")
+            if not ex:
+                _lib.check(self.lib.pd_train_backward(self._h, C.byref(w), g_loss.data_ptr(), C.byref(g), dz, self._stream()), "pd_train_backward")
+            else:
+                rc = self.lib.pd_train_backward_ex(self._h, C.byref(w), *(None if u is None else u.data_ptr() for u in (g_loss, g_model_out, g_x0_pred)),
+                                                   C.byref(g), dz, self._stream())
+                if rc == -4 and "g_x0_pred" in _lib.last_error():      # refused for the missing recip tables: nothing ran, the stash is still pending
+                    self._pending = (B, N)
+                _lib.check(rc, "pd_train_backward_ex")
         return grads
 
     def debug_relu(self, layer: int) -> torch.Tensor:
@@ -298,31 +317,44 @@ class PoseTrainer:
 
 
 class _PLossesFn(torch.autograd.Function):
-    """(trainer, loss_type, x_start, z, t, noise, *params) -> (loss, x_0_pred, x_t, model_out); only ``loss`` is differentiable, with
-    respect to the parameters (passed flat so that autograd routes their gradients) and z.  ``loss_type`` is the string, or the tuple
-    ``(loss_type, dropout_p, dropout_sites, seed, step[, n_frames])`` of a forward with dropout and / or frame counts."""
+    """(trainer, loss_type, x_start, z, t, noise, *params) -> (loss, x_0_pred, x_t, model_out), differentiable with respect to the
+    parameters (passed flat so that autograd routes their gradients) and z.  ``loss_type`` is the string, or the tuple
+    ``(loss_type, dropout_p, dropout_sites, seed, step[, n_frames[, differentiable_outputs]])`` of a forward with dropout, frame counts
+    and / or differentiable outputs.  By default only ``loss`` is differentiable.  With ``differentiable_outputs`` so are ``x_0_pred``
+    and ``model_out`` (``x_t`` stays data), and undefined upstream gradients are NOT materialised: an output nobody used reaches
+    pd_train_backward_ex as a NULL pointer, not as a tensor of zeros."""
 
     @staticmethod
     def forward(ctx, trainer, loss_type, x_start, z, t, noise, *params):
         sd = dict(zip(trainer.names, params))
         loss_type, *drop = (loss_type,) if isinstance(loss_type, str) else loss_type
+        ctx.outputs = bool(drop.pop()) if len(drop) == 6 else False
         out = trainer.forward(sd, x_start, z, t, noise, loss_type, *drop)
         ctx.trainer, ctx.generation = trainer, trainer._generation
         ctx.z_shape_dtype = (z.shape, z.dtype, z.device)
         ctx.save_for_backward(*params)
-        ctx.mark_non_differentiable(out["x_0_pred"], out["x_t"], out["model_out"])
+        if ctx.outputs:
+            ctx.set_materialize_grads(False)
+            ctx.mark_non_differentiable(out["x_t"])
+        else:
+            ctx.mark_non_differentiable(out["x_0_pred"], out["x_t"], out["model_out"])
         return out["loss"], out["x_0_pred"], out["x_t"], out["model_out"]
 
     @staticmethod
-    def backward(ctx, g_loss, *_unused):
+    def backward(ctx, g_loss, g_x0_pred=None, _g_xt=None, g_model_out=None):
         tr = ctx.trainer
+        n_in = 6 + len(tr.names)
+        if not ctx.outputs:
+            g_x0_pred = g_model_out = None
+        elif g_loss is None and g_x0_pred is None and g_model_out is None:      # nothing flows back: the stash is left alone
+            return (None,) * n_in
         if ctx.generation != tr._generation or tr._pending is None:
             raise RuntimeError("PoseTrainer keeps ONE activation stash: backward must follow its own forward, once, before the next forward "
                                "on the same trainer (no retain_graph, no two losses in flight)")
         params = ctx.saved_tensors
         needs = ctx.needs_input_grad
         want = [n for n, need in zip(tr.names, needs[6:]) if need] + (["z"] if needs[3] else [])
-        grads = tr.backward(dict(zip(tr.names, params)), g_loss, want)
+        grads = tr.backward(dict(zip(tr.names, params)), g_loss, want, g_model_out=g_model_out, g_x0_pred=g_x0_pred)
         gz = grads.get("z")
         if gz is not None:
             shape, dtype, device = ctx.z_shape_dtype
@@ -331,15 +363,58 @@ class _PLossesFn(torch.autograd.Function):
 
 
 def p_losses_with_grad(trainer: PoseTrainer, denoiser: torch.nn.Module, x_start, z, t, noise, loss_type: str = "l1", dropout_p: float = 0.0,
-                       dropout_sites: int = ALL, seed: int = 0, step: int = 0, n_frames=None) -> Dict[str, torch.Tensor]:
+                       dropout_sites: int = ALL, seed: int = 0, step: int = 0, n_frames=None,
+                       differentiable_outputs: bool = False) -> Dict[str, torch.Tensor]:
     """The p_losses dict of ``trainer.forward`` (same dropout and ``n_frames`` keywords) with ``loss`` attached to ``denoiser``'s
-    parameters (and to z when it requires grad).  With ``n_frames`` the gradient of padding rows of z is +0."""
+    parameters (and to z when it requires grad).  With ``n_frames`` the gradient of padding rows of z is +0.
+    ``differentiable_outputs``: ``x_0_pred`` and ``model_out`` are attached too, so any loss written on them (or on cameras decoded from
+    ``x_0_pred``) flows back through pd_train_backward_ex; ``x_t`` stays data.  Still ONE stash: every term must be part of the one
+    total whose ``.backward()`` follows this forward (no ``retain_graph``)."""
     if n_frames is not None:
         n_frames = check_frame_counts(n_frames, x_start.shape[0], x_start.shape[1])
     named = dict(denoiser.named_parameters())
     params = [named[n] for n in trainer.names]
     mode = loss_type if float(dropout_p) == 0.0 and 0 <= int(dropout_sites) <= ALL else (loss_type, dropout_p, dropout_sites, seed, step)
-    if n_frames is not None:
+    if n_frames is not None or differentiable_outputs:
         mode = ((loss_type, 0.0, ALL, 0, 0) if isinstance(mode, str) else mode) + (n_frames,)
+    if differentiable_outputs:
+        mode = mode + (True,)
     loss, x0, xt, mo = _PLossesFn.apply(trainer, mode, x_start, z, t, noise, *params)
     return {"loss": loss, "x_0_pred": x0, "x_t": xt, "model_out": mo}
+
+
+class _PoseToCameraFn(torch.autograd.Function):
+    """pose_encoding_to_camera with a gradient: (enc [n, 9], bias, min, max, engine) -> (R [n, 3, 3], T [n, 3], focal [n, 2]) by
+    pd_pose_to_camera_ex, backward by pd_pose_to_camera_backward (which recomputes the decode from ``enc``).  Undefined upstream
+    gradients are not materialised: an output nobody used is a NULL pointer."""
+
+    @staticmethod
+    def forward(ctx, enc, bias, fmin, fmax, engine):
+        enc32 = enc.detach().to(device=engine.device, dtype=torch.float32).reshape(-1, 9).contiguous()
+        R, T, f = engine.pose_to_camera(enc32, bias, fmin, fmax)
+        ctx.save_for_backward(enc32)
+        ctx.args = (float(bias), float(fmin), float(fmax), enc.shape, enc.dtype, enc.device)
+        ctx.set_materialize_grads(False)
+        return R, T, f
+
+    @staticmethod
+    def backward(ctx, g_R, g_T, g_f):
+        if g_R is None and g_T is None and g_f is None:
+            return None, None, None, None, None
+        enc32, = ctx.saved_tensors
+        bias, fmin, fmax, shape, dtype, device = ctx.args
+        n = enc32.shape[0]
+        ups = [None if g is None else g.detach().to(device=enc32.device, dtype=torch.float32).reshape(n, w).contiguous()
+               for g, w in ((g_R, 9), (g_T, 3), (g_f, 2))]
+        out = torch.empty_like(enc32)
+        with torch.cuda.device(enc32.device):
+            _lib.check(_lib.load().pd_pose_to_camera_backward(enc32.data_ptr(), *(None if u is None else u.data_ptr() for u in ups), n, bias, fmin,
+                                                              fmax, out.data_ptr(), torch.cuda.current_stream(enc32.device).cuda_stream),
+                       "pd_pose_to_camera_backward")
+        return out.reshape(shape).to(device=device, dtype=dtype), None, None, None, None
+
+
+def pose_to_camera_with_grad(engine, enc, log_focal_length_bias: float = 1.8, min_focal_length: float = 0.1, max_focal_length: float = 20.0):
+    """(R, T, focal_length) of ``engine.pose_to_camera`` attached to ``enc`` (the drop-in's pose_encoding_to_camera uses it when grad mode
+    is on and ``enc`` requires grad)."""
+    return _PoseToCameraFn.apply(enc, log_focal_length_bias, min_focal_length, max_focal_length, engine)
