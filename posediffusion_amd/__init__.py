@@ -11,9 +11,18 @@ host-side mirror of the reference's Python interface for that path (``dropin/``)
     dropin/    `models` + `util` packages with the reference's names (Hydra _target_ registry)
     synth.py   synthetic weights / features / matches for tests and bench
     shard.py   one-process-per-GPU sharding of independent sequences + final gather
+    optim.py   EngineAdamW / clip_grad_norm_: the optimiser step of training on the engine
 """
 import os
 
 DROPIN_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "dropin")
 
-__all__ = ["DROPIN_PATH"]
+__all__ = ["DROPIN_PATH", "EngineAdamW", "clip_grad_norm_"]
+
+
+def __getattr__(name):
+    # the optimiser's names, resolved on first use: importing the package alone must not import torch
+    if name in ("EngineAdamW", "clip_grad_norm_"):
+        from . import optim
+        return getattr(optim, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -98,6 +98,7 @@ PD_OPT_GGS_LONG_PAIR_ITEMS = 8  # 0 (default) / 1: above 64 frames a frame pair 
 PD_DROP_ATTN, PD_DROP_RESID1, PD_DROP_FF, PD_DROP_RESID2, PD_DROP_ALL = 1, 2, 4, 8, 15   # pd_train_forward_dropout's sites (include/pd_engine_train.h)
 PD_TR_OPT_MAX_FRAMES, PD_TR_OPT_LONG_ATTN = 1, 2   # pd_trainer_set_option (include/pd_engine_train.h): frame limit 64 .. 256; key-tiled attention at every N
 PD_MATCH_HINT_ONE_ORDER = 1 << 30   # pd_match_hints.max_pairs flag: every frame pair in one order only (hloc's i < j pairs)
+PD_OPTIM_CHUNK = 4096   # include/pd_engine_optim.h: elements of one tensor per partial sum of the gradient norm and per workgroup turn
 
 
 class pd_ggs_cfg(C.Structure):
@@ -108,6 +109,16 @@ class pd_ggs_cfg(C.Structure):
 
 class pd_match_hints(C.Structure):
     _fields_ = [("max_pairs", C.c_int32), ("max_matches_per_pair", C.c_int32)]
+
+
+class pd_optim_tensor(C.Structure):
+    """include/pd_engine_optim.h: one parameter that has a gradient this step (device pointers as integers)"""
+    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p),
+                ("numel", C.c_int64), ("group", C.c_int32), ("step", C.c_int32)]
+
+
+class pd_optim_group(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("lr", "beta1", "beta2", "eps", "weight_decay")]
 
 
 # name -> (restype, argtypes); kept in one table so the "exports every declared symbol" test and
@@ -185,6 +196,14 @@ VIT_TRAIN_SIGNATURES = {
     "pd_vit_train_forward": (_i, [_vp, C.POINTER(pd_vit_weights), _vp, _i, _i, _i, C.POINTER(C.c_double), _i, C.POINTER(_vp), _vp, _vp]),
     "pd_vit_train_backward": (_i, [_vp, C.POINTER(pd_vit_weights), _vp, C.POINTER(pd_vit_weight_grads), _vp]),
 }
+# the exports of include/pd_engine_optim.h: global-norm clipping and AdamW (a fourth extension table)
+OPTIM_SIGNATURES = {
+    "pd_optimizer_create": (_i, [_i, _i64, C.POINTER(_vp)]),
+    "pd_optimizer_destroy": (None, [_vp]),
+    "pd_optim_grad_norm": (_i, [_vp, C.POINTER(pd_optim_tensor), _i, _vp, _vp]),
+    "pd_optim_clip_grad_norm": (_i, [_vp, C.POINTER(pd_optim_tensor), _i, C.c_double, _vp, _vp]),
+    "pd_optim_adamw_step": (_i, [_vp, C.POINTER(pd_optim_tensor), _i, C.POINTER(pd_optim_group), _i, C.c_double, _vp, _vp]),
+}
 
 _lib = None
 
@@ -214,7 +233,7 @@ def load():
             "There is no CPU fallback.")
     import torch  # noqa: F401  (loads the HIP runtime first)
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-    for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **TRAIN_SIGNATURES, **VIT_TRAIN_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **TRAIN_SIGNATURES, **VIT_TRAIN_SIGNATURES, **OPTIM_SIGNATURES}.items():
         if os.environ.get("PD_ENGINE_LIB") and not hasattr(lib, name):
             continue              # an older build under A / B lacks the newest debug exports
         fn = getattr(lib, name)   # AttributeError here = library does not match the header

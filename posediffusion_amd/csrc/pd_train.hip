@@ -2,7 +2,7 @@
 // stash, and the backward of the diffusion loss through the Denoiser to every parameter and to z.  Kernels: pd_train_kernels.h.
 //
 // Replaces (paths relative to the reference's pose_diffusion/): the autograd graph of models/gaussian_diffuser.py:308-327 over
-// models/denoiser.py:53-76 that train.py:245-251 back-propagates.  The optimiser, LR schedule and clipping stay PyTorch's.
+// models/denoiser.py:53-76 that train.py:245-251 back-propagates.  The LR schedule stays PyTorch's; clipping and the optimiser step are pd_optim.hip's.
 //
 // Forward (the generic path's structure, DESIGN 3.5, on the caller's live weights):
 //   q_sample -> time embedding of the B timesteps -> _first's rows -> _first GEMM -> per layer { LN1 (+stats) -> in_proj GEMM -> attention ->
