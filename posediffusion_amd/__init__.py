@@ -12,12 +12,13 @@ host-side mirror of the reference's Python interface for that path (``dropin/``)
     synth.py   synthetic weights / features / matches for tests and bench
     shard.py   one-process-per-GPU sharding of independent sequences + final gather
     optim.py   EngineAdamW / clip_grad_norm_: the optimiser step of training on the engine
+    cameras.py normalize_cameras_batch: ground-truth camera normalisation (util/normalize_cameras.py) on the engine
 """
 import os
 
 DROPIN_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "dropin")
 
-__all__ = ["DROPIN_PATH", "EngineAdamW", "clip_grad_norm_"]
+__all__ = ["DROPIN_PATH", "EngineAdamW", "clip_grad_norm_", "normalize_cameras_batch"]
 
 
 def __getattr__(name):
@@ -25,4 +26,7 @@ def __getattr__(name):
     if name in ("EngineAdamW", "clip_grad_norm_"):
         from . import optim
         return getattr(optim, name)
+    if name == "normalize_cameras_batch":
+        from . import cameras
+        return cameras.normalize_cameras_batch
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -121,6 +121,15 @@ class pd_optim_group(C.Structure):
     _fields_ = [(n, C.c_double) for n in ("lr", "beta1", "beta2", "eps", "weight_decay")]
 
 
+class pd_cam_norm_cfg(C.Structure):
+    """include/pd_engine_cameras.h: scale_mode 0 none / 1 optical-axis intersection / 2 sqrt(||T||_F); first_camera 0 off / 1 full /
+    2 rotation only; normalize_T 0 / 1"""
+    _fields_ = [(n, C.c_int) for n in ("scale_mode", "first_camera", "normalize_T")]
+
+
+PD_CAM_OK, PD_CAM_ZERO_SCALE, PD_CAM_RANK, PD_CAM_NON_FINITE, PD_CAM_BAD_COUNT = range(5)   # pd_normalize_cameras' status_out
+
+
 # name -> (restype, argtypes); kept in one table so the "exports every declared symbol" test and
 # the binding cannot drift apart.
 _vp, _i, _i64 = C.c_void_p, C.c_int, C.c_int64
@@ -204,6 +213,11 @@ OPTIM_SIGNATURES = {
     "pd_optim_clip_grad_norm": (_i, [_vp, C.POINTER(pd_optim_tensor), _i, C.c_double, _vp, _vp]),
     "pd_optim_adamw_step": (_i, [_vp, C.POINTER(pd_optim_tensor), _i, C.POINTER(pd_optim_group), _i, C.c_double, _vp, _vp]),
 }
+# the exports of include/pd_engine_cameras.h: ground-truth camera normalisation (a fifth extension table)
+CAMERA_SIGNATURES = {
+    "pd_normalize_cameras": (_i, [_vp, _vp, _i, _i, _vp, C.POINTER(pd_cam_norm_cfg), _vp, _vp, _vp, C.c_float, C.c_float, C.c_float,
+                                  _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+}
 
 _lib = None
 
@@ -233,7 +247,8 @@ def load():
             "There is no CPU fallback.")
     import torch  # noqa: F401  (loads the HIP runtime first)
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-    for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **TRAIN_SIGNATURES, **VIT_TRAIN_SIGNATURES, **OPTIM_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **TRAIN_SIGNATURES, **VIT_TRAIN_SIGNATURES, **OPTIM_SIGNATURES,
+                                   **CAMERA_SIGNATURES}.items():
         if os.environ.get("PD_ENGINE_LIB") and not hasattr(lib, name):
             continue              # an older build under A / B lacks the newest debug exports
         fn = getattr(lib, name)   # AttributeError here = library does not match the header

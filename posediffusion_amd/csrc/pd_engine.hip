@@ -7,6 +7,7 @@
 //   util/camera_transform.py:108-129     camera_to_pose_encoding (pd_camera_to_pose)
 //   models/gaussian_diffuser.py:308-327  p_losses, forward half in eval mode (pd_p_losses; kernels in pd_denoiser*.hip)
 #include "pd_internal.h"
+#include "pd_pose_encode.h"
 
 #include <algorithm>
 
@@ -117,9 +118,6 @@ static int counts_unsupported(const pd_engine *eng, const char *who) {
     return PD_ERR_UNSUPPORTED;
 }
 
-// torch.clamp: NaN stays NaN (fminf / fmaxf would return the bound)
-__device__ __forceinline__ float pd_clamp_torch(float v, float lo, float hi) { return v != v ? v : fminf(fmaxf(v, lo), hi); }
-
 __global__ void pd_camera_kernel(const float *__restrict__ enc, int n, float *__restrict__ R, float *__restrict__ T,
                                  float *__restrict__ F, float fl_bias, float fl_min, float fl_max) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
@@ -190,46 +188,13 @@ __global__ void pd_camera_bwd_kernel(const float *__restrict__ enc, const float 
     }
 }
 
-// camera_to_pose_encoding (camera_transform.py:108-129), one thread per camera: enc =[T | matrix_to_quaternion(R) | log(clamp(focal)) - bias].
-// The quaternion follows current pytorch3d (transforms/rotation_conversions.py matrix_to_quaternion): the four candidates
-// q_abs = sqrt(max(0, 1 +- m00 +- m11 +- m22)), the candidate row of the largest q_abs divided by 2 max(q_abs, 0.1), standardised to a
-// non-negative real part.  pytorch3d itself is not a dependency of this project: the yardstick of this kernel is the fp64 restatement of
-// that function in tests/pose_codec_checks.py, not a fixture generated by the reference.
+// camera_to_pose_encoding (camera_transform.py:108-129), one thread per camera: enc =[T | matrix_to_quaternion(R) | log(clamp(focal)) - bias];
+// the arithmetic of one camera is pd_camera_to_pose_row (pd_pose_encode.h), shared with pd_normalize_cameras_kernel (pd_cameras.hip).
 __global__ void pd_camera_to_pose_kernel(const float *__restrict__ R, const float *__restrict__ T, const float *__restrict__ F, int n,
                                          float fl_bias, float fl_min, float fl_max, float *__restrict__ enc) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= n) return;
-    const float *m = R + (size_t)c * 9;
-    const float m00 = m[0], m01 = m[1], m02 = m[2], m10 = m[3], m11 = m[4], m12 = m[5], m20 = m[6], m21 = m[7], m22 = m[8];
-    const float s[4] = {1.0f + m00 + m11 + m22, 1.0f + m00 - m11 - m22, 1.0f - m00 + m11 - m22, 1.0f - m00 - m11 + m22};
-    float qa[4];
-    int best = 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        qa[i] = s[i] > 0.0f ? sqrtf(s[i]) : 0.0f;               // _sqrt_positive_part
-        if (qa[i] > qa[best]) best = i;                         // argmax, the first of equal candidates
-    }
-    const float cand[4][4] = {{qa[0] * qa[0], m21 - m12, m02 - m20, m10 - m01},
-                              {m21 - m12, qa[1] * qa[1], m10 + m01, m02 + m20},
-                              {m02 - m20, m10 + m01, qa[2] * qa[2], m12 + m21},
-                              {m10 - m01, m20 + m02, m21 + m12, qa[3] * qa[3]}};
-    float q[4] = {cand[0][0], cand[0][1], cand[0][2], cand[0][3]}, qb = qa[0];
-#pragma unroll
-    for (int i = 1; i < 4; ++i)
-        if (best == i) {
-            q[0] = cand[i][0]; q[1] = cand[i][1]; q[2] = cand[i][2]; q[3] = cand[i][3];
-            qb = qa[i];
-        }
-    const float den = 2.0f * fmaxf(qb, 0.1f);
-    const float sign = q[0] / den < 0.0f ? -1.0f : 1.0f;        // standardize_quaternion
-    float *o = enc + (size_t)c * 9;
-    o[0] = T[c * 3 + 0];
-    o[1] = T[c * 3 + 1];
-    o[2] = T[c * 3 + 2];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) o[3 + i] = sign * (q[i] / den);
-    o[7] = logf(pd_clamp_torch(F[c * 2 + 0], fl_min, fl_max)) - fl_bias;
-    o[8] = logf(pd_clamp_torch(F[c * 2 + 1], fl_min, fl_max)) - fl_bias;
+    pd_camera_to_pose_row(R + (size_t)c * 9, T + c * 3, F + c * 2, fl_bias, fl_min, fl_max, enc + (size_t)c * 9);
 }
 
 // ---- lifecycle ----------------------------------------------------------------------------------
