@@ -13,12 +13,13 @@ host-side mirror of the reference's Python interface for that path (``dropin/``)
     shard.py   one-process-per-GPU sharding of independent sequences + final gather
     optim.py   EngineAdamW / clip_grad_norm_: the optimiser step of training on the engine
     cameras.py normalize_cameras_batch: ground-truth camera normalisation (util/normalize_cameras.py) on the engine
+    images.py  prepare_training_images: crop, antialiased resize and colour jitter of a batch's decoded frames (datasets/co3d_v2.py) on the engine
 """
 import os
 
 DROPIN_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "dropin")
 
-__all__ = ["DROPIN_PATH", "EngineAdamW", "clip_grad_norm_", "normalize_cameras_batch"]
+__all__ = ["DROPIN_PATH", "EngineAdamW", "clip_grad_norm_", "normalize_cameras_batch", "prepare_training_images"]
 
 
 def __getattr__(name):
@@ -29,4 +30,7 @@ def __getattr__(name):
     if name == "normalize_cameras_batch":
         from . import cameras
         return cameras.normalize_cameras_batch
+    if name == "prepare_training_images":
+        from . import images
+        return images.prepare_training_images
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -130,6 +130,21 @@ class pd_cam_norm_cfg(C.Structure):
 PD_CAM_OK, PD_CAM_ZERO_SCALE, PD_CAM_RANK, PD_CAM_NON_FINITE, PD_CAM_BAD_COUNT = range(5)   # pd_normalize_cameras' status_out
 
 
+class pd_img_frame(C.Structure):
+    """include/pd_engine_images.h: one decoded frame inside the pixel buffer and its square crop box (colour: index of its draw, -1 none)"""
+    _fields_ = [("offset", C.c_int64)] + [(n, C.c_int32) for n in ("height", "width", "x0", "y0", "side", "colour")]
+
+
+class pd_img_colour(C.Structure):
+    """include/pd_engine_images.h: one sequence's colour draw (order: a permutation of 0 brightness, 1 contrast, 2 saturation, 3 hue)"""
+    _fields_ = ([("jitter", C.c_int32), ("order", C.c_int32 * 4)] + [(n, C.c_float) for n in ("brightness", "contrast", "saturation", "hue")]
+                + [(n, C.c_int32) for n in ("grayscale", "erase_top", "erase_left", "erase_h", "erase_w")])
+
+
+PD_IMG_OK, PD_IMG_BAD_SIDE, PD_IMG_BAD_SIZE, PD_IMG_BAD_COLOUR, PD_IMG_BAD_ORDER, PD_IMG_BAD_ERASE = range(6)   # pd_train_images' status_out
+PD_IMG_MAX_SIDE, PD_IMG_MAX_SIZE, PD_IMG_MAX_FRAMES = 6144, 1024, 65535
+
+
 # name -> (restype, argtypes); kept in one table so the "exports every declared symbol" test and
 # the binding cannot drift apart.
 _vp, _i, _i64 = C.c_void_p, C.c_int, C.c_int64
@@ -219,6 +234,12 @@ CAMERA_SIGNATURES = {
                                   _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
+# the exports of include/pd_engine_images.h: training images, crop + antialiased resize + colour draw (a sixth extension table)
+IMAGE_SIGNATURES = {
+    "pd_train_images_workspace_bytes": (C.c_longlong, [_i, _i]),
+    "pd_train_images": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, C.c_longlong, _vp]),
+}
+
 _lib = None
 
 
@@ -248,7 +269,7 @@ def load():
     import torch  # noqa: F401  (loads the HIP runtime first)
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
     for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **TRAIN_SIGNATURES, **VIT_TRAIN_SIGNATURES, **OPTIM_SIGNATURES,
-                                   **CAMERA_SIGNATURES}.items():
+                                   **CAMERA_SIGNATURES, **IMAGE_SIGNATURES}.items():
         if os.environ.get("PD_ENGINE_LIB") and not hasattr(lib, name):
             continue              # an older build under A / B lacks the newest debug exports
         fn = getattr(lib, name)   # AttributeError here = library does not match the header
